@@ -2,9 +2,10 @@
 """Headline benchmark: training throughput (supervoxel-graphs/sec) of 7xGraphSAGE-pool-256
 on synthetic 15k-node supervoxel graphs, N MI355X GPUs (BASELINE.json metric, config C2).
 
-  python bench.py --gpus N --steps 20 --warmup 5          (N > 1: starts its own torchrun child)
+  python bench.py --gpus N --steps 600 --warmup 5         (N > 1: starts its own torchrun child)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+  python bench.py --steps K --dump-outputs DIR            (also writes what the last timed step computed)
 
 One "step" = forward + class-weighted cross-entropy + backward + (gradient all-reduce when
 N > 1) + AdamW update on one batch of `--graphs-per-gpu` (default 4) 15 000-node lattice
@@ -12,10 +13,20 @@ graphs per GPU (N_b = 60 000 nodes, E_b = 345 400 edges), in_feats 4, fp32, laye
 [256]*7 => 8 SAGEConv layers.  Inputs are resident in HBM before the timed region.  Weak
 scaling: per-GPU work is fixed, global batch = graphs-per-gpu x N.
 
-Timing: after W warm-up steps the block of EXACTLY K steps (barrier + synchronize on both
-sides, MAX over ranks) is timed `--blocks` times (default 30: ~3 s of GPU time at the headline shape); `value` is the MEDIAN block's
-rate and `blocks` carries min / median / max.  One further block of the same K steps runs
-with HIP events around every launch of the kernels the roofline objects describe.
+Timing: after W warm-up steps EXACTLY K steps are timed, as `--blocks` consecutive blocks of
+near-equal size (barrier + synchronize on both sides of each block, MAX over ranks; by default
+one block per 20 steps, at most 30: the default K = 600 is ~2.5 s of GPU time at the headline
+shape).  `ms_per_step` is the MEDIAN block's time per step, `value` its rate, and `blocks`
+carries min / median / max.  One further run of K steps follows with HIP events around every
+launch of the kernels the roofline objects describe.
+
+--dump-outputs DIR writes, once the timed blocks are done, what the last timed step computed
+as DIR/<name>.npy (float32): for the training configurations the step's loss (`loss`) and the
+network's parameters after its optimizer update (`param.<state_dict key>`); for --config c5 the
+logits of the step's batch (`logits`) and, of every projected 240^3 volume, the 4-float rows of
+the same seeded sample of voxels (`volumes_sample`, [graphs, voxels, 4]).  At most 64 MiB in
+all; rank 0's outputs under torchrun.  Inputs and initial weights are seeded, so two runs
+with the same arguments start from the same state.
 
 Rank 0 prints ONE JSON line with the throughput, plus
   "roofline":     K11, the MFMA fp32 GEMM kernel most of the step is spent in: flops of every
@@ -59,8 +70,12 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak BW (spec)
-MFMA_F32_PEAK_TFLOPS = 157.3   # same guide: dense fp32 MFMA (v_mfma_f32_32x32x2_f32) peak
+HBM_PEAK_GBS = 8000.0          # MI355X HBM3E peak BW (spec)
+MFMA_F32_PEAK_TFLOPS = 157.3   # MI355X dense fp32 MFMA (v_mfma_f32_32x32x2_f32) peak
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: all arrays together
+DUMP_VOXELS = 1 << 19          # --config c5 --dump-outputs: sampled voxels per volume (fewer if the limit needs it)
+STEPS_PER_AUTO_BLOCK = 20      # default --blocks: one block per this many timed steps ...
+MAX_AUTO_BLOCKS = 30           # ... and at most this many blocks
 IN_FEATS = 4
 N_CLASSES = 4
 CLASS_WEIGHTS = [0.1, 1.0, 2.0, 2.0]
@@ -87,20 +102,54 @@ CONFIGS = {
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=600, help="timed steps, in all blocks together")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--blocks", type=int, default=30,
-                    help="the --steps block is timed this many times; value = the median block")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help=f"split the --steps timed steps into this many blocks (at most one per step); value = the "
+                         f"median block (default: one per {STEPS_PER_AUTO_BLOCK} steps, at most {MAX_AUTO_BLOCKS})")
     ap.add_argument("--graphs-per-gpu", type=int, default=None,
                     help="graphs in one rank's batch (default 4; 8 for --config c4, 6 for --config real)")
     ap.add_argument("--graph-kind", default="lattice", choices=["lattice", "random", "selfloop"])
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=5, help="timed CPU-oracle steps after one warm-up (SURVEY.md §8d: >= 5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MiB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.blocks is not None and args.blocks < 1:
+        ap.error("--blocks must be at least 1")
     if args.graphs_per_gpu is None:
         args.graphs_per_gpu = CONFIGS[args.config].get("graphs_per_gpu", 4)
     return args
+
+
+def block_sizes(steps, blocks=None):
+    """The timed steps as consecutive blocks of near-equal size (larger blocks first); they sum to `steps`."""
+    if blocks is None:
+        blocks = min(MAX_AUTO_BLOCKS, max(1, steps // STEPS_PER_AUTO_BLOCK))
+    n = min(blocks, steps)
+    return [steps // n + (1 if b < steps % n else 0) for b in range(n)]
+
+
+def voxel_sample(n_voxels, n_sample):
+    """Sorted flat voxel indices of the --dump-outputs volume sample: fixed seed, the same for every volume."""
+    if n_sample >= n_voxels:
+        return np.arange(n_voxels)
+    return np.sort(np.random.default_rng(0).choice(n_voxels, size=n_sample, replace=False))
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> tensor.  Writes out_dir/<name>.npy as float32; refuses more than DUMP_LIMIT_BYTES in all."""
+    host = {name: t.detach().to("cpu", torch.float32).numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"dumped {len(host)} arrays ({total / 2 ** 20:.1f} MiB) to {out_dir}")
 
 
 def log(msg):
@@ -347,7 +396,16 @@ def main():
                 logits = model.net(g, feats)
                 vols = [ops.project_rows(svs, logits[k * per_graph:(k + 1) * per_graph], bg)
                         for k in range(args.graphs_per_gpu)]
-            return vols[-1][0, 0, 0, 0]
+            return logits, vols
+
+        def last_value(out):
+            return out[1][-1][0, 0, 0, 0]
+
+        def step_outputs(out):
+            logits, vols = out
+            room = (DUMP_LIMIT_BYTES - logits.numel() * 4) // (len(vols) * 4 * 4)
+            idx = torch.from_numpy(voxel_sample(svs.numel(), min(DUMP_VOXELS, max(room, 0)))).to(device)
+            return {"logits": logits, "volumes_sample": torch.stack([v.reshape(-1, 4)[idx] for v in vols])}
     elif args.config == "real":
         model.net.train()
 
@@ -371,18 +429,25 @@ def main():
             g, feats, labels = batches[i % len(batches)]
             return model.train_step(g, feats, labels)
 
+    if args.config != "c5":
+        def last_value(loss):
+            return loss
+
+        def step_outputs(loss):    # what a training step hands back: its loss, and the parameters it updated
+            return {"loss": loss, **{"param." + k: v for k, v in model.net.state_dict().items()}}
+
     def fence():
         if world > 1:
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    def timed_block(step=step):
-        """EXACTLY --steps steps between two fences; (seconds [max over ranks], host enqueue s, last)."""
+    def timed_block(n_steps, step=step):
+        """EXACTLY n_steps steps between two fences; (seconds [max over ranks], host enqueue s, last output, own s)."""
         fence()
         t0 = time.perf_counter()
-        for i in range(args.steps):
+        for i in range(n_steps):
             last = step(i)
-        enqueue = time.perf_counter() - t0      # CPU time to enqueue K steps (no sync inside)
+        enqueue = time.perf_counter() - t0      # CPU time to enqueue the steps (no sync inside)
         fence()
         elapsed = time.perf_counter() - t0
         own = elapsed
@@ -392,36 +457,41 @@ def main():
             elapsed = float(t.item())
         return elapsed, enqueue, last, own
 
+    sizes = block_sizes(args.steps, args.blocks)
     log(f"rank {rank}/{world}: {args.config} batches resident (N_b={n_b}, E_b={e_b}); warm-up")
     for i in range(args.warmup):
         step(i)
-    log(f"timed region: {args.blocks} blocks of {args.steps} steps")
-    blocks = [timed_block() for _ in range(args.blocks)]
-    times = sorted(b[0] for b in blocks)
-    elapsed = float(np.median(times))            # the headline: median block
-    host_enqueue = float(np.median([b[1] for b in blocks]))
+    log(f"timed region: {args.steps} steps in {len(sizes)} blocks of {sizes[-1]}-{sizes[0]} steps")
+    blocks = [timed_block(n) for n in sizes]
+    per_step = sorted(b[0] / n for b, n in zip(blocks, sizes))
+    step_s = float(np.median(per_step))          # the headline: median block, seconds per step
+    host_enqueue = float(np.median([b[1] / n for b, n in zip(blocks, sizes)]))
     last = blocks[-1][2]
-    # one more block of the same K steps with HIP events around every launch of the kernels the
-    # roofline objects describe (kept out of the blocks above: events cost a few us per launch)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(last))
+    last = last_value(last)
+    # K more steps with HIP events around every launch of the kernels the roofline objects describe
+    # (kept out of the blocks above: events cost a few us per launch)
     timers.enabled = ops.INSTRUMENTED = True
-    instrumented = timed_block()[0]
+    instrumented = timed_block(args.steps)[0]
     timers.enabled = ops.INSTRUMENTED = False
     # per-rank view (N > 1): every rank's own wall time for the last timed block and the time its all-reduce launches took
     # (a rank that finishes its graphs early waits there: the spread between ranks IS the load imbalance)
     per_rank = None
     if world > 1:
         ar = timers.summary("all_reduce")
-        mine = torch.tensor([blocks[-1][3], (ar["total_ms"] / ar["launches"]) if ar else 0.0], dtype=torch.float64, device=device)
+        mine = torch.tensor([blocks[-1][3] / sizes[-1], (ar["total_ms"] / ar["launches"]) if ar else 0.0],
+                            dtype=torch.float64, device=device)
         everyone = [torch.zeros_like(mine) for _ in range(world)]
         torch.distributed.all_gather(everyone, mine)
         per_rank = [[float(v) for v in t.tolist()] for t in everyone]
     # --config real: the same steps on two RESIDENT batches (every rank; the blocks fence collectively): what the host path costs
-    resident = sorted(timed_block(resident_step)[:2] for _ in range(3))[1] if args.config == "real" else None
+    resident = sorted(timed_block(args.steps, resident_step)[:2] for _ in range(3))[1] if args.config == "real" else None
     log("block seconds in order: " + " ".join(f"{b[0]:.4f}" for b in blocks))
-    log(f"blocks: median {elapsed:.4f} s, min {times[0]:.4f}, max {times[-1]:.4f} for {args.steps} steps; "
-        f"instrumented block {instrumented:.4f} s (host enqueue {1e3 * host_enqueue / args.steps:.2f} ms/step)")
+    log(f"blocks: median {1e3 * step_s:.4f} ms/step, min {1e3 * per_step[0]:.4f}, max {1e3 * per_step[-1]:.4f} over "
+        f"{args.steps} steps; instrumented run {instrumented:.4f} s (host enqueue {1e3 * host_enqueue:.2f} ms/step)")
     global_batch = args.graphs_per_gpu * world
-    value = global_batch * args.steps / elapsed
+    value = global_batch / step_s
 
     if rank == 0:
         arg_b = batches[0][0].arg_bytes
@@ -448,11 +518,11 @@ def main():
             "c5": "C5: no-grad forward of 7xGraphSAGE-pool-256 + logits projection of every graph to an "
                   "int16 240^3 partition (fp32 x4 rows)",
         }
-        rate = lambda t: global_batch * args.steps / t          # noqa: E731
+        rate = lambda t: global_batch * args.steps / t          # noqa: E731  (t: seconds for --steps steps)
         result = {
             "metric": cfg["metric"], "value": round(value, 3),
             "unit": "volumes/s" if args.config == "c5" else "graphs/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * step_s, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic",
             "config": {"workload": f"{workloads[args.config]}, {args.graphs_per_gpu} x {n_b // args.graphs_per_gpu}-node/"
@@ -460,10 +530,10 @@ def main():
                                    f"{cfg.get('in_feats', IN_FEATS)}-chan feat, fp32",
                        "global_batch": global_batch, "nodes_per_batch": n_b, "edges_per_batch": e_b,
                        "parallelism": f"dp{world}", "last_value": round(float(last), 6),
-                       "host_enqueue_ms_per_step": round(1e3 * host_enqueue / args.steps, 3)},
-            "blocks": {"n": args.blocks, "steps_per_block": args.steps, "value": "median block",
-                       "median": round(rate(elapsed), 3), "min": round(rate(times[-1]), 3),
-                       "max": round(rate(times[0]), 3)},
+                       "host_enqueue_ms_per_step": round(1e3 * host_enqueue, 3)},
+            "blocks": {"n": len(sizes), "steps_per_block": sizes, "value": "median block",
+                       "median": round(value, 3), "min": round(global_batch / per_step[-1], 3),
+                       "max": round(global_batch / per_step[0], 3)},
             "ranks": world,
             "backend": torch.distributed.get_backend() if world > 1 else None,
         }
@@ -541,7 +611,7 @@ def main():
                                     "avg_us": round(1e3 * ar["total_ms"] / ar["launches"], 1),
                                     "launches_timed": ar["launches"]}
         if per_rank is not None:
-            step_ms = [1e3 * r[0] / args.steps for r in per_rank]
+            step_ms = [1e3 * r[0] for r in per_rank]
             result["per_rank"] = {"step_ms": [round(v, 4) for v in step_ms], "step_ms_max": round(max(step_ms), 4),
                                   "step_ms_min": round(min(step_ms), 4),
                                   "all_reduce_us": [round(1e3 * r[1], 1) for r in per_rank],

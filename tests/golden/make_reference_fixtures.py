@@ -1,6 +1,7 @@
 """Generate golden fixtures by IMPORTING the reference's pure-numpy modules.
 
-Run in the build container only (needs /root/reference):   python tests/golden/make_reference_fixtures.py
+Needs a checkout of the reference (rsinghlab/GNN-Tumor-Seg); not part of the test suite:
+    python tests/golden/make_reference_fixtures.py /path/to/GNN-Tumor-Seg
 Writes data files (inputs + expected outputs) next to this script; no reference source is
 copied.  Importable reference modules: data_processing.graph_io,
 utils.hyperparam_helpers, utils.training_helpers, data_processing.image_processing,
@@ -16,7 +17,9 @@ from contextlib import redirect_stdout
 
 import numpy as np
 
-REF = "/root/reference"
+if len(sys.argv) != 2:
+    raise SystemExit(f"usage: python {sys.argv[0]} /path/to/GNN-Tumor-Seg")
+REF = os.path.abspath(sys.argv[1])
 OUT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REF)
 if not hasattr(np, "bool"):

@@ -26,17 +26,45 @@ def test_algorithmic_bytes_match_design_doc():
     assert bench.host_cores() >= 1
     assert set(bench.CONFIGS) == {"c2", "c3", "c4", "c5", "real"}
     assert bench.CONFIGS["c4"]["graphs_per_gpu"] == 8          # BASELINE.json: global batch 64 over 8 GPUs
-    real = bench.CONFIGS["real"]                               # /root/reference/utils/hyperparam_helpers.py:36-39, model/gnn_model.py:12
+    real = bench.CONFIGS["real"]                               # the reference's utils/hyperparam_helpers.py:36-39, model/gnn_model.py:12
     assert (real["in_feats"], real["layer_sizes"], real["graphs_per_gpu"]) == (20, [256] * 4, 6)
     for kernel in ("gat_bwd_edge", "gat_bwd_src"):
         assert bench.compulsory_bytes(kernel, n_b, e_b, 1) < bench.algorithmic_bytes(kernel, n_b, e_b, 1)
 
 
+def test_timed_steps_and_output_dump_helpers(tmp_path):
+    """--steps is the number of timed steps, whatever the blocks; --dump-outputs writes float32 .npy within 64 MiB."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    for steps, blocks in [(1, None), (3, 2), (2, 5), (20, None), (45, None), (600, None), (10_000, None), (7, 3)]:
+        sizes = bench.block_sizes(steps, blocks)
+        assert sum(sizes) == steps and max(sizes) - min(sizes) <= 1 and sizes == sorted(sizes, reverse=True)
+        assert len(sizes) == (min(blocks, steps) if blocks else min(30, max(1, steps // 20)))
+    assert bench.block_sizes(600) == [20] * 30                   # the default run: 30 blocks of 20 steps
+    idx = bench.voxel_sample(240 ** 3, 1 << 19)
+    assert idx.size == 1 << 19 and np.all(np.diff(idx) > 0) and idx[-1] < 240 ** 3
+    assert np.array_equal(idx, bench.voxel_sample(240 ** 3, 1 << 19))
+    assert np.array_equal(bench.voxel_sample(10, 20), np.arange(10))
+    bench.dump_outputs(str(tmp_path / "d"), {"loss": torch.tensor(0.5, dtype=torch.float64),
+                                             "param.w": torch.arange(6.0).reshape(2, 3)})
+    loss, w = np.load(tmp_path / "d" / "loss.npy"), np.load(tmp_path / "d" / "param.w.npy")
+    assert loss.dtype == w.dtype == np.float32 and loss.shape == () and float(loss) == 0.5
+    assert np.array_equal(w, np.arange(6.0).reshape(2, 3))
+    with pytest.raises(SystemExit, match="limit"):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+    assert not (tmp_path / "big").exists()
+
+
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
-def test_bench_prints_one_json_line_with_the_contract_fields(hip_lib):
+def test_bench_prints_one_json_line_with_the_contract_fields(hip_lib, tmp_path):
+    dump = tmp_path / "outputs"
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1",
-                          "--blocks", "2", "--cpu-steps", "1"], capture_output=True, text=True, timeout=550, cwd=REPO)
+                          "--blocks", "2", "--cpu-steps", "1", "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=550, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, out.stdout
@@ -62,9 +90,21 @@ def test_bench_prints_one_json_line_with_the_contract_fields(hip_lib):
         assert (h["traffic"] is None) == (h["traffic_source"] is None)
     b = d["blocks"]
     assert b["n"] == 2 and b["min"] <= b["median"] <= b["max"] and abs(b["median"] - d["value"]) < 1e-2
+    assert b["steps_per_block"] == [2, 1]                    # --steps 3: three timed steps in all
+    assert abs(d["value"] * d["ms_per_step"] - 1e3 * d["config"]["global_batch"]) < 1e-2 * d["value"]
     assert d["ranks"] == 1 and d["backend"] is None
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and "sample" in c
+    # --dump-outputs: the last timed step's loss and the parameters its AdamW update wrote
+    import numpy as np
+
+    files = sorted(os.listdir(dump))
+    assert "loss.npy" in files and len([f for f in files if f.startswith("param.")]) == 40 and len(files) == 41
+    arrays = {f: np.load(dump / f) for f in files}
+    assert all(a.dtype == np.float32 and np.all(np.isfinite(a)) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert abs(float(arrays["loss.npy"]) - d["config"]["last_value"]) < 1e-6 * max(1.0, d["config"]["last_value"])
+    assert arrays["param.layers.0.fc_self.weight.npy"].shape == (256, 4)
 
 
 @pytest.mark.gpu
