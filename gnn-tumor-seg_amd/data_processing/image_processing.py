@@ -55,3 +55,17 @@ def determine_brain_crop(multi_modal_data):
     else:
         raise Exception(f"Expected input shape of either nxmxr or nxmxrxC. Instead got {multi_modal_data.shape}")
     return _any_along_other_axes(intensity > 0.01)
+
+
+
+def normalize_img(img_array, is_flat=False):
+    """Scale each channel by its 0.995 quantile taken as float32 (reference image_processing.py:45-51).
+    Channels are the last axis; is_flat means [voxels, channels] instead of [X, Y, Z, channels]."""
+    spatial_axes = 0 if is_flat else (0, 1, 2)
+    top = np.quantile(img_array, 0.995, axis=spatial_axes).astype(np.float32)
+    return img_array / top
+
+
+def standardize_img(img_array, mean, std):
+    """Per-channel z-score with given statistics (reference image_processing.py:53-56)."""
+    return (img_array - mean) / std

@@ -10,6 +10,7 @@ the specification leaves to the writer (scl_slope 1.0 here, NaN in nibabel — b
 scaling"; descrip) may differ; every reader-relevant field is the spec's.
 """
 import gzip
+import os
 import struct
 
 import numpy as np
@@ -111,3 +112,35 @@ def read_nifti(fp, data_type):
         if slope != 0.0 and not np.isnan(slope):
             data = data * slope + inter
     return np.array(data, dtype=data_type)
+
+
+
+def _files_with_suffix(folder, suffix, recursive):
+    """Sorted paths under folder whose name ends with suffix."""
+    if recursive:
+        found = [os.path.join(root, f) for root, _, files in os.walk(folder) for f in files]
+    else:
+        found = [os.path.join(folder, f) for f in os.listdir(folder)]
+    return sorted(p for p in found if p.endswith(suffix))
+
+
+def read_in_patient_sample(scan_dir, modality_exts):
+    """One scan's modalities as float32, channel last in the order of modality_exts (a single
+    modality is returned without a channel axis).  Counterpart of reference nifti_io.py:12-29:
+    files are searched below scan_dir, and every suffix must match exactly one of them."""
+    channels = []
+    for ext in modality_exts:
+        paths = _files_with_suffix(scan_dir, ext, recursive=True)
+        if len(paths) != 1:
+            raise FileNotFoundError(f"{scan_dir}: {len(paths)} files end with {ext!r}, expected exactly one")
+        channels.append(read_nifti(paths[0], np.float32))
+    return channels[0] if len(channels) == 1 else np.stack(channels, axis=3)
+
+
+def read_in_labels(scan_dir, label_ext):
+    """One scan's int16 label volume (reference nifti_io.py:32-39): the first file directly in
+    scan_dir whose name ends with label_ext."""
+    paths = _files_with_suffix(scan_dir, label_ext, recursive=False)
+    if not paths:
+        raise FileNotFoundError(f"{scan_dir}: no label file ending with {label_ext!r}")
+    return read_nifti(paths[0], np.int16)

@@ -1,0 +1,145 @@
+"""Raw BraTS scan folders -> supervoxel graph dataset (counterpart of the reference's
+scripts/preprocess_dataset.py; same flags, defaults, standardization constants and outputs).
+
+For each scan folder: the modalities are stacked, cropped to the planes that hold brain, the labels
+moved to the internal coding, the intensities normalized and standardized, and the graph built by
+mri2graph.graphgen.img2graph (SLIC, statistics and edges on the MI355X).  Written into
+OUTPUT/{id}/: {id}_nxgraph.json, {id}_input.nii.gz, {id}_label.nii.gz (only with -l),
+{id}_supervoxels.nii.gz and {id}_crop.npz (read back by data_loader.load_crop).
+
+The GPU takes one scan at a time; decoding the next scans and encoding the finished ones run on a
+small thread pool meanwhile.  A scan that raises is reported and left out; the exit status is 1
+when any scan was left out.
+
+    python -m scripts.preprocess_dataset -d RAW_DIR -l _seg.nii.gz -o OUT_DIR
+"""
+import argparse
+import glob
+import os
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+_PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _PKG not in sys.path:
+    sys.path.insert(0, _PKG)
+
+import Filepaths  # noqa: E402
+from data_processing import graph_io, nifti_io  # noqa: E402
+from data_processing.data_loader import save_crop  # noqa: E402
+from data_processing.image_processing import determine_brain_crop, normalize_img, standardize_img  # noqa: E402
+from data_processing.labels import LABEL_MAP, swap_labels_from_brats  # noqa: E402,F401
+
+# per-modality (mean, standard deviation) after normalization: the reference's fixed values
+STANDARDIZATION_STATS = ([0.4645, 0.6625, 0.4064, 0.3648], [0.1593, 0.1703, 0.1216, 0.1627])
+BRATS_MODALITIES = ["_flair.nii.gz", "_t1.nii.gz", "_t1ce.nii.gz", "_t2.nii.gz"]
+IO_WORKERS = 3     # threads for NIfTI decode / encode around the GPU work
+READ_AHEAD = 2     # scans decoded ahead of the one on the GPU
+
+_FLAGS = (
+    # short, long, default, type, help
+    ("-d", "--data_dir", None, str, "folder holding the raw scan folders (default: Filepaths.INPUT_MRI_DIR)"),
+    ("-n", "--num_nodes", 15000, int, "approximate number of SLIC supervoxels per scan"),
+    ("-k", "--num_neighbors", 10, int, "edges per node of the kNN graph; 0 links supervoxels that touch instead"),
+    ("-b", "--boxiness", 0.5, float, "SLIC compactness: larger gives more cube-like supervoxels"),
+    ("-o", "--output_dir", None, str, "where the graph dataset goes (default: PROCESSED_DATA_DIR_n_b_k)"),
+)
+
+
+def build_parser():
+    """Same flags and defaults as the reference CLI (scripts/preprocess_dataset.py:177-184)."""
+    parser = argparse.ArgumentParser(description="Build supervoxel graphs from BraTS MRI folders on MI355X")
+    for short, long_name, default, kind, text in _FLAGS:
+        parser.add_argument(short, long_name, default=default, type=kind, help=text)
+    parser.add_argument("-m", "--modality_extensions", nargs="+", default=list(BRATS_MODALITIES),
+                        help="file suffix of each modality, in channel order")
+    parser.add_argument("-l", "--label_extension", default=None,
+                        help="file suffix of the label volume; without it no labels are read or written")
+    parser.add_argument("-p", "--data_prefix", default="", help="common prefix of the scan folders, e.g. BraTS2021")
+    return parser
+
+
+def default_output_dir(args):
+    return f"{Filepaths.PROCESSED_DATA_DIR}_{args.num_nodes}_{args.boxiness}_{args.num_neighbors}"
+
+
+def find_scans(data_dir, prefix):
+    """{scan id: folder} for every folder under data_dir whose name starts with prefix."""
+    root = os.path.join(os.path.expanduser(data_dir), "")
+    folders = glob.glob(f"{root}**/{prefix}*/", recursive=True)
+    return {os.path.basename(os.path.normpath(f)): f for f in folders}
+
+
+class DataPreprocessor:
+    """Runs the per-scan pipeline over every scan folder of args.data_dir."""
+
+    def __init__(self, args):
+        self.args = args
+        self.k = args.num_neighbors or None
+        self.output_dir = os.path.expanduser(args.output_dir or default_output_dir(args))
+        self.scans = find_scans(args.data_dir or Filepaths.INPUT_MRI_DIR, args.data_prefix)
+        self.all_ids = sorted(self.scans)
+        self.mean, self.std = (np.array(s, dtype=np.float32) for s in STANDARDIZATION_STATS)
+        print(f"{len(self.all_ids)} scan folders found; graphs go to {self.output_dir}")
+
+    def load(self, scan_id):
+        """Host stage: decode, crop, relabel, normalize, standardize."""
+        folder = self.scans[scan_id]
+        image = nifti_io.read_in_patient_sample(folder, self.args.modality_extensions)
+        crop = determine_brain_crop(image)
+        labels = None
+        if self.args.label_extension:
+            labels = swap_labels_from_brats(nifti_io.read_in_labels(folder, self.args.label_extension)[crop])
+        image = standardize_img(normalize_img(image[crop]), self.mean, self.std)
+        return image, labels, crop
+
+    def store(self, scan_id, graph, image, labels, partition, crop):
+        """Host stage: JSON + gzip NIfTI encode."""
+        stem = os.path.join(self.output_dir, scan_id, scan_id)
+        os.makedirs(os.path.dirname(stem), exist_ok=True)
+        graph_io.save_networkx_graph(graph, stem + "_nxgraph.json")
+        outputs = {"_input.nii.gz": image, "_label.nii.gz": labels, "_supervoxels.nii.gz": partition}
+        for suffix, volume in outputs.items():
+            if volume is not None:
+                nifti_io.save_as_nifti(volume, stem + suffix)
+        save_crop(stem + "_crop.npz", crop)
+
+    def run(self):
+        """Process every scan; returns the ids that failed."""
+        from mri2graph.graphgen import img2graph
+
+        failed, writes = [], []
+        ids = self.all_ids
+        with ThreadPoolExecutor(max_workers=IO_WORKERS) as pool:
+            pending = {i: pool.submit(self.load, ids[i]) for i in range(min(READ_AHEAD, len(ids)))}
+            for i, scan_id in enumerate(ids):
+                if i + READ_AHEAD < len(ids):
+                    pending[i + READ_AHEAD] = pool.submit(self.load, ids[i + READ_AHEAD])
+                try:
+                    image, labels, crop = pending.pop(i).result()
+                    graph, _, partition = img2graph(image, labels, self.args.num_nodes, self.args.boxiness, self.k)
+                except Exception as exc:
+                    print(f"{scan_id}: skipped ({exc!r})")
+                    failed.append(scan_id)
+                    continue
+                writes.append((scan_id, pool.submit(self.store, scan_id, graph, image, labels, partition, crop)))
+            for scan_id, job in writes:
+                try:
+                    job.result()
+                    print(f"{scan_id}: done")
+                except Exception as exc:
+                    print(f"{scan_id}: writing failed ({exc!r})")
+                    failed.append(scan_id)
+        return failed
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    failed = DataPreprocessor(args).run()
+    print(f"preprocessing finished, {len(failed)} scan(s) skipped")
+    return 1 if failed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -534,6 +534,73 @@ int32_t gts_collate_batch(const gts_collate_member_t* members, int32_t n_members
                           const gts_collate_kind_t* kinds, int32_t n_kinds, void* dst, int64_t dst_bytes,
                           int32_t n_threads, gts_collate_plan_t* plan);
 
+/* ---- G1-G8: supervoxel graph construction (reference mri2graph/graphgen.py) -----------------
+ * The SLIC of skimage <= 0.18 (mri2graph/graphgen.py:243) and the statistics / discard / edge
+ * builders around it, restated in DESIGN.md "Graph generation".  Volumes are [D, H, W, C]
+ * row-major (C fastest), int32 voxel indexing (D*H*W*C < 2^31).  Supervoxel counts are at
+ * most GTS_GG_MAX_SV (the partition is int16, as in the reference), k at most GTS_GG_MAX_K. */
+#define GTS_GG_MAX_SV 32767
+#define GTS_GG_MAX_K 32
+#define GTS_GG_MAX_RADIUS 16
+/* G1: scipy.ndimage.gaussian_filter(image, sigma=[s, s, s, 0]) (skimage slic's smoothing before
+ * mri2graph/graphgen.py:243), mode 'reflect', then out *= scale (slic's 1 / compactness).
+ * weights[0..radius]: the normalised taps, weights[j] = w(+-j).  tmp: scratch of the image's size.
+ * Bit-exact against scipy: centre tap first, then (v[i-j] + v[i+j]) * w[j] for j = radius .. 1. */
+int32_t gts_gg_gaussian_f64(const double* in, double* out, double* tmp, const double* weights, int32_t radius,
+                            double scale, int64_t d, int64_t h, int64_t w, int64_t c, void* stream);
+/* G2: one SLIC assignment round (mri2graph/graphgen.py:243, skimage _slic_cython's assignment loop).
+ * centres [n_centres, 3 + c] = (z, y, x, colour...); a NaN centre (emptied segment) is skipped.
+ * Every voxel takes the centre of least distance among the windows that contain it (lowest index
+ * on ties); a voxel in no window keeps labels[v].  c <= 8.  best (uint64 [D*H*W]) and winner
+ * (uint32 [D*H*W]) are scratch. */
+int32_t gts_gg_slic_assign_f64(const double* img, const double* centres, int32_t n_centres, int64_t d, int64_t h,
+                               int64_t w, int64_t c, int32_t step_z, int32_t step_y, int32_t step_x,
+                               double spatial_weight, int32_t* labels, uint64_t* best, uint32_t* winner,
+                               void* stream);
+/* G3: SLIC centre update (same call site): centre = raster-order sums of (z, y, x, colour...) over
+ * the segment's voxels / count (0 voxels -> NaN).  bbox: int32 scratch [n_centres * 6]. */
+int32_t gts_gg_slic_update_f64(const double* img, const int32_t* labels, double* centres, int32_t n_centres,
+                               int64_t d, int64_t h, int64_t w, int64_t c, int32_t* bbox, void* stream);
+/* G4 (HOST function: host pointers, no GPU call): skimage's _enforce_label_connectivity_cython
+ * (mri2graph/graphgen.py:243, enforce_connectivity=True): raster-order BFS over 6-neighbours
+ * (+x, -x, +y, -y, +z, -z), truncated at max_size voxels; components below min_size take the
+ * last adjacent relabelled neighbour (0 when none).  queue: int64 scratch [max_size].
+ * n_labels = max label + 1. */
+int32_t gts_gg_enforce_connectivity(const int32_t* labels, int32_t* out, int64_t d, int64_t h, int64_t w,
+                                    int64_t min_size, int64_t max_size, int64_t* queue, int32_t* n_labels);
+/* G5: extract_supervoxel_statistics (mri2graph/graphgen.py:47-61): per supervoxel and channel the
+ * quantiles 0.1, 0.25, 0.5, 0.75, 0.9 of the float32 intensities (numpy 'linear'), fp64,
+ * feats [n_sv, 5 * c] channel-major; the mode of vox_labels (NULL -> zeros; smallest value among
+ * ties) and the centroid (mean of integer coordinates).  partition: int32 ids in [0, n_sv).
+ * scratch: gts_gg_sv_stats_workspace(d * h * w, n_sv) bytes.  5 * c <= 256. */
+int64_t gts_gg_sv_stats_workspace(int64_t n_vox, int32_t n_sv);
+int32_t gts_gg_sv_stats(const int32_t* partition, const float* intensities, const int16_t* vox_labels, int64_t d,
+                        int64_t h, int64_t w, int64_t c, int32_t n_sv, double* feats, double* centroids,
+                        int32_t* sv_labels, void* scratch, void* stream);
+/* G6: discard_empty_svs (mri2graph/graphgen.py:71-96): supervoxels whose feats[:, 4] is below
+ * min(feats[:, 4]) + 0.01 are dropped, the kept ones numbered in order (remap, -1 = dropped) and
+ * gathered into node_feats / node_centroids / node_labels; new_partition (int16) = remap[partition].
+ * keep: int32 scratch [n_sv]; n_nodes: one device int32. */
+int32_t gts_gg_discard_f64(const double* feats, const double* centroids, const int32_t* sv_labels, int32_t n_sv,
+                           int32_t n_feat, const int32_t* partition, int64_t n_vox, int32_t* remap, int32_t* keep,
+                           double* node_feats, double* node_centroids, int32_t* node_labels, int16_t* new_partition,
+                           int32_t* n_nodes, void* stream);
+/* G7: build_adjacency_matrix(..., weighted=False, enforce_regularity=True) (mri2graph/graphgen.py:120-153)
+ * without the N x N matrices.  gts_gg_knn_candidates_f64: cand[i, 0..k) = the k nearest j > i by
+ * (scipy cdist euclidean distance, j), -1 past the last one.  gts_gg_knn_greedy (HOST function):
+ * the reference's sequential pass — row i takes the first k - (rows i' < i that took i) of its
+ * candidates: picks[i, t] = j or -1; n_edges = undirected edges; got: int32 host scratch [n]. */
+int32_t gts_gg_knn_candidates_f64(const double* positions, int32_t n, int32_t k, int32_t* cand, void* stream);
+int32_t gts_gg_knn_greedy(const int32_t* cand, int32_t n, int32_t k, int32_t* picks, int32_t* got, int64_t* n_edges);
+/* G8: find_adjacent_nodes (mri2graph/graphgen.py:161-196): pairs of distinct ids >= 0 that touch across
+ * a face, both orientations, plus every (i, i).  gts_gg_touching_count_i16 marks them in scratch
+ * (gts_gg_touching_workspace(n) bytes) and writes indptr [n + 1]; gts_gg_touching_emit then writes
+ * the columns of each row in ascending order (the row-major order of np.where on the matrix). */
+int64_t gts_gg_touching_workspace(int32_t n);
+int32_t gts_gg_touching_count_i16(const int16_t* partition, int64_t d, int64_t h, int64_t w, int32_t n, void* scratch,
+                                  int32_t* indptr, void* stream);
+int32_t gts_gg_touching_emit(const void* scratch, int32_t n, const int32_t* indptr, int32_t* cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
