@@ -20,6 +20,7 @@ import torch
 
 import gts
 from data_processing import graph_io, nifti_io
+from data_processing.image_processing import determine_tumor_crop
 
 
 class ImageGraphDataset(torch.utils.data.Dataset):
@@ -195,3 +196,35 @@ def minibatch_graphs(samples):
         at += len(f)
     return (mri_ids, gts.batch(graphs), torch.from_numpy(feats),
             torch.from_numpy(np.concatenate(labels).astype(np.int64, copy=False)))
+
+
+class PredLogitDataset:
+    """Voxel logits that `generate_gnn_predictions -f logits` wrote (`{root}/{id}_logits.nii.gz`) and the crop
+    around their predicted tumour (reference data_loader.py:131-159).  The crop of a sample is computed on its
+    first read and cached, as in the reference; not meant to be iterated."""
+
+    def __init__(self, root_dir):
+        self.root_dir = root_dir
+        self.mri_crops = {}
+
+    def get_crop(self, mri_id):
+        if mri_id not in self.mri_crops:
+            self.mri_crops[mri_id] = determine_tumor_crop(np.argmax(self.read_logits(mri_id), axis=-1))
+        return self.mri_crops[mri_id]
+
+    def read_logits(self, mri_id):
+        fp = f"{self.root_dir}{os.sep}{mri_id}_logits.nii.gz"
+        if not os.path.exists(fp):
+            raise FileNotFoundError(f"{mri_id}: no voxel logits at {fp}")
+        return nifti_io.read_nifti(fp, np.float32)
+
+    def get_one(self, mri_id):
+        """(logits float32 [X, Y, Z, C], np.ix_ crop)."""
+        logits = self.read_logits(mri_id)
+        return logits, self.get_crop(mri_id)
+
+
+def collate_refinement_net(samples):
+    """Batch of one (mri_id, image, labels) -> (mri_id, FloatTensor, LongTensor) (reference data_loader.py:172-174)."""
+    mri, img, lab = samples[0]
+    return mri, torch.as_tensor(np.asarray(img), dtype=torch.float32), torch.as_tensor(np.asarray(lab), dtype=torch.int64)

@@ -94,13 +94,21 @@ SIGNATURES = {
     "gts_gg_touching_workspace": [_i32],
     "gts_gg_touching_count_i16": [_p, _i64, _i64, _i64, _i32, _p, _p, _p],
     "gts_gg_touching_emit": [_p, _i32, _p, _p, _p],
+    "gts_conv3d_fwd_workspace": [_i32, _i32],
+    "gts_conv3d_fwd_f32": [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _p, _i64, _p],
+    "gts_conv3d_bwd_data_workspace": [_i64, _i64, _i64, _i32, _i32],
+    "gts_conv3d_bwd_data_f32": [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _p, _i64, _p],
+    "gts_conv3d_bwd_weight_workspace": [_i64, _i64, _i64, _i32, _i32],
+    "gts_conv3d_bwd_weight_f32": [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _p, _i64, _p],
 }
 _RESTYPE = {"gts_error_string": ctypes.c_char_p, "gts_linear_bwd_weight_workspace": _i64,
             "gts_weighted_ce_workspace": _i64, "gts_gat_reduce_workspace": _i64,
             "gts_label_confusion_workspace": _i64, "gts_gat_fc_scores_workspace": _i64,
             "gts_relu_bits_bytes": _i64, "gts_cluster_record_words": _i64, "gts_sage_pool_stack_fwd_arena": _i64, "gts_sage_pool_stack_bwd_scratch": _i64, "gts_cluster_lds_bytes": _i64,
             "gts_linear_bwd_input_t_act_workspace": _i64, "gts_gat_cluster_workspace": _i64,
-            "gts_packed_weight_floats": _i64, "gts_gg_sv_stats_workspace": _i64, "gts_gg_touching_workspace": _i64}
+            "gts_packed_weight_floats": _i64, "gts_gg_sv_stats_workspace": _i64, "gts_gg_touching_workspace": _i64,
+            "gts_conv3d_fwd_workspace": _i64, "gts_conv3d_bwd_data_workspace": _i64,
+            "gts_conv3d_bwd_weight_workspace": _i64}
 
 COLLATE_MAX_SCHEDULES = 6      # GTS_COLLATE_MAX_SCHEDULES
 

@@ -1,12 +1,163 @@
-"""Input assembly of the refinement CNN.
+"""Training harness and input assembly of the refinement CNN.
 
-Counterpart of `combine_logits_and_image` in /root/reference/model/cnn_model.py:85-88, plus the
-fused form the joint predictor uses on the GPU.  Training the CNN itself (RefinementModel,
-reference :23-82) is dense Conv3d work on the vendor library and is not part of this build.
+Counterpart of /root/reference/model/cnn_model.py:24-88: `RefinementModel` (constructor, `run_epoch`,
+`evaluate`, `save_weights`) and `combine_logits_and_image`, plus the fused form the joint predictor uses
+on the GPU.  Training runs both Conv3d layers and their backward on the HIP kernels of gts.conv3d
+(C1-C5); `CnnRefinementNet.forward` itself is untouched.
 """
-import torch
+import queue
+import threading
 
+import numpy as np
+import torch
+from torch.utils.data import DataLoader
+
+from data_processing.data_loader import collate_refinement_net
 from gts import ops
+from gts.conv3d import refinement_logits
+from gts.optim import FlatAdamW
+
+from . import evaluation
+from .networks import CnnRefinementNet
+
+
+class RefinementModel:
+    """Trains CnnRefinementNet on GNN voxel logits ++ image inside the crop around the GNN-predicted tumour.
+
+    Same arithmetic as the reference: batch of one, shuffled; AdamW(lr, weight_decay) with ExponentialLR
+    (one step per epoch); class-weighted cross-entropy (mean over the crop's voxels).  Differences:
+      * everything runs on the GPU through HIP: both convolutions and their gradients (gts.conv3d), the loss
+        (gts.ops.weighted_cross_entropy), AdamW (gts.optim.FlatAdamW), Dice counting (gts.ops.label_confusion);
+        there is no CPU path;
+      * the next sample's logits are decoded, concatenated and cropped on a host thread while the current step
+        runs (`prefetch=True`; same samples, same order), and the loss is read back once per epoch;
+      * `ExponentialLR(..., verbose=False)` raises on current PyTorch; the kwarg is dropped.
+    Two reference quirks are kept on purpose, so results stay comparable with the reference's:
+      * a sample whose logit file is missing is skipped (FileNotFoundError), in training and in evaluation;
+      * in `evaluate` the row of such a sample stays all zeros and is still averaged into the returned mean.
+    HD95 is computed, as in the reference, on the [1, cx, cy, cz] arrays of the crop.
+    """
+
+    def __init__(self, hyperparameters, train_dataset, logit_dataset, prefetch=True):
+        if not torch.cuda.is_available():
+            raise RuntimeError("RefinementModel trains on an AMD GPU only (no CPU path)")
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.class_weights = torch.tensor(hyperparameters.class_weights, dtype=torch.float32, device=self.device)
+        self.net = CnnRefinementNet(hyperparameters.in_feats, hyperparameters.out_classes,
+                                    hyperparameters.layer_sizes).to(self.device)
+        self.optimizer = FlatAdamW(self.net.parameters(), lr=hyperparameters.lr,
+                                   weight_decay=hyperparameters.w_decay)
+        self.lr_decay = torch.optim.lr_scheduler.ExponentialLR(self.optimizer, hyperparameters.lr_decay,
+                                                               last_epoch=-1)
+        self.train_loader = DataLoader(train_dataset, batch_size=1, shuffle=True, num_workers=0,
+                                       collate_fn=collate_refinement_net) if train_dataset is not None else None
+        self.logit_dataset = logit_dataset
+        self.prefetch = prefetch
+
+    def _cropped(self, mri, img, lab):
+        """(input float32 [cx, cy, cz, C], labels int64 [V]) of one sample, or None when its logits are missing."""
+        try:
+            gnn_out, crop = self.logit_dataset.get_one(mri)
+        except FileNotFoundError:
+            return None
+        img = np.asarray(img, dtype=np.float32)
+        x = np.concatenate([img, np.asarray(gnn_out, dtype=np.float32)], axis=-1)[crop]
+        y = np.asarray(lab)[crop].astype(np.int64).reshape(-1)
+        return torch.from_numpy(np.ascontiguousarray(x)), torch.from_numpy(y)
+
+    def _samples(self, items):
+        """Cropped host samples of `items` in order (None for a skipped one), produced one ahead on a thread."""
+        if not self.prefetch:
+            for mri, img, lab in items:
+                yield self._cropped(mri, img, lab)
+            return
+        box = queue.Queue(maxsize=1)
+        stop = threading.Event()
+        done = object()
+
+        def put(item):
+            """Hand one item over; give up when the consumer has gone away."""
+            while not stop.is_set():
+                try:
+                    box.put(item, timeout=0.1)
+                    return True
+                except queue.Full:
+                    pass
+            return False
+
+        def produce():
+            try:
+                for mri, img, lab in items:
+                    if not put(self._cropped(mri, img, lab)):
+                        return
+            except BaseException as e:  # surfaced in the consuming thread
+                put(e)
+                return
+            put(done)
+
+        worker = threading.Thread(target=produce, name="gts-cnn-prefetch", daemon=True)
+        worker.start()
+        try:
+            while True:
+                item = box.get()
+                if item is done:
+                    break
+                if isinstance(item, BaseException):
+                    raise item
+                yield item
+        finally:            # also when the consumer stops early (an exception in its step, or close())
+            stop.set()
+            worker.join()
+
+    def train_step(self, x, y):
+        """One forward / backward / AdamW step on a cropped sample already on the device; returns the loss
+        as a device scalar."""
+        logits = refinement_logits(x, self.net)
+        loss = ops.weighted_cross_entropy(logits, y, self.class_weights)
+        self.optimizer.zero_grad()
+        loss.backward()
+        self.optimizer.step()
+        return loss.detach()
+
+    def run_epoch(self):
+        self.net.train()
+        losses = []
+        for sample in self._samples(self.train_loader):
+            if sample is None:
+                continue
+            x, y = (t.to(self.device, non_blocking=False) for t in sample)
+            losses.append(self.train_step(x, y))
+        self.lr_decay.step()
+        if not losses:
+            return float("nan")      # numpy.mean([]) in the reference
+        return float(np.mean(torch.stack(losses).cpu().numpy()))
+
+    @torch.no_grad()
+    def evaluate(self, dataset=None):
+        """Mean over `dataset` of [loss, WT / CT / ET voxel Dice, WT / CT / ET HD95] inside each sample's crop."""
+        self.net.eval()
+        metrics = np.zeros((len(dataset), 7))
+        i = 0
+        items = ((mri, img, lab) for mri, img, lab in dataset)
+        for sample in self._samples(items):
+            if sample is None:
+                continue
+            shape = tuple(sample[0].shape[:3])
+            x, y = (t.to(self.device) for t in sample)
+            logits = refinement_logits(x, self.net)
+            loss = ops.weighted_cross_entropy(logits, y, self.class_weights)
+            pred = torch.argmax(logits, dim=1).to(torch.int16)
+            confusion = ops.label_confusion(pred, y.to(torch.int16))
+            pred_np = pred.cpu().numpy().reshape((1,) + shape)
+            lab_np = sample[1].numpy().reshape((1,) + shape)
+            metrics[i][0] = float(loss)
+            metrics[i][1:4] = evaluation.dices_from_confusion(confusion.cpu().numpy())
+            metrics[i][4:] = evaluation.calculate_hd95s(pred_np, lab_np)
+            i += 1
+        return np.mean(metrics, axis=0)
+
+    def save_weights(self, folder, name):
+        torch.save(self.net.state_dict(), f"{folder}{name}.pt")
 
 
 def combine_logits_and_image(gnn_out, img, tumor_crop):

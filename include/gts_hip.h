@@ -601,6 +601,31 @@ int32_t gts_gg_touching_count_i16(const int16_t* partition, int64_t d, int64_t h
                                   int32_t* indptr, void* stream);
 int32_t gts_gg_touching_emit(const void* scratch, int32_t n, const int32_t* indptr, int32_t* cols, void* stream);
 
+/* ---- C1-C5: 5x5x5 Conv3d, stride 1, replicate padding 2 (refinement CNN training) ----------------
+ * The two layers of CnnRefinementNet (model/networks.py:83-93) and their backward, as reached from
+ * RefinementModel.run_epoch (model/cnn_model.py:36-56) and .evaluate (:58-78).  Activations are
+ * channels-last [cx, cy, cz, C] (= [V, C]); w is torch's Conv3d weight [cout, cin, 5, 5, 5]; channel
+ * counts 1..32; every dimension >= 1 and (cx + 4)(cy + 4)(cz + 4) * 32 < 2^31.  Each call first packs
+ * w into its workspace.  Deterministic: no float atomics, fixed reduction orders.
+ * gts_conv3d_fwd_f32 (C1 / C2): y = act(conv(x, w) + bias); bias may be NULL; relu 0 or 1. */
+int64_t gts_conv3d_fwd_workspace(int32_t cin, int32_t cout);
+int32_t gts_conv3d_fwd_f32(const float* x, const float* w, const float* bias, float* y, int64_t cx, int64_t cy,
+                           int64_t cz, int32_t cin, int32_t cout, int32_t relu, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+/* C3: dx = d conv(x, w) / d x applied to dy [V, cout] -> [V, cin], the exact adjoint of the replicate
+ * clamp (every tap that clamps onto a boundary voxel contributes to it).  h (optional, [V, cin]): the
+ * ReLU output that fed the layer; dx is zeroed where h <= 0. */
+int64_t gts_conv3d_bwd_data_workspace(int64_t cx, int64_t cy, int64_t cz, int32_t cin, int32_t cout);
+int32_t gts_conv3d_bwd_data_f32(const float* dy, const float* w, const float* h, float* dx, int64_t cx, int64_t cy,
+                                int64_t cz, int32_t cin, int32_t cout, void* workspace, int64_t workspace_bytes,
+                                void* stream);
+/* C4 / C5: dw [cout, cin, 5, 5, 5] = sum over voxels of dy (x) the clamped input taps; db [cout] (optional)
+ * = sum over voxels of dy.  Split-K over voxel bricks into the workspace, summed in a fixed order. */
+int64_t gts_conv3d_bwd_weight_workspace(int64_t cx, int64_t cy, int64_t cz, int32_t cin, int32_t cout);
+int32_t gts_conv3d_bwd_weight_f32(const float* x, const float* dy, float* dw, float* db, int64_t cx, int64_t cy,
+                                  int64_t cz, int32_t cin, int32_t cout, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
