@@ -100,6 +100,8 @@ SIGNATURES = {
     "gts_conv3d_bwd_data_f32": [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _p, _i64, _p],
     "gts_conv3d_bwd_weight_workspace": [_i64, _i64, _i64, _i32, _i32],
     "gts_conv3d_bwd_weight_f32": [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _p, _i64, _p],
+    "gts_hd95_workspace": [_i64, _i64, _i64],
+    "gts_hd95_order_stats_i16": [_p, _p, _i64, _i64, _i64, _i32, _p, _p, _i64, _p],
 }
 _RESTYPE = {"gts_error_string": ctypes.c_char_p, "gts_linear_bwd_weight_workspace": _i64,
             "gts_weighted_ce_workspace": _i64, "gts_gat_reduce_workspace": _i64,
@@ -108,7 +110,7 @@ _RESTYPE = {"gts_error_string": ctypes.c_char_p, "gts_linear_bwd_weight_workspac
             "gts_linear_bwd_input_t_act_workspace": _i64, "gts_gat_cluster_workspace": _i64,
             "gts_packed_weight_floats": _i64, "gts_gg_sv_stats_workspace": _i64, "gts_gg_touching_workspace": _i64,
             "gts_conv3d_fwd_workspace": _i64, "gts_conv3d_bwd_data_workspace": _i64,
-            "gts_conv3d_bwd_weight_workspace": _i64}
+            "gts_conv3d_bwd_weight_workspace": _i64, "gts_hd95_workspace": _i64}
 
 COLLATE_MAX_SCHEDULES = 6      # GTS_COLLATE_MAX_SCHEDULES
 

@@ -13,6 +13,7 @@ import torch
 from torch.utils.data import DataLoader
 
 from data_processing.data_loader import collate_refinement_net
+from gts import metrics as metrics_ops
 from gts import ops
 from gts.conv3d import refinement_logits
 from gts.optim import FlatAdamW
@@ -147,12 +148,13 @@ class RefinementModel:
             logits = refinement_logits(x, self.net)
             loss = ops.weighted_cross_entropy(logits, y, self.class_weights)
             pred = torch.argmax(logits, dim=1).to(torch.int16)
-            confusion = ops.label_confusion(pred, y.to(torch.int16))
-            pred_np = pred.cpu().numpy().reshape((1,) + shape)
-            lab_np = sample[1].numpy().reshape((1,) + shape)
+            truth = y.to(torch.int16)
+            confusion = ops.label_confusion(pred, truth)
+            # the reference passes [1, cx, cy, cz] arrays: the unit axis makes every region voxel border
+            hd95s = metrics_ops.hd95s(pred.reshape((1,) + shape), truth.reshape((1,) + shape))
             metrics[i][0] = float(loss)
             metrics[i][1:4] = evaluation.dices_from_confusion(confusion.cpu().numpy())
-            metrics[i][4:] = evaluation.calculate_hd95s(pred_np, lab_np)
+            metrics[i][4:] = hd95s
             i += 1
         return np.mean(metrics, axis=0)
 

@@ -31,6 +31,7 @@ from data_processing.graph_io import project_nodes_to_img
 from gts import collate as gcollate
 from gts import dense as gdense
 from gts import dist as gdist
+from gts import metrics as gmetrics
 from gts import nn as gnn
 from gts import ops as gops
 from gts.graph import PinnedRing, _upload, uploads_through
@@ -342,11 +343,11 @@ class GNN:
         reference's one-sample-at-a-time route, under the same tile pin) included (tests/test_gpu_cli.py).
         A forward OUTSIDE this method runs under the automatic tile choice and may round differently.  Everything up to the Dice quotients stays on the GPU:
         arg-max + projection is one K12 pass per sample, the node- and voxel-level label
-        coincidences are counted by K15, and only the two 5x5 integer tables, the loss and the
-        predicted volume (for the scipy distance transforms of HD95) travel to the host.
+        coincidences are counted by K15, the HD95 order statistics by H1-H5, and only the two 5x5
+        integer tables, the [3, 4] HD95 integers and the loss travel to the host.
 
         Under torch.distributed the samples are dealt round-robin over the ranks (rank r evaluates r, r + W, ...:
-        forwards AND the host-side HD95 transforms), the per-sample rows are gathered on the host and every rank
+        forwards AND the HD95 passes), the per-sample rows are gathered on the host and every rank
         returns the same two arrays — the doubles a single process computes, because a sample's row does not
         depend on what it is batched with (tests/test_gpu_dp.py)."""
         assert dataset.dataset.read_label == True  # noqa: E712
@@ -374,10 +375,10 @@ class GNN:
                     predicted = torch.max(logits, dim=1)[1]
                     node_table = gops.label_confusion(predicted.to(torch.int16), node_labels.to(torch.int16))
                     predicted_voxels = gops.project_argmax(partitioning, logits)          # K12 + arg-max
-                    voxel_table = gops.label_confusion(                                  # K15
-                        predicted_voxels, torch.from_numpy(true_voxels).to(self.device).contiguous())
+                    truth_voxels = torch.from_numpy(true_voxels).to(self.device).contiguous()
+                    voxel_table = gops.label_confusion(predicted_voxels, truth_voxels)  # K15
+                    hd95s = gmetrics.hd95s(predicted_voxels, truth_voxels)              # H1-H5
                 tables = torch.stack([node_table, voxel_table]).cpu().numpy()
-                hd95s = evaluation.calculate_hd95s(predicted_voxels.cpu().numpy(), true_voxels)
                 rows[indices[j]] = (np.concatenate([[loss.item()], evaluation.dices_from_confusion(tables[0]),
                                                     evaluation.dices_from_confusion(tables[1]), hd95s]),
                                     evaluation.label_counts_from_confusion(tables[0]))

@@ -626,6 +626,27 @@ int32_t gts_conv3d_bwd_weight_f32(const float* x, const float* dy, float* dw, fl
                                   int64_t cz, int32_t cin, int32_t cout, void* workspace, int64_t workspace_bytes,
                                   void* stream);
 
+/* ---- H1-H5: BraTS HD95 order statistics ------------------------------------------------------------
+ * Replace the scipy / numpy arithmetic of model/evaluation.py:83-96 (calculate_hd95_from_logical_array) and
+ * :112-189 (medpy's hd95 and __surface_distances: binary_erosion, distance_transform_edt, np.percentile), reached
+ * from GNN.evaluate (model/gnn_model.py:76-87) and RefinementModel.evaluate.
+ * pred, truth: int16 label volumes [X, Y, Z], Z contiguous.  Regions WT (v != 0), CT (v in {2, 3}), ET (v == 3).
+ * Border B(r, side): region voxels with a 6-neighbour inside the volume outside the region, or on a face of an
+ * axis longer than 1; all_border = 1 (scipy's erosion of an array with a unit axis) makes every region voxel
+ * border, and so does a 1x1x1 volume.  out (device int64 [3][4], one row per region): n = |B(r, pred)| +
+ * |B(r, truth)|; the squared distances at ranks lo and hi of the sorted multiset { d2(p, B(r, truth)) : p in
+ * B(r, pred) } + { d2(q, B(r, pred)) : q in B(r, truth) }, where v = (n - 1) * 0.95, lo = floor(v), hi = lo + 1,
+ * or lo = hi = n - 1 when v >= n - 1 (np.percentile's linear method); presence bits (1: the region is in
+ * pred, 2: in truth).  Ranks are only selected when both bits are set; otherwise both entries are 0.
+ * Limits: every extent >= 1, X * Y * Z < 2^31 and (X-1)^2 + (Y-1)^2 + (Z-1)^2 <= 2^24 (the histogram of
+ * squared distances has one bin per value), else GTS_ERR_SHAPE; all_border outside {0, 1}: GTS_ERR_ARGKIND.
+ * workspace: gts_hd95_workspace(X, Y, Z) bytes (0 for a rejected shape).  Integer arithmetic throughout:
+ * identical results on every run. */
+int64_t gts_hd95_workspace(int64_t X, int64_t Y, int64_t Z);
+int32_t gts_hd95_order_stats_i16(const int16_t* pred, const int16_t* truth, int64_t X, int64_t Y, int64_t Z,
+                                 int32_t all_border, int64_t* out, void* workspace, int64_t workspace_bytes,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
