@@ -6,6 +6,7 @@ on synthetic 15k-node supervoxel graphs, N MI355X GPUs (BASELINE.json metric, co
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
   python bench.py --steps K --dump-outputs DIR            (also writes what the last timed step computed)
+  python bench.py --gpus 1 --full                         (also the rooflines, the CPU baseline and the per-rank figures)
 
 One "step" = forward + class-weighted cross-entropy + backward + (gradient all-reduce when
 N > 1) + AdamW update on one batch of `--graphs-per-gpu` (default 4) 15 000-node lattice
@@ -17,8 +18,13 @@ Timing: after W warm-up steps EXACTLY K steps are timed, as `--blocks` consecuti
 near-equal size (barrier + synchronize on both sides of each block, MAX over ranks; by default
 one block per 20 steps, at most 30: the default K = 600 is ~2.5 s of GPU time at the headline
 shape).  `ms_per_step` is the MEDIAN block's time per step, `value` its rate, and `blocks`
-carries min / median / max.  One further run of K steps follows with HIP events around every
-launch of the kernels the roofline objects describe.
+carries min / median / max.
+
+A plain run does only that: it sets up, warms up, times the K steps, writes --dump-outputs and
+prints the result line.  With --full the same run goes on to measure what the headline does not
+need: one further run of K steps with HIP events around every launch of the kernels the roofline
+objects describe, the per-rank figures and, for --config real, the resident-batch rate, then
+the CPU baseline.  The timed steps and the dumped outputs are the same with and without it.
 
 --dump-outputs DIR writes, once the timed blocks are done, what the last timed step computed
 as DIR/<name>.npy (float32): for the training configurations the step's loss (`loss`) and the
@@ -28,7 +34,8 @@ the same seeded sample of voxels (`volumes_sample`, [graphs, voxels, 4]).  At mo
 all; rank 0's outputs under torchrun.  Inputs and initial weights are seeded, so two runs
 with the same arguments start from the same state.
 
-Rank 0 prints ONE JSON line with the throughput, plus
+Rank 0 prints ONE JSON line with the throughput ("ranks" and "backend": what the collective
+used when N > 1), plus, with --full,
   "roofline":     K11, the MFMA fp32 GEMM kernel most of the step is spent in: flops of every
                   forward / input-gradient / weight-gradient launch / their summed HIP-event
                   durations, against the 157.3 TFLOP/s dense fp32 MFMA peak;
@@ -39,7 +46,7 @@ Rank 0 prints ONE JSON line with the throughput, plus
                   profile (tagged with its source file) beside it;
   "cpu_baseline": the CPU oracle (pure-PyTorch restatement of the DGL CPU path) timed on this
                   box's host cores on a bounded sample of the same workload (N=1 only);
-  "ranks", "backend", "all_reduce": what the collective saw when N > 1.
+  "all_reduce", "per_rank": what the collective and every rank saw when N > 1.
 
 Other BASELINE.json configurations (parity-test cases, not the headline) can be timed with
   --config c3   GAT 4 layers x 4 heads x 256 training on the same graphs   (graphs/s)
@@ -49,7 +56,7 @@ Other BASELINE.json configurations (parity-test cases, not the headline) can be 
   --config real the reference's own training workload (utils/hyperparam_helpers.py:36-39, model/gnn_model.py:12):
                 in_feats 20, layer_sizes [256]*4, batches of 6 graphs of ~6k nodes (18^3 lattices), every step a
                 FRESH batch collated on the host and uploaded through GNN's prefetch path (graphs/s, with the
-                resident-batch rate and the host enqueue time beside it)
+                host enqueue time and, with --full, the resident-batch rate beside it)
 """
 import argparse
 import contextlib
@@ -99,7 +106,7 @@ CONFIGS = {
 }
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=600, help="timed steps, in all blocks together")
@@ -111,11 +118,15 @@ def parse_args():
                     help="graphs in one rank's batch (default 4; 8 for --config c4, 6 for --config real)")
     ap.add_argument("--graph-kind", default="lattice", choices=["lattice", "random", "selfloop"])
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-steps", type=int, default=5, help="timed CPU-oracle steps after one warm-up (SURVEY.md §8d: >= 5)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MiB)")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the rooflines (one more run of --steps steps with HIP "
+                         "events), the per-rank figures, --config real's resident-batch rate and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--cpu-steps", type=int, default=5,
+                    help="--full: timed CPU-oracle steps after one warm-up (SURVEY.md §8d: >= 5)")
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.blocks is not None and args.blocks < 1:
@@ -378,6 +389,7 @@ def main():
     batches = build_batches(rank, args.graphs_per_gpu, args.graph_kind, n_batches=2, device=device, cfg=cfg)
     n_b, e_b = batches[0][0].n, batches[0][0].number_of_edges()
 
+    # installed in every run, enabled only in --full's instrumented block: the timed blocks make the same calls either way
     timers = KernelTimers()
     for name in cfg["hbm_kernels"]:
         ops.KERNEL_TIMERS[name] = timers.bracket(name)
@@ -470,43 +482,34 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, step_outputs(last))
     last = last_value(last)
-    # K more steps with HIP events around every launch of the kernels the roofline objects describe
-    # (kept out of the blocks above: events cost a few us per launch)
-    timers.enabled = ops.INSTRUMENTED = True
-    instrumented = timed_block(args.steps)[0]
-    timers.enabled = ops.INSTRUMENTED = False
-    # per-rank view (N > 1): every rank's own wall time for the last timed block and the time its all-reduce launches took
-    # (a rank that finishes its graphs early waits there: the spread between ranks IS the load imbalance)
-    per_rank = None
-    if world > 1:
-        ar = timers.summary("all_reduce")
-        mine = torch.tensor([blocks[-1][3] / sizes[-1], (ar["total_ms"] / ar["launches"]) if ar else 0.0],
-                            dtype=torch.float64, device=device)
-        everyone = [torch.zeros_like(mine) for _ in range(world)]
-        torch.distributed.all_gather(everyone, mine)
-        per_rank = [[float(v) for v in t.tolist()] for t in everyone]
-    # --config real: the same steps on two RESIDENT batches (every rank; the blocks fence collectively): what the host path costs
-    resident = sorted(timed_block(args.steps, resident_step)[:2] for _ in range(3))[1] if args.config == "real" else None
+    instrumented = per_rank = resident = None
+    if args.full:
+        # K more steps with HIP events around every launch of the kernels the roofline objects describe
+        # (kept out of the blocks above: events cost a few us per launch)
+        timers.enabled = ops.INSTRUMENTED = True
+        instrumented = timed_block(args.steps)[0]
+        timers.enabled = ops.INSTRUMENTED = False
+        # per-rank view (N > 1): every rank's own wall time for the last timed block and the time its all-reduce launches
+        # took (a rank that finishes its graphs early waits there: the spread between ranks IS the load imbalance)
+        if world > 1:
+            ar = timers.summary("all_reduce")
+            mine = torch.tensor([blocks[-1][3] / sizes[-1], (ar["total_ms"] / ar["launches"]) if ar else 0.0],
+                                dtype=torch.float64, device=device)
+            everyone = [torch.zeros_like(mine) for _ in range(world)]
+            torch.distributed.all_gather(everyone, mine)
+            per_rank = [[float(v) for v in t.tolist()] for t in everyone]
+        # --config real: the same steps on two RESIDENT batches (every rank; the blocks fence collectively): what the host
+        # path costs
+        if args.config == "real":
+            resident = sorted(timed_block(args.steps, resident_step)[:2] for _ in range(3))[1]
     log("block seconds in order: " + " ".join(f"{b[0]:.4f}" for b in blocks))
     log(f"blocks: median {1e3 * step_s:.4f} ms/step, min {1e3 * per_step[0]:.4f}, max {1e3 * per_step[-1]:.4f} over "
-        f"{args.steps} steps; instrumented run {instrumented:.4f} s (host enqueue {1e3 * host_enqueue:.2f} ms/step)")
+        f"{args.steps} steps (host enqueue {1e3 * host_enqueue:.2f} ms/step)"
+        + (f"; instrumented run {instrumented:.4f} s" if instrumented is not None else ""))
     global_batch = args.graphs_per_gpu * world
     value = global_batch / step_s
 
     if rank == 0:
-        arg_b = batches[0][0].arg_bytes
-        # the committed profiles ran the lattice workload at 4, 8 and 32 graphs per GPU (C2 / C3 models)
-        tag = "real_" if args.config == "real" else {4: "", 8: "b8_", 32: "b32_"}.get(args.graphs_per_gpu)
-        profiled = tag is not None and args.graph_kind == "lattice" and args.config in ("c2", "c3", "c4", "c5", "real")
-
-        def from_profile(fname, key):
-            path = os.path.join(REPO, "profiles", fname)
-            if not (profiled and os.path.exists(path)):
-                return None, None
-            with open(path) as fh:
-                value = json.load(fh).get(key)
-            return (value, "profiles/" + fname) if value is not None else (None, None)
-
         workloads = {
             "c2": "C2: 7xGraphSAGE-pool-256 (8 SAGEConv), fwd+weighted-CE+bwd+AdamW",
             "c4": "C4: 7xGraphSAGE-pool-256 (8 SAGEConv) data-parallel, fwd+weighted-CE+bwd+gradient all-reduce+AdamW, "
@@ -542,85 +545,101 @@ def main():
             result["config"]["resident_batches"] = {"value": round(rate(resident[0]), 3),
                                                     "ms_per_step": round(1e3 * resident[0] / args.steps, 4),
                                                     "host_enqueue_ms_per_step": round(1e3 * resident[1] / args.steps, 3)}
-        # --- K11, where most of the step goes (all three GEMM forms are one kernel template)
-        kinds = {k: timers.summary("gemm_" + k) for k in ("fwd", "igrad", "wgrad")}
-        kinds = {k: v for k, v in kinds.items() if v}
-        sample = f"HIP events around every launch in one extra block of {args.steps} steps after the timed blocks"
-        # the timed blocks issue the SAGE-pool layer stack through the one-call entry points (gts_sage_pool_stack_*_f32);
-        # events need single launches, so the instrumented block issues the same kernels, in the same order, one library
-        # call each (gts/nn.py::_SagePoolStack) — same device work, more host calls
-        path = ("launch-by-launch: one C-ABI call per kernel (the timed blocks enqueue the same launches through "
-                "gts_sage_pool_stack_fwd_f32 / _bwd_f32)") if cfg["model"] == "GSpool" else "as in the timed blocks"
-        if kinds:
-            flops = sum(v["work"] for v in kinds.values())
-            secs = sum(v["total_ms"] for v in kinds.values()) * 1e-3
-            tf = flops / secs / 1e12
-            result["roofline"] = {
-                "bound": "mfma",
-                "kernel": "K11, every forward / input-gradient / weight-gradient launch of the step: "
-                          "gts::gemm_panel_direct_kernel (16x16x4 MFMA row panels: the chained layer GEMMs, ~58 % of a C2 step) "
-                          "and gts::wgrad_stream_kernel (32x32x2 MFMA split-reduction weight gradients, ~25 %)",
-                "achieved": round(tf, 1), "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(tf / MFMA_F32_PEAK_TFLOPS, 4), "traffic": None,
-                "flops_per_step": flops / args.steps, "gemm_ms_per_step": round(1e3 * secs / args.steps, 4),
-                "share_of_step": round(secs / instrumented, 3), "path": path,
-                "by_kind": {k: {"launches_per_step": v["launches"] / args.steps,
-                                "avg_launch_us": round(1e3 * v["total_ms"] / v["launches"], 2),
-                                "tflops": round(v["work"] / (v["total_ms"] * 1e-3) / 1e12, 1)}
-                            for k, v in kinds.items()},
-                "sample": sample}
-        # --- the HBM-bound kernels of the path: fraction from COMPULSORY bytes (each array once)
-        # what the events of an entry bracket: one library call = these kernels (clustered form when the graph has a schedule)
-        calls = {
-            "spmm_max_fwd_f256": "gts_spmm_max_fwd_cluster_f32: spmm_cluster_stream_kernel<fwd> (from 100 000 rows), else gts_spmm_max_fwd_f32",
-            "spmm_max_bwd_f256": "gts_spmm_max_bwd_cluster_f32: spmm_cluster_stream_kernel<bwd>, else gts_spmm_max_bwd_f32",
-            "gat_fwd": "gts_gat_fwd_cluster_f32: gat_weights_one_chunk_kernel (edge softmax) + gat_cluster_stream_kernel<fwd>, "
-                       "else gts_gat_fwd_f32",
-            "gat_bwd_edge": "gts_gat_bwd_edge_cluster_f32: gat_cluster_stream_kernel<edge> + gat_edge_finish_kernel (graphs with a "
-                            "'gat_edge_in' schedule: in-degree <= 8, >= 20 000 rows), else gts_gat_bwd_edge_f32: gat_bwd_edge_kernel",
-            "gat_bwd_src": "gts_gat_bwd_src_cluster_f32: gat_weights_one_chunk_kernel + gat_cluster_stream_kernel<bwd>, "
-                           "else gts_gat_bwd_src_f32",
-            "project_rows": "gts_project_rows_i16: project_rows_kernel",
-        }
-        hbm = []
-        for name in cfg["hbm_kernels"]:
-            s = timers.summary(name)
-            if not s:
-                continue
-            us = 1e3 * s["total_ms"] / s["launches"]
-            need = compulsory_bytes(name, n_b, e_b, arg_b)
-            alg = algorithmic_bytes(name, n_b, e_b, arg_b)
-            pmc_file = "pmc_traffic_c3.json" if args.config == "c3" else f"pmc_traffic{'_' + tag[:-1] if tag else ''}.json"
-            traffic, source = from_profile(pmc_file, name + "_bytes_per_launch")
-            rocprof_us, rsource = from_profile("rocprof_kernel_avg.json", (tag or "") + name + "_avg_us")
-            gbs = need / (us * 1e-6) / 1e9
-            hbm.append({"bound": "hbm", "kernel": name, "call": calls.get(name), "model": "compulsory bytes: every input/output array once",
-                        "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(gbs / HBM_PEAK_GBS, 4), "compulsory_bytes_per_launch": need,
-                        "traffic": traffic, "traffic_source": source,
-                        "algorithmic_bytes_per_launch": alg,
-                        "algorithmic_gbs": round(alg / (us * 1e-6) / 1e9, 1),
-                        "avg_launch_us": round(us, 2), "launches_timed": s["launches"],
-                        "rocprof_avg_launch_us": rocprof_us, "rocprof_source": rsource, "sample": sample, "path": path})
-        result["roofline_hbm"] = hbm
-        if "roofline" not in result and hbm:
-            result["roofline"] = hbm[0]
-        ar = timers.summary("all_reduce")
-        if ar:
-            result["all_reduce"] = {"payload_bytes": int(model.grad_sync.flat.numel() * 4),
-                                    "avg_us": round(1e3 * ar["total_ms"] / ar["launches"], 1),
-                                    "launches_timed": ar["launches"]}
-        if per_rank is not None:
-            step_ms = [1e3 * r[0] for r in per_rank]
-            result["per_rank"] = {"step_ms": [round(v, 4) for v in step_ms], "step_ms_max": round(max(step_ms), 4),
-                                  "step_ms_min": round(min(step_ms), 4),
-                                  "all_reduce_us": [round(1e3 * r[1], 1) for r in per_rank],
-                                  "note": "own wall time per step of the last timed block (fences on both sides), and the mean "
-                                          "duration of the rank's all-reduce launches in the instrumented block: a rank with "
-                                          "less work waits longer inside the collective"}
-        if world == 1 and not args.no_cpu_baseline and args.config != "c5":
-            cpu_steps = 1 if args.config == "c3" else args.cpu_steps   # a GAT step takes ~1 min on the CPU
-            result["cpu_baseline"] = cpu_baseline(cfg, args.graphs_per_gpu, args.graph_kind, cpu_steps)
+        if args.full:
+            arg_b = batches[0][0].arg_bytes
+            # the committed profiles ran the lattice workload at 4, 8 and 32 graphs per GPU (C2 / C3 models)
+            tag = "real_" if args.config == "real" else {4: "", 8: "b8_", 32: "b32_"}.get(args.graphs_per_gpu)
+            profiled = tag is not None and args.graph_kind == "lattice" and args.config in ("c2", "c3", "c4", "c5", "real")
+
+            def from_profile(fname, key):
+                path = os.path.join(REPO, "profiles", fname)
+                if not (profiled and os.path.exists(path)):
+                    return None, None
+                with open(path) as fh:
+                    value = json.load(fh).get(key)
+                return (value, "profiles/" + fname) if value is not None else (None, None)
+
+            # --- K11, where most of the step goes (all three GEMM forms are one kernel template)
+            kinds = {k: timers.summary("gemm_" + k) for k in ("fwd", "igrad", "wgrad")}
+            kinds = {k: v for k, v in kinds.items() if v}
+            sample = f"HIP events around every launch in one extra block of {args.steps} steps after the timed blocks"
+            # the timed blocks issue the SAGE-pool layer stack through the one-call entry points (gts_sage_pool_stack_*_f32);
+            # events need single launches, so the instrumented block issues the same kernels, in the same order, one library
+            # call each (gts/nn.py::_SagePoolStack) — same device work, more host calls
+            path = ("launch-by-launch: one C-ABI call per kernel (the timed blocks enqueue the same launches through "
+                    "gts_sage_pool_stack_fwd_f32 / _bwd_f32)") if cfg["model"] == "GSpool" else "as in the timed blocks"
+            if kinds:
+                flops = sum(v["work"] for v in kinds.values())
+                secs = sum(v["total_ms"] for v in kinds.values()) * 1e-3
+                tf = flops / secs / 1e12
+                result["roofline"] = {
+                    "bound": "mfma",
+                    "kernel": "K11, every forward / input-gradient / weight-gradient launch of the step: "
+                              "gts::gemm_panel_direct_kernel (16x16x4 MFMA row panels: the chained layer GEMMs, ~58 % of a C2 step) "
+                              "and gts::wgrad_stream_kernel (32x32x2 MFMA split-reduction weight gradients, ~25 %)",
+                    "achieved": round(tf, 1), "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": round(tf / MFMA_F32_PEAK_TFLOPS, 4), "traffic": None,
+                    "flops_per_step": flops / args.steps, "gemm_ms_per_step": round(1e3 * secs / args.steps, 4),
+                    "share_of_step": round(secs / instrumented, 3), "path": path,
+                    "by_kind": {k: {"launches_per_step": v["launches"] / args.steps,
+                                    "avg_launch_us": round(1e3 * v["total_ms"] / v["launches"], 2),
+                                    "tflops": round(v["work"] / (v["total_ms"] * 1e-3) / 1e12, 1)}
+                                for k, v in kinds.items()},
+                    "sample": sample}
+            # --- the HBM-bound kernels of the path: fraction from COMPULSORY bytes (each array once)
+            # what the events of an entry bracket: one library call = these kernels (clustered form when the graph has a schedule)
+            calls = {
+                "spmm_max_fwd_f256": "gts_spmm_max_fwd_cluster_f32: spmm_cluster_stream_kernel<fwd> (from 100 000 rows), "
+                                     "else gts_spmm_max_fwd_f32",
+                "spmm_max_bwd_f256": "gts_spmm_max_bwd_cluster_f32: spmm_cluster_stream_kernel<bwd>, else gts_spmm_max_bwd_f32",
+                "gat_fwd": "gts_gat_fwd_cluster_f32: gat_weights_one_chunk_kernel (edge softmax) + gat_cluster_stream_kernel<fwd>, "
+                           "else gts_gat_fwd_f32",
+                "gat_bwd_edge": "gts_gat_bwd_edge_cluster_f32: gat_cluster_stream_kernel<edge> + gat_edge_finish_kernel (graphs with a "
+                                "'gat_edge_in' schedule: in-degree <= 8, >= 20 000 rows), else gts_gat_bwd_edge_f32: gat_bwd_edge_kernel",
+                "gat_bwd_src": "gts_gat_bwd_src_cluster_f32: gat_weights_one_chunk_kernel + gat_cluster_stream_kernel<bwd>, "
+                               "else gts_gat_bwd_src_f32",
+                "project_rows": "gts_project_rows_i16: project_rows_kernel",
+            }
+            hbm = []
+            for name in cfg["hbm_kernels"]:
+                s = timers.summary(name)
+                if not s:
+                    continue
+                us = 1e3 * s["total_ms"] / s["launches"]
+                need = compulsory_bytes(name, n_b, e_b, arg_b)
+                alg = algorithmic_bytes(name, n_b, e_b, arg_b)
+                pmc_file = "pmc_traffic_c3.json" if args.config == "c3" else f"pmc_traffic{'_' + tag[:-1] if tag else ''}.json"
+                traffic, source = from_profile(pmc_file, name + "_bytes_per_launch")
+                rocprof_us, rsource = from_profile("rocprof_kernel_avg.json", (tag or "") + name + "_avg_us")
+                gbs = need / (us * 1e-6) / 1e9
+                hbm.append({"bound": "hbm", "kernel": name, "call": calls.get(name),
+                            "model": "compulsory bytes: every input/output array once",
+                            "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": round(gbs / HBM_PEAK_GBS, 4), "compulsory_bytes_per_launch": need,
+                            "traffic": traffic, "traffic_source": source,
+                            "algorithmic_bytes_per_launch": alg,
+                            "algorithmic_gbs": round(alg / (us * 1e-6) / 1e9, 1),
+                            "avg_launch_us": round(us, 2), "launches_timed": s["launches"],
+                            "rocprof_avg_launch_us": rocprof_us, "rocprof_source": rsource, "sample": sample, "path": path})
+            result["roofline_hbm"] = hbm
+            if "roofline" not in result and hbm:
+                result["roofline"] = hbm[0]
+            ar = timers.summary("all_reduce")
+            if ar:
+                result["all_reduce"] = {"payload_bytes": int(model.grad_sync.flat.numel() * 4),
+                                        "avg_us": round(1e3 * ar["total_ms"] / ar["launches"], 1),
+                                        "launches_timed": ar["launches"]}
+            if per_rank is not None:
+                step_ms = [1e3 * r[0] for r in per_rank]
+                result["per_rank"] = {"step_ms": [round(v, 4) for v in step_ms], "step_ms_max": round(max(step_ms), 4),
+                                      "step_ms_min": round(min(step_ms), 4),
+                                      "all_reduce_us": [round(1e3 * r[1], 1) for r in per_rank],
+                                      "note": "own wall time per step of the last timed block (fences on both sides), and the mean "
+                                              "duration of the rank's all-reduce launches in the instrumented block: a rank with "
+                                              "less work waits longer inside the collective"}
+            if world == 1 and not args.no_cpu_baseline and args.config != "c5":
+                cpu_steps = 1 if args.config == "c3" else args.cpu_steps   # a GAT step takes ~1 min on the CPU
+                result["cpu_baseline"] = cpu_baseline(cfg, args.graphs_per_gpu, args.graph_kind, cpu_steps)
         print(json.dumps(result), flush=True)
     if world > 1:
         torch.distributed.barrier()

@@ -3,6 +3,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -58,12 +59,62 @@ def test_timed_steps_and_output_dump_helpers(tmp_path):
     assert not (tmp_path / "big").exists()
 
 
+def test_full_is_an_option_and_off_by_default():
+    """A plain run measures the headline only; the rooflines, per-rank figures and CPU baseline wait for --full."""
+    import bench
+
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.full is False and (plain.gpus, plain.steps, plain.warmup) == (1, 7, 2)
+    full = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2", "--full"])
+    assert full.full is True and (full.gpus, full.steps, full.warmup) == (1, 7, 2)
+
+
+HEADLINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                 "scaling", "vs_baseline", "dtype", "data", "config", "blocks", "ranks", "backend")
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_plain_bench_prints_the_headline_only_and_dumps_what_full_dumps(hip_lib, tmp_path):
+    """Without --full: the headline line, nothing that needs runs of its own, the same dumped arrays as a --full run
+    of the same arguments, and at most 30 s outside the warm-up and timed steps."""
+    import numpy as np
+
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--blocks", "2"]
+    runs = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        t0 = time.perf_counter()
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), *args, *extra,
+                              "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=550, cwd=REPO)
+        wall = time.perf_counter() - t0
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, out.stdout
+        runs[name] = (json.loads(lines[0]), wall)
+    d, wall = runs["plain"]
+    assert set(d) == set(HEADLINE_KEYS), sorted(d)
+    assert d["unit"] == "graphs/s" and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0
+    assert d["dtype"] == "f32" and d["higher_is_better"] is True and d["blocks"]["steps_per_block"] == [2, 1]
+    assert abs(d["value"] * d["ms_per_step"] - 1e3 * d["config"]["global_batch"]) < 1e-2 * d["value"]
+    assert wall - (3 + 1) * d["ms_per_step"] * 1e-3 < 30.0, wall
+    f = runs["full"][0]
+    assert "roofline" in f and "roofline_hbm" in f and "cpu_baseline" not in f
+    same = ("workload", "global_batch", "nodes_per_batch", "edges_per_batch", "parallelism")
+    assert [f["config"][k] for k in same] == [d["config"][k] for k in same]
+    assert abs(f["config"]["last_value"] - d["config"]["last_value"]) < 1e-5 * max(1.0, d["config"]["last_value"])
+    files = sorted(os.listdir(tmp_path / "plain"))
+    assert files == sorted(os.listdir(tmp_path / "full")) and len(files) == 41
+    for fname in files:
+        np.testing.assert_allclose(np.load(tmp_path / "plain" / fname), np.load(tmp_path / "full" / fname),
+                                   rtol=1e-5, atol=1e-6, err_msg=fname)
+
+
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
 def test_bench_prints_one_json_line_with_the_contract_fields(hip_lib, tmp_path):
     dump = tmp_path / "outputs"
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1",
-                          "--blocks", "2", "--cpu-steps", "1", "--dump-outputs", str(dump)],
+                          "--blocks", "2", "--cpu-steps", "1", "--full", "--dump-outputs", str(dump)],
                          capture_output=True, text=True, timeout=550, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -115,7 +166,7 @@ def test_bench_gpus_2_starts_its_own_ranks(hip_lib):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(GTS_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2",
-                          "--warmup", "1", "--blocks", "2", "--graphs-per-gpu", "1"],
+                          "--warmup", "1", "--blocks", "2", "--graphs-per-gpu", "1", "--full"],
                          capture_output=True, text=True, timeout=550, cwd=REPO, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
@@ -134,7 +185,7 @@ def test_bench_gpus_2_starts_its_own_ranks(hip_lib):
                                              ("real", ["spmm_max_fwd_f256", "spmm_max_bwd_f256"])])
 def test_other_configs_keep_the_contract(hip_lib, config, kernels):
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--config", config, "--steps", "2",
-                          "--warmup", "1", "--blocks", "1", "--no-cpu-baseline"], capture_output=True, text=True,
+                          "--warmup", "1", "--blocks", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True,
                          timeout=550, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])

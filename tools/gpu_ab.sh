@@ -11,7 +11,7 @@ i=0
 for envs in "$@"; do
   i=$((i+1))
   echo "== [$i] $envs" | tee -a $OUT/ab.log
-  env $envs timeout -k 10 300 python bench.py $FLAGS > $OUT/ab_$i.json 2> $OUT/ab_$i.err || { tail -20 $OUT/ab_$i.err; exit 1; }
+  env $envs timeout -k 10 300 python bench.py --full $FLAGS > $OUT/ab_$i.json 2> $OUT/ab_$i.err || { tail -20 $OUT/ab_$i.err; exit 1; }
   python - $OUT/ab_$i.json <<'PY' | tee -a $OUT/ab.log
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ TAG=${1:-rXX}; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for envs in "$@"; do
   echo "== $envs" | tee -a $OUT/ab.log
-  env $envs timeout -k 10 200 python bench.py --config c3 --no-cpu-baseline --blocks 6 > $OUT/x.json 2> $OUT/x.err || { tail -5 $OUT/x.err; exit 1; }
+  env $envs timeout -k 10 200 python bench.py --config c3 --full --no-cpu-baseline --blocks 6 > $OUT/x.json 2> $OUT/x.err || { tail -5 $OUT/x.err; exit 1; }
   python - $OUT/x.json <<'PY' | tee -a $OUT/ab.log
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -12,7 +12,7 @@ for b in $BS; do
   i=0
   for envs in "$@"; do
     i=$((i+1))
-    env $envs timeout -k 10 300 python bench.py --graphs-per-gpu $b --steps $steps --warmup 3 --blocks 5 --no-cpu-baseline > $OUT/ab_b${b}_$i.json 2> $OUT/ab_b${b}_$i.err || { tail -20 $OUT/ab_b${b}_$i.err; exit 1; }
+    env $envs timeout -k 10 300 python bench.py --graphs-per-gpu $b --steps $steps --warmup 3 --blocks 5 --full --no-cpu-baseline > $OUT/ab_b${b}_$i.json 2> $OUT/ab_b${b}_$i.err || { tail -20 $OUT/ab_b${b}_$i.err; exit 1; }
     python - $OUT/ab_b${b}_$i.json "b=$b [$envs]" <<'PY' | tee -a $OUT/ab.log
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ TAG=${1:-rXX}; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for envs in "$@"; do
   echo "== $envs" | tee -a $OUT/ab.log
-  env $envs timeout -k 10 200 python bench.py --config real --steps 40 --warmup 8 --blocks 10 --no-cpu-baseline > $OUT/x.json 2> $OUT/x.err || { tail -5 $OUT/x.err; exit 1; }
+  env $envs timeout -k 10 200 python bench.py --config real --steps 40 --warmup 8 --blocks 10 --full --no-cpu-baseline > $OUT/x.json 2> $OUT/x.err || { tail -5 $OUT/x.err; exit 1; }
   python - $OUT/x.json <<'PY' | tee -a $OUT/ab.log
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

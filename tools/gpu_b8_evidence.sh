@@ -9,7 +9,7 @@ B=${2:-8}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-FLAGS="--graphs-per-gpu $B --no-cpu-baseline"
+FLAGS="--graphs-per-gpu $B --full --no-cpu-baseline"
 timeout -k 10 300 python bench.py $FLAGS --steps 10 --warmup 3 --blocks 5 > $OUT/bench_c2_b$B.json 2> $OUT/bench_c2_b$B.err || { tail -20 $OUT/bench_c2_b$B.err; exit 1; }
 tail -1 $OUT/bench_c2_b$B.json | cut -c1-200
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_b$B -- python bench.py $FLAGS --steps 5 --warmup 2 --blocks 1 > $OUT/prof_b$B.log 2> $OUT/prof_b$B.err || exit 1

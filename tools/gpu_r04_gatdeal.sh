@@ -13,7 +13,7 @@ for opt in "17=1" "17=0" "17=1" "17=0"; do
   GTS_OPTIONS="$opt" timeout -k 10 200 python tools/diag/gat_passes_ab.py --group 16 2>&1 | grep -v amdgpu.ids | tee -a $OUT/ab.log
 done
 for opt in "17=1" "17=0" "17=1" "17=0"; do
-  GTS_OPTIONS="$opt" timeout -k 10 300 python bench.py --config c3 --steps 10 --warmup 3 --blocks 5 --no-cpu-baseline > $OUT/c3.json 2> $OUT/c3.err || { tail -5 $OUT/c3.err; exit 1; }
+  GTS_OPTIONS="$opt" timeout -k 10 300 python bench.py --config c3 --steps 10 --warmup 3 --blocks 5 --full --no-cpu-baseline > $OUT/c3.json 2> $OUT/c3.err || { tail -5 $OUT/c3.err; exit 1; }
   python - $OUT/c3.json "$opt" <<'PY' | tee -a $OUT/c3.log
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -13,7 +13,7 @@ for args in "" "--waves 8"; do
   echo "== $args"
   timeout -k 10 200 python tools/diag/gat_passes_ab.py --group 16 $args 2>&1 | grep -v amdgpu.ids | tee -a $OUT/ab.log
 done
-timeout -k 10 300 python bench.py --config c3 --steps 10 --warmup 3 --blocks 5 --no-cpu-baseline > $OUT/c3.json 2> $OUT/c3.err || { tail -5 $OUT/c3.err; exit 1; }
+timeout -k 10 300 python bench.py --config c3 --steps 10 --warmup 3 --blocks 5 --full --no-cpu-baseline > $OUT/c3.json 2> $OUT/c3.err || { tail -5 $OUT/c3.err; exit 1; }
 python - $OUT/c3.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

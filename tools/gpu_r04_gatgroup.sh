@@ -8,7 +8,7 @@ GTS_OPTIONS="16=16" timeout -k 10 300 python -m pytest tests/test_gpu_gat_cluste
 echo "pytest (group 16) rc=$?"; tail -2 $OUT/pytest.log
 grep -q " passed" $OUT/pytest.log || exit 1
 for g in 0 8 16 32 64 128 0 16; do
-  GTS_OPTIONS="16=$g" timeout -k 10 300 python bench.py --config c3 --steps 5 --warmup 2 --blocks 3 --no-cpu-baseline > $OUT/c3_$g.json 2> $OUT/c3_$g.err
+  GTS_OPTIONS="16=$g" timeout -k 10 300 python bench.py --config c3 --steps 5 --warmup 2 --blocks 3 --full --no-cpu-baseline > $OUT/c3_$g.json 2> $OUT/c3_$g.err
   python - $OUT/c3_$g.json $g <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ timeout -k 10 900 python -m pytest tests/test_gpu_model.py tests/test_gpu_full_s
 echo "pytest rc=$?"; tail -2 $OUT/pytest.log
 grep -q " passed" $OUT/pytest.log || exit 1
 for v in 1 0 1 0; do
-  GTS_PACK_GAT=$v timeout -k 10 300 python bench.py --config c3 --steps 10 --warmup 3 --blocks 5 --no-cpu-baseline > $OUT/c3_$v.json 2> $OUT/c3_$v.err
+  GTS_PACK_GAT=$v timeout -k 10 300 python bench.py --config c3 --steps 10 --warmup 3 --blocks 5 --full --no-cpu-baseline > $OUT/c3_$v.json 2> $OUT/c3_$v.err
   python - $OUT/c3_$v.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r = d["roofline"]

@@ -17,7 +17,7 @@ done
 for lib in prev new prev new; do
   if [ $lib = prev ]; then export GTS_LIB_PATH=$PREV; else unset GTS_LIB_PATH; fi
   for cfg in "" "--config real"; do
-    timeout -k 10 300 python bench.py $cfg --steps 20 --warmup 5 --blocks 10 --no-cpu-baseline > $OUT/b.json 2> $OUT/b.err || { tail -5 $OUT/b.err; exit 1; }
+    timeout -k 10 300 python bench.py $cfg --steps 20 --warmup 5 --blocks 10 --full --no-cpu-baseline > $OUT/b.json 2> $OUT/b.err || { tail -5 $OUT/b.err; exit 1; }
     python - $OUT/b.json "$lib $cfg" <<'PY' | tee -a $OUT/bench.log
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ OUT=gpurun_out/${1:-r04tr}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for cfg in c2 real; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_$cfg -- python bench.py --config $cfg --steps 3 --warmup 2 --blocks 1 --no-cpu-baseline > $OUT/trace_$cfg.log 2> $OUT/trace_$cfg.err || { tail -5 $OUT/trace_$cfg.err; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace_$cfg -- python bench.py --config $cfg --steps 3 --warmup 2 --blocks 1 --full --no-cpu-baseline > $OUT/trace_$cfg.log 2> $OUT/trace_$cfg.err || { tail -5 $OUT/trace_$cfg.err; exit 1; }
   python tools/step_trace.py $OUT/trace_$cfg $OUT/step_$cfg.md $([ $cfg = c2 ] && echo 3 || echo 0) > /dev/null
   rm -rf $OUT/trace_$cfg
 done

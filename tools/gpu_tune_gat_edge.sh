@@ -6,7 +6,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 run() {
   local label=$1; shift
-  env "$@" timeout -k 10 200 python bench.py --config c3 --no-cpu-baseline --blocks 4 > $OUT/c3_$label.json 2> $OUT/c3_$label.err || { tail -5 $OUT/c3_$label.err; return 1; }
+  env "$@" timeout -k 10 200 python bench.py --config c3 --full --no-cpu-baseline --blocks 4 > $OUT/c3_$label.json 2> $OUT/c3_$label.err || { tail -5 $OUT/c3_$label.err; return 1; }
   python - $OUT/c3_$label.json "$label" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -52,12 +52,12 @@ def mean_us(rows, needle):
     return round(sum(float(r["TotalDurationNs"]) for r in hit) / calls / 1e3, 2), calls
 
 
-c2 = stats("prof", f"{rnd}_bench", 65, f"Round {rnd[1:]}: bench.py --steps 20 --warmup 5 --blocks 2 (C2; 5 warm-up + 2 timed blocks + 1 "
+c2 = stats("prof", f"{rnd}_bench", 65, f"Round {rnd[1:]}: bench.py --steps 20 --warmup 5 --blocks 2 --full (C2; 5 warm-up + 2 timed blocks + 1 "
            "instrumented block = 65 steps)")
-c3 = stats("prof_c3", f"{rnd}_bench_c3", 12, f"Round {rnd[1:]}: bench.py --config c3 --steps 5 --warmup 2 --blocks 1 (GAT 4x4x256; 2 + 5 + 5 = 12 steps)")
-b8 = stats("prof_b8", f"{rnd}_bench_c2_b8", 12, f"Round {rnd[1:]}: bench.py --config c4 --steps 5 --warmup 2 --blocks 1 (8 graphs per GPU; 2 + 5 + 5 = 12 steps)")
-b32 = stats("prof_b32", f"{rnd}_bench_c2_b32", 7, f"Round {rnd[1:]}: bench.py --graphs-per-gpu 32 --steps 3 --warmup 1 --blocks 1 (1 + 3 + 3 = 7 steps)")
-real = stats("prof_real", f"{rnd}_bench_real", 105, f"Round {rnd[1:]}: bench.py --config real --steps 20 --warmup 5 --blocks 1 (5 + 20 + 20 fresh-batch steps + 3 x 20 resident)")
+c3 = stats("prof_c3", f"{rnd}_bench_c3", 12, f"Round {rnd[1:]}: bench.py --config c3 --steps 5 --warmup 2 --blocks 1 --full (GAT 4x4x256; 2 + 5 + 5 = 12 steps)")
+b8 = stats("prof_b8", f"{rnd}_bench_c2_b8", 12, f"Round {rnd[1:]}: bench.py --config c4 --steps 5 --warmup 2 --blocks 1 --full (8 graphs per GPU; 2 + 5 + 5 = 12 steps)")
+b32 = stats("prof_b32", f"{rnd}_bench_c2_b32", 7, f"Round {rnd[1:]}: bench.py --graphs-per-gpu 32 --steps 3 --warmup 1 --blocks 1 --full (1 + 3 + 3 = 7 steps)")
+real = stats("prof_real", f"{rnd}_bench_real", 105, f"Round {rnd[1:]}: bench.py --config real --steps 20 --warmup 5 --blocks 1 --full (5 + 20 + 20 fresh-batch steps + 3 x 20 resident)")
 stats("prof_aux", f"{rnd}_aux", 1, f"Round {rnd[1:]}: tools/measure_aux_kernels.py (streaming kernels around the network)")
 K1 = (("spmm_cluster_stream_kernel<false, 1",), ("spmm_max_fwd_kernel<4, 64, 1>",))     # clustered form first, plain form otherwise
 K2 = (("spmm_cluster_stream_kernel<true, 1",), ("spmm_max_bwd_kernel<4, 64, 1>",))
@@ -74,7 +74,7 @@ def first_mean(rows, needles):
 
 panel, panel_calls = mean_us(c2, ("gemm_panel_direct_kernel<3, 4, 1",))
 avg = {"source": f"{dst}/{rnd}_bench_kernel_stats.csv (rocprofv3 --kernel-trace --stats of `bench.py --steps 20 --warmup 5 --blocks 2 "
-                 "--no-cpu-baseline`, kernel-only durations)",
+                 "--full --no-cpu-baseline`, kernel-only durations)",
        "gemm_panel_direct_avg_us": panel, "gemm_panel_direct_calls": panel_calls,
        "gemm_wgrad_256x256_avg_us": mean_us(c2, ("wgrad_stream_kernel",) if any("wgrad_stream_kernel" in n for n in c2)
                                              else ("gemm_kernel<256, 256, 4, 4, false, false, true",))[0]}

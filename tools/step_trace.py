@@ -2,7 +2,7 @@
 """Kernel sequence of ONE training step out of a rocprofv3 --kernel-trace CSV: the launches between two consecutive
 adamw_kernel launches (the last full step of the trace), in start order, with durations and the idle gap in front of each.
   python tools/step_trace.py <dir with *_kernel_trace.csv> [out.md] [steps back from the last one, default 0]
-(bench.py's last block runs launch by launch with HIP events: with --steps K pass K to look at a step of the timed blocks)"""
+(the last block of bench.py --full runs launch by launch with HIP events: with --steps K pass K to look at a step of the timed blocks)"""
 import csv
 import glob
 import os
