@@ -114,6 +114,34 @@ def read_nifti(fp, data_type):
     return np.array(data, dtype=data_type)
 
 
+RAW_DTYPES = (np.dtype(np.int16), np.dtype(np.float32))
+
+
+def _header(raw):
+    endian = "<" if struct.unpack_from("<i", raw, 0)[0] == 348 else ">"
+    dim = struct.unpack_from(endian + "8h", raw, 40)
+    code, _bits = struct.unpack_from(endian + "hh", raw, 70)
+    vox_offset = int(struct.unpack_from(endian + "f", raw, 108)[0])
+    slope, inter = struct.unpack_from(endian + "ff", raw, 112)
+    return endian, tuple(dim[1:1 + dim[0]]), code, vox_offset, slope, inter
+
+
+def read_nifti_raw(fp):
+    """The volume as the file stores it, without conversion: a read-only x-fastest (Fortran order)
+    view of the decoded bytes, when the file holds little-endian int16 or float32 and no scaling
+    applies (read_nifti's rule).  Any other file comes back as read_nifti(fp, np.float32).  Either
+    way np.float32 of the result equals read_nifti(fp, np.float32)."""
+    with _open(fp, "rb") as f:
+        raw = f.read()
+    endian, shape, code, vox_offset, slope, inter = _header(raw)
+    scaled = (slope not in (0.0, 1.0) or inter != 0.0) and slope != 0.0 and not np.isnan(slope)
+    dt = np.dtype(_CODES.get(code, np.uint8))
+    if endian != "<" or scaled or code not in _CODES or dt not in RAW_DTYPES:
+        return read_nifti(fp, np.float32)
+    data = np.frombuffer(raw, dtype=dt, count=int(np.prod(shape)), offset=max(vox_offset, 352))
+    return data.reshape(shape, order="F")
+
+
 
 def _files_with_suffix(folder, suffix, recursive):
     """Sorted paths under folder whose name ends with suffix."""
@@ -135,6 +163,24 @@ def read_in_patient_sample(scan_dir, modality_exts):
             raise FileNotFoundError(f"{scan_dir}: {len(paths)} files end with {ext!r}, expected exactly one")
         channels.append(read_nifti(paths[0], np.float32))
     return channels[0] if len(channels) == 1 else np.stack(channels, axis=3)
+
+
+def find_modality_files(scan_dir, modality_exts):
+    """Path of each modality of a scan, in the order of modality_exts: read_in_patient_sample's rule
+    (searched below scan_dir, every suffix must match exactly one file)."""
+    paths = []
+    for ext in modality_exts:
+        found = _files_with_suffix(scan_dir, ext, recursive=True)
+        if len(found) != 1:
+            raise FileNotFoundError(f"{scan_dir}: {len(found)} files end with {ext!r}, expected exactly one")
+        paths.append(found[0])
+    return paths
+
+
+def read_in_patient_sample_raw(scan_dir, modality_exts):
+    """One scan's modalities as read_nifti_raw returns them (stored dtype, x-fastest), one array per
+    modality in the order of modality_exts."""
+    return [read_nifti_raw(p) for p in find_modality_files(scan_dir, modality_exts)]
 
 
 def read_in_labels(scan_dir, label_ext):

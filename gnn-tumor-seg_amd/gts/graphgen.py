@@ -323,12 +323,14 @@ def touching_edges(partition, n_nodes):
 
 # ---- whole pipeline -------------------------------------------------------------------------------
 
-def build_graph(voxel_intensities, voxel_labels, approx_num_nodes=5000, boxiness=0.5, k=10, timer=None):
+def build_graph(voxel_intensities, voxel_labels, approx_num_nodes=5000, boxiness=0.5, k=10, timer=None,
+                keep_on_device=False):
     """img2graph's arithmetic without networkx.  Returns a dict with `slic` (int32 labels after
     connectivity), `n_sv`, `partition` (int16, -1 = dropped), `feats`, `centroids`, `labels`
     (numpy) and `edges` = (rows, cols): for k > 0 the undirected kNN pairs (rows < cols), for
     k == 0 the face adjacency in both orientations with self-loops.  timer(name) is called at
-    the end of each stage (host clock hooks for the measurement tool)."""
+    the end of each stage (host clock hooks for the measurement tool).  keep_on_device: `partition`,
+    `feats`, `centroids` and `labels` stay tensors on the device."""
     tick = timer or (lambda name: None)
     d, h, w, c = _volume(voxel_intensities)
     if not 0 < approx_num_nodes <= MAX_SV:
@@ -363,5 +365,27 @@ def build_graph(voxel_intensities, voxel_labels, approx_num_nodes=5000, boxiness
     else:
         edges = touching_edges(new_part, n_nodes)
     tick("edges")
-    return {"slic": slic_host, "n_sv": n_sv, "partition": new_part.cpu().numpy(), "feats": nf.cpu().numpy(),
-            "centroids": nc.cpu().numpy(), "labels": nl.cpu().numpy(), "edges": edges}
+    out = {"partition": new_part, "feats": nf, "centroids": nc, "labels": nl}
+    if not keep_on_device:
+        out = {name: t.cpu().numpy() for name, t in out.items()}
+    return dict(out, slic=slic_host, n_sv=n_sv, edges=edges)
+
+
+def symmetric_pairs(rows, cols):
+    """The distinct (u, v) of the edge list in both orientations, sorted by u, then v: the row-major
+    nonzeros of the symmetric 0/1 matrix with ones at (rows, cols) (a self-loop once)."""
+    r = np.concatenate([rows, cols])
+    c = np.concatenate([cols, rows])
+    order = np.lexsort((c, r))
+    return np.unique(np.stack([r[order], c[order]], axis=1), axis=0)
+
+
+def graph_from_edges(edges, n_nodes):
+    """gts.Graph of build_graph's edge list without networkx: the graph that
+    gts.from_networkx(graph_io.load_networkx_graph(json)) gives for img2graph's networkx graph.
+    Nodes 0..n-1 are inserted in order and the pairs in symmetric_pairs order, so every adjacency
+    list of that graph is ascending and its directed edges are exactly symmetric_pairs."""
+    from .graph import Graph
+
+    pairs = symmetric_pairs(*edges)
+    return Graph(pairs[:, 0], pairs[:, 1], n_nodes)

@@ -59,10 +59,7 @@ def find_adjacent_nodes(regionImg, n_nodes, as_mat=False):
 def _graph(n, rows, cols, weight):
     """networkx.from_numpy_array of the symmetric matrix with ones at (rows, cols): nodes 0..n-1,
     edges inserted in the row-major order of the matrix's nonzeros."""
-    r = np.concatenate([rows, cols])
-    c = np.concatenate([cols, rows])
-    order = np.lexsort((c, r))
-    pairs = np.unique(np.stack([r[order], c[order]], axis=1), axis=0)
+    pairs = gg.symmetric_pairs(rows, cols)
     g = nx.Graph()
     g.add_nodes_from(range(n))
     g.add_edges_from((int(u), int(v), {"weight": weight}) for u, v in pairs)

@@ -52,16 +52,23 @@ def load_nets(gnn_type, gnn_weights, cnn_weights,
     return graph_net, conv_net
 
 
+def _on_device(x, device, dtype=None):
+    """A tensor (kept where it is when already on the device) or an array, as a tensor on device."""
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x), dtype=dtype)
+    return t.to(device=device, dtype=dtype or t.dtype)
+
+
 def predict_one_sample(graph_net, conv_net, graph, node_feats, img, supervoxel_partitioning, relabel=None):
     """int16 label volume of the partitioning's shape: GNN prediction refined by the CNN inside
     the (dilated) box around the GNN-predicted tumour, healthy outside (reference :59-73).
-    `relabel` (optional int16 table on the device) maps the labels on the way out."""
+    `relabel` (optional int16 table on the device) maps the labels on the way out.  The features,
+    image and partitioning may be numpy arrays or tensors already on the device."""
     device = _device()
     with torch.no_grad():
         graph = graph.to(device)
-        node_feats = torch.as_tensor(np.asarray(node_feats), dtype=torch.float32).to(device)
-        img = torch.as_tensor(np.asarray(img), dtype=torch.float32).to(device)
-        svs = torch.as_tensor(np.asarray(supervoxel_partitioning)).to(device)
+        node_feats = _on_device(node_feats, device, torch.float32)
+        img = _on_device(img, device, torch.float32)
+        svs = _on_device(supervoxel_partitioning, device)
         node_logits = graph_net(graph, node_feats).float()
         _, plane_flags = ops.project_argmax_occupancy(svs, node_logits)                     # K12
         crop = tumor_crop_from_plane_flags(*[f.cpu().numpy() for f in plane_flags])

@@ -1,0 +1,167 @@
+"""Raw BraTS scans -> segmentations, end to end on the MI355X: the four modality files of a scan in,
+OUT/{id}.nii.gz out (int16, BraTS size, BraTS label coding).
+
+Per scan: the stored volumes are uploaded as they are (int16 or float32), cropped, normalized and
+standardized on the device (gts.intake, I1-I3), the supervoxel graph is built from the device image
+(gts.graphgen.build_graph) and turned into a gts.Graph without networkx, and the GNN (and, with -c,
+the refinement CNN through generate_joint_predictions.predict_one_sample) predicts.  The result equals
+what `preprocess_dataset` followed by `generate_joint_predictions` (or, without -c,
+`generate_gnn_predictions -f preds`) writes for the same scan and weights, without the intermediate
+files.  Decoding of the next scans and encoding of finished ones run on a small thread pool.
+
+INPUT is a folder that directly holds one scan's modality files (its id is the first modality's file
+name without the suffix), or a folder of scan folders (found as preprocess_dataset finds them).
+A scan that raises is reported and skipped; the exit status is 1 when any scan was skipped.
+
+    python -m scripts.segment_scans -d INPUT -o OUT -g GNN.pt [-c CNN.pt] [-m GSpool] [-n 15000 -b 0.5 -k 10]
+"""
+import argparse
+import os
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+_PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _PKG not in sys.path:
+    sys.path.insert(0, _PKG)
+
+from data_processing import nifti_io  # noqa: E402
+from data_processing.image_processing import uncrop_to_brats_size  # noqa: E402
+from data_processing.labels import INTERNAL_TO_BRATS  # noqa: E402
+from gts import graphgen, intake, ops  # noqa: E402
+from scripts import preprocess_dataset as prep  # noqa: E402
+
+IO_WORKERS = 3     # threads for NIfTI decode / encode around the GPU work
+READ_AHEAD = 2     # scans decoded ahead of the one on the GPU
+
+
+def build_parser():
+    """Graph flags: preprocess_dataset's (same defaults and meanings); model flags: generate_joint_predictions'."""
+    parser = argparse.ArgumentParser(description="Segment raw BraTS scans on MI355X: NIfTI in, labels out")
+    parser.add_argument("-d", "--data_dir", required=True,
+                        help="folder of one scan's modality files, or a folder of scan folders")
+    parser.add_argument("-o", "--output_dir", required=True, help="where {id}.nii.gz goes")
+    parser.add_argument("-g", "--gnn_weights", required=True, help="Path to weights file for graph net")
+    parser.add_argument("-c", "--cnn_weights", default="",
+                        help="Path to weights file for convolutional net; without it the GNN prediction is written")
+    parser.add_argument("-m", "--gnn_type", default="GSpool",
+                        help="What graph learning layer the saved model uses. GSpool, GSmean, GSgcn, GAT")
+    for short, long_name, default, kind, text in prep._FLAGS:
+        if long_name in ("--num_nodes", "--num_neighbors", "--boxiness"):
+            parser.add_argument(short, long_name, default=default, type=kind, help=text)
+    parser.add_argument("-M", "--modality_extensions", nargs="+", default=list(prep.BRATS_MODALITIES),
+                        help="file suffix of each modality, in channel order")
+    parser.add_argument("-p", "--data_prefix", default="", help="common prefix of the scan folders, e.g. BraTS2021")
+    return parser
+
+
+def find_inputs(data_dir, modality_exts, prefix=""):
+    """{scan id: folder}.  A folder that directly holds a file ending with the first modality suffix is
+    one scan, named after that file; otherwise its scan folders are found as preprocess_dataset does."""
+    root = os.path.expanduser(data_dir)
+    first = modality_exts[0]
+    direct = sorted(f for f in os.listdir(root) if f.endswith(first) and os.path.isfile(os.path.join(root, f)))
+    if len(direct) > 1:
+        raise ValueError(f"{root} holds {len(direct)} files ending with {first!r}: one scan per folder")
+    if direct:
+        return {direct[0][:-len(first)]: root}
+    return prep.find_scans(root, prefix)
+
+
+def _device():
+    if not torch.cuda.is_available():
+        raise RuntimeError("segment_scans needs an AMD GPU (no CPU fallback)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+class Segmenter:
+    """Holds the nets and runs the per-scan pipeline."""
+
+    def __init__(self, args):
+        self.args = args
+        self.device = _device()
+        self.k = args.num_neighbors or 0
+        self.mean, self.std = (np.array(s, dtype=np.float32) for s in prep.STANDARDIZATION_STATS)
+        gnn = os.path.expanduser(args.gnn_weights)
+        if args.cnn_weights:
+            from scripts.generate_joint_predictions import load_nets
+
+            self.graph_net, self.conv_net = load_nets(args.gnn_type, gnn, os.path.expanduser(args.cnn_weights))
+        else:
+            from scripts.generate_gnn_predictions import load_net_and_weights
+
+            self.graph_net, self.conv_net = load_net_and_weights(gnn, args.gnn_type).to(self.device), None
+        self.relabel = torch.from_numpy(INTERNAL_TO_BRATS).to(self.device)
+
+    def load(self, folder):
+        """Host stage: decode the modalities and stage them for the upload."""
+        return intake.stage_scan(nifti_io.read_in_patient_sample_raw(folder, self.args.modality_extensions))
+
+    def segment(self, staged, timer=None):
+        """Device stage: int16 label volume at BraTS size in BraTS coding."""
+        tick = timer or (lambda name: None)
+        image, crop, _ = intake.prepare_scan(staged, self.mean, self.std, timer=tick)
+        res = graphgen.build_graph(image, None, self.args.num_nodes, self.args.boxiness, self.k, keep_on_device=True)
+        graph = graphgen.graph_from_edges(res["edges"], res["feats"].shape[0])
+        norm = torch.pow(graph.in_degrees().float(), -0.5)          # data_loader.ImageGraphDataset.get_graph
+        norm[torch.isinf(norm)] = 0
+        graph.ndata["norm"] = norm.unsqueeze(1)
+        feats = res["feats"].to(torch.float32)
+        partition = res["partition"]
+        tick("graph")
+        if self.conv_net is not None:
+            from scripts.generate_joint_predictions import predict_one_sample
+
+            pred = predict_one_sample(self.graph_net, self.conv_net, graph, feats, image, partition, self.relabel)
+        else:
+            with torch.no_grad():
+                logits = self.graph_net(graph.to(self.device), feats)
+            pred = ops.project_argmax(partition, logits.float(), self.relabel).cpu().numpy()
+        tick("predict")
+        return uncrop_to_brats_size(crop, pred)
+
+    def store(self, scan_id, volume):
+        """Host stage: gzip NIfTI encode."""
+        nifti_io.save_as_nifti(volume, os.path.join(self.output_dir, scan_id + ".nii.gz"))
+
+    def run(self, scans, output_dir):
+        """Segment every scan of {id: folder}; returns the ids that were skipped."""
+        self.output_dir = output_dir
+        os.makedirs(output_dir, exist_ok=True)
+        ids = sorted(scans)
+        failed, writes = [], []
+        with ThreadPoolExecutor(max_workers=IO_WORKERS) as pool:
+            pending = {i: pool.submit(self.load, scans[ids[i]]) for i in range(min(READ_AHEAD, len(ids)))}
+            for i, scan_id in enumerate(ids):
+                if i + READ_AHEAD < len(ids):
+                    pending[i + READ_AHEAD] = pool.submit(self.load, scans[ids[i + READ_AHEAD]])
+                try:
+                    volume = self.segment(pending.pop(i).result())
+                except Exception as exc:
+                    print(f"{scan_id}: skipped ({exc!r})")
+                    failed.append(scan_id)
+                    continue
+                writes.append((scan_id, pool.submit(self.store, scan_id, volume)))
+            for scan_id, job in writes:
+                try:
+                    job.result()
+                    print(f"{scan_id}: done")
+                except Exception as exc:
+                    print(f"{scan_id}: writing failed ({exc!r})")
+                    failed.append(scan_id)
+        return failed
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    scans = find_inputs(args.data_dir, args.modality_extensions, args.data_prefix)
+    print(f"{len(scans)} scan(s) found; segmentations go to {args.output_dir}")
+    failed = Segmenter(args).run(scans, os.path.expanduser(args.output_dir))
+    print(f"segmentation finished, {len(failed)} scan(s) skipped")
+    return 1 if failed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

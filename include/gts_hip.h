@@ -647,6 +647,34 @@ int32_t gts_hd95_order_stats_i16(const int16_t* pred, const int16_t* truth, int6
                                  int32_t all_border, int64_t* out, void* workspace, int64_t workspace_bytes,
                                  void* stream);
 
+/* ---- I1-I3: intake of a raw four-modality scan --------------------------------------------------------
+ * The host step of DataPreprocessor.load (scripts/preprocess_dataset.py) on the device:
+ *   crop = determine_brain_crop(image); image = standardize_img(normalize_img(image[crop]), mean, std).
+ * src: the four modality volumes as NIfTI stores them, [4][Z][Y][X] (x fastest), dtype given by its NIfTI
+ * code: 4 (int16) or 16 (float32), else GTS_ERR_ARGKIND; values are taken as float32.  Every extent in
+ * [1, 4096] and X * Y * Z < 2^31, else GTS_ERR_SHAPE.
+ * gts_intake_occupancy (I1): flag_x[X], flag_y[Y], flag_z[Z] (int32) = 1 where the plane holds a voxel whose
+ * np.amax over the channels is > 0.01 (a NaN in any channel: not counted), else 0; nonfinite (one uint64) = the
+ * number of voxels with a non-finite value in some channel.  Buffers are cleared by the call.
+ * Crops: xs[cx], ys[cy], zs[cz] are plane indices inside the volume (the nonzeros of I1's flags); the cropped
+ * region is their outer product (np.ix_), x fastest, n = cx * cy * cz, 1 <= cx <= X, 1 <= cy <= Y, 1 <= cz <= Z.
+ * gts_intake_order_stats (I2): out (device float32 [4][2]) = the values at ranks rank_lo and rank_hi
+ * (0 <= rank_lo <= rank_hi < n) of each channel's cropped values in ascending order; -0.0 counts as +0.0
+ * (and is returned as +0.0).  Radix select on the order-preserving key, exact; workspace:
+ * gts_intake_select_workspace() bytes.
+ * gts_intake_standardize (I3): out (device float32, C-order [cx][cy][cz][4]) = ((v / top_c) - mean_c) /
+ * std_c in IEEE float32, params = HOST float32 [3][4] (top, mean, std), copied at launch. */
+int32_t gts_intake_occupancy(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, int32_t* flag_x,
+                             int32_t* flag_y, int32_t* flag_z, uint64_t* nonfinite, void* stream);
+int64_t gts_intake_select_workspace(void);
+int32_t gts_intake_order_stats(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, const int32_t* xs,
+                               int64_t cx, const int32_t* ys, int64_t cy, const int32_t* zs, int64_t cz,
+                               int64_t rank_lo, int64_t rank_hi, float* out, void* workspace, int64_t workspace_bytes,
+                               void* stream);
+int32_t gts_intake_standardize(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, const int32_t* xs,
+                               int64_t cx, const int32_t* ys, int64_t cy, const int32_t* zs, int64_t cz,
+                               const float* params, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
