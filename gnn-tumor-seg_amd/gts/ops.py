@@ -491,11 +491,132 @@ class CropBox:
             self.host.append(idx)
         self.shape = tuple(len(i) for i in self.host)
         self.dev = [torch.from_numpy(i.astype(np.int32)).to(device) for i in self.host]
+        self.device = device
+        self._inverse_dev = None
 
     def as_ix(self):
         import numpy as np
 
         return np.ix_(*self.host)
+
+    def inverse_host(self):
+        """Per axis, int32 [extent]: plane index of the volume -> its index inside the crop, -1 for a plane
+        outside it (what the adjoint of crop_concat_rows reads)."""
+        import numpy as np
+
+        tables = []
+        for idx, extent in zip(self.host, self.volume_shape):
+            inv = np.full(extent, -1, dtype=np.int32)
+            inv[idx] = np.arange(len(idx), dtype=np.int32)
+            tables.append(inv)
+        return tables
+
+    def inverse_dev(self):
+        if self._inverse_dev is None:
+            self._inverse_dev = [torch.from_numpy(t).to(self.device) for t in self.inverse_host()]
+        return self._inverse_dev
+
+
+def supervoxel_voxel_lists(svs, n_rows):
+    """(list_ptr int32 [n_rows + 1], list_vox int32) of a partitioning [X, Y, Z] (integer array on the host):
+    for every table row n the C-order linear indices of the voxels whose id resolves to n, ascending.  An id
+    resolves as numpy indexes `table_plus_bg[id]` (negative ids wrap over n_rows + 1 rows); voxels that take
+    the background row, or an id outside the table, are in no list.  Independent of any crop box."""
+    import numpy as np
+
+    ids = np.asarray(svs).reshape(-1).astype(np.int64)
+    if ids.size >= 2 ** 31:
+        raise _lib.GtsError("partitioning too large for int32 voxel indices")
+    rows = np.where(ids < 0, ids + n_rows + 1, ids)
+    vox = np.flatnonzero((rows >= 0) & (rows < n_rows))
+    order = np.argsort(rows[vox], kind="stable")          # stable: raster order inside every row
+    counts = np.bincount(rows[vox], minlength=n_rows)[:n_rows] if n_rows else np.zeros(0, dtype=np.int64)
+    list_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    return list_ptr, vox[order].astype(np.int32)
+
+
+class SupervoxelLists:
+    """One sample's device-resident partitioning (`svs`, int16 [X, Y, Z]) together with its
+    supervoxel_voxel_lists for `n_rows` table rows: built once per sample, J2 reads the lists for every box.
+    A tensor already on `device` is kept as it is (contiguous), anything else is uploaded."""
+
+    def __init__(self, svs, n_rows, device):
+        import numpy as np
+
+        host = svs.detach().cpu().numpy() if isinstance(svs, torch.Tensor) else np.ascontiguousarray(svs)
+        if host.ndim != 3 or host.dtype != np.int16:
+            raise _lib.GtsError("supervoxel partitioning must be a 3-D int16 volume")
+        on_device = isinstance(svs, torch.Tensor) and svs.device == torch.device(device) and svs.is_contiguous()
+        self.svs = svs if on_device else torch.from_numpy(host).to(device)
+        self.volume_shape = tuple(int(d) for d in host.shape)
+        self.n_rows = int(n_rows)
+        list_ptr, list_vox = supervoxel_voxel_lists(host, self.n_rows)
+        self.list_ptr = torch.from_numpy(list_ptr).to(device)
+        # never empty, so the pointer handed to the kernel is valid
+        self.list_vox = torch.from_numpy(list_vox).to(device) if list_vox.size else \
+            torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def _crop_operands(img, svs, table, bg_row, box, what):
+    """The operand checks of crop_concat (K16 keeps its own copy: it is left as it was), for J1; returns
+    (img, svs, table, bg_row, ci, ct), contiguous."""
+    _f32(img, table, bg_row)
+    if svs.dtype != torch.int16 or tuple(svs.shape) != box.volume_shape:
+        raise _lib.GtsError("partitioning must be int16 with the crop box's volume shape")
+    ci = 0
+    if img is not None:
+        if img.dim() != 4 or tuple(img.shape[:3]) != box.volume_shape:
+            raise _lib.GtsError("image must be [X, Y, Z, C] over the same volume")
+        img, ci = img.contiguous(), img.shape[3]
+    if table.dim() != 2:
+        raise _lib.GtsError(f"{what}: table must be [N, C], got {tuple(table.shape)}")
+    svs, table, bg_row = svs.contiguous(), table.contiguous(), bg_row.contiguous()
+    require_device(svs, table, bg_row, img, *box.dev)
+    ct = table.shape[1]
+    if bg_row.numel() != ct:
+        raise _lib.GtsError("background row does not match table rows")
+    return img, svs, table, bg_row, ci, ct
+
+
+def crop_concat_rows(img, svs, table, bg_row, box):
+    """J1.  [cx, cy, cz, Ci + Ct] fp32 = cat([img, table_plus_bg[svs]], -1)[box], channels-last (what
+    gts.conv3d reads); the same values as crop_concat(...)[0].movedim(0, -1).  Operands as crop_concat."""
+    img, svs, table, bg_row, ci, ct = _crop_operands(img, svs, table, bg_row, box, "crop_concat_rows")
+    cx, cy, cz = box.shape
+    out = torch.empty((cx, cy, cz, ci + ct), dtype=torch.float32, device=svs.device)
+    if out.numel():
+        check(_lib.load().gts_crop_concat_rows_f32(ptr(img), ptr(svs), ptr(table), ptr(bg_row), ptr(box.dev[0]),
+                                                   ptr(box.dev[1]), ptr(box.dev[2]), ptr(out), cx, cy, cz,
+                                                   box.volume_shape[1], box.volume_shape[2], table.shape[0], ci, ct,
+                                                   current_stream()), "gts_crop_concat_rows_f32")
+    return out
+
+
+def crop_concat_rows_bwd(dx, lists, box, img_channels=0):
+    """J2, the adjoint of crop_concat_rows with respect to `table`: d_table [N, Ct] from dx [V, Ci + Ct] (or
+    [cx, cy, cz, Ci + Ct]) over the crop, Ci = img_channels (0 when dx holds the table's columns only).
+    `lists`: the SupervoxelLists of the partitioning for N rows.  Deterministic (fixed-order sums)."""
+    _f32(dx)
+    cx, cy, cz = box.shape
+    v = cx * cy * cz
+    if dx.dim() == 4 and tuple(dx.shape[:3]) == box.shape:
+        dx = dx.reshape(v, -1)
+    if dx.dim() != 2 or dx.shape[0] != v or dx.shape[1] <= img_channels or img_channels < 0:
+        raise _lib.GtsError(f"crop_concat_rows_bwd: expected dx [{v}, > {img_channels}], got {tuple(dx.shape)}")
+    if not isinstance(lists, SupervoxelLists) or lists.volume_shape != box.volume_shape:
+        raise _lib.GtsError("crop_concat_rows_bwd: the voxel lists belong to another volume")
+    dx = dx.contiguous()
+    inv = box.inverse_dev()
+    require_device(dx, lists.list_ptr, lists.list_vox, *inv)
+    ct = dx.shape[1] - img_channels
+    out = torch.empty((lists.n_rows, ct), dtype=torch.float32, device=dx.device)
+    if out.numel():
+        dim_x, dim_y, dim_z = box.volume_shape
+        check(_lib.load().gts_crop_concat_rows_bwd_f32(ptr(dx), ptr(lists.list_ptr), ptr(lists.list_vox), ptr(inv[0]),
+                                                       ptr(inv[1]), ptr(inv[2]), ptr(out), cx, cy, cz, dim_x, dim_y,
+                                                       dim_z, lists.n_rows, img_channels, ct, current_stream()),
+              "gts_crop_concat_rows_bwd_f32")
+    return out
 
 
 def crop_concat(img, svs, table, bg_row, box):

@@ -258,6 +258,30 @@ int32_t gts_argmax_scatter_i16(const float* scores, const int16_t* relabel, cons
                                const int32_t* ys, const int32_t* zs, int16_t* out, int64_t cx,
                                int64_t cy, int64_t cz, int64_t dim_y, int64_t dim_z,
                                int64_t n_classes, void* stream);
+/* J1 crop_concat_rows: crop_concat in channels-last, the layout gts_conv3d_* read (joint GNN + CNN
+ * training, no counterpart in the reference: scripts/train_refinement_cnn.py:21-22 declines to build it):
+ *   out[t, :] (fp32, [cx * cy * cz, img_channels + row_channels]) = [img[v, :], table_plus_bg[svs[v]]]
+ *   for crop voxel t = (i * cy + j) * cz + k with source voxel v = (xs[i], ys[j], zs[k]).  Same id rules
+ *   and limits as crop_concat; exact copies (bit-equal to crop_concat's output moved to channels-last). */
+int32_t gts_crop_concat_rows_f32(const float* img, const int16_t* svs, const float* table,
+                                 const float* bg_row, const int32_t* xs, const int32_t* ys,
+                                 const int32_t* zs, float* out, int64_t cx, int64_t cy, int64_t cz,
+                                 int64_t dim_y, int64_t dim_z, int64_t n_rows, int64_t img_channels,
+                                 int64_t row_channels, void* stream);
+/* J2 crop_concat_rows_bwd: the adjoint of J1 with respect to `table`:
+ *   d_table[n, c] = sum over the crop voxels t whose source voxel took table row n of
+ *                   dx[t, img_channels + c],   dx [cx * cy * cz, img_channels + row_channels].
+ * Voxels that took the background row contribute to nothing; rows without a voxel in the box get 0.0.
+ * list_ptr [n_rows + 1], list_vox: per table row the linear indices (x * dim_y + y) * dim_z + z of the
+ * voxels that resolve to it (numpy's wrap of negative ids included), ascending; inv_x [dim_x], inv_y
+ * [dim_y], inv_z [dim_z]: plane index -> index inside the crop, or -1 for a plane outside it (all int32,
+ * on the device).  The list does not depend on the box.  Entries outside the volume or the box are
+ * skipped.  Every sum is formed in a fixed order (no float atomics): two calls give identical bits. */
+int32_t gts_crop_concat_rows_bwd_f32(const float* dx, const int32_t* list_ptr, const int32_t* list_vox,
+                                     const int32_t* inv_x, const int32_t* inv_y, const int32_t* inv_z,
+                                     float* d_table, int64_t cx, int64_t cy, int64_t cz, int64_t dim_x,
+                                     int64_t dim_y, int64_t dim_z, int64_t n_rows, int64_t img_channels,
+                                     int64_t row_channels, void* stream);
 
 /* ---- K14: AdamW step over one flat fp32 buffer ---------------------------------------------
  * torch.optim.AdamW(net.parameters(), lr, weight_decay).step() (model/gnn_model.py:28,46), same
