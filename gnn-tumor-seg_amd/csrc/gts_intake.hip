@@ -14,49 +14,17 @@
 //       not a box): a 4-pass radix select on the order-preserving uint32 key, 8 bits per pass, with
 //       LDS-privatised histograms merged into the workspace per pass and a one-block step that walks
 //       the 256 bins; the two ranks are followed separately (they may fall into different buckets)
-//       and share one histogram while their prefixes agree;
+//       and share one histogram while their prefixes agree (the select lives in gts_select.h, shared
+//       with D2 of gts_dataset_stats.hip, which names its elements by a bit mask instead);
 //   I3  fused gather + ((x / top_c) - mean_c) / std_c in IEEE float32 (-ffp-contract=off, correctly
 //       rounded division) into C-order [cx, cy, cz, 4]: a 64 (x) x 16 (z) tile per workgroup is read
 //       along x into LDS and written along z with one 16-byte store per voxel.
-#include "gts_common.h"
+#include "gts_select.h"
 
 namespace gts {
 namespace {
 
-constexpr int kChannels = 4;
-constexpr int kMaxExtent = 4096;   // LDS flag arrays of I1
-constexpr int kMaxBlocks = 2048;
-constexpr int kBins = 256;
-constexpr int kHist = kChannels * 2 * kBins;   // [channel][rank][bin]
 constexpr int kTileX = 64, kTileZ = 16;
-constexpr int32_t kI16 = 4, kF32 = 16;       // NIfTI datatype codes
-
-struct SelectState {
-  unsigned prefix[kChannels][2];
-  unsigned long long rank[kChannels][2];   // rank still to skip inside the current prefix
-};
-
-struct Layout {
-  int64_t hist, state, total;
-};
-constexpr Layout kLayout = {0, kHist * 4, kHist * 4 + 256};
-
-// Order-preserving key of a float32; -0.0 is mapped to +0.0 first, so that the two zeros form one
-// value (np.partition does not order them; a rank that lands on zeros returns +0.0).
-__device__ __forceinline__ unsigned float_key(float v) {
-  unsigned b = __float_as_uint(v);
-  if (b == 0x80000000u) b = 0;
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ float key_float(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
-template <typename T>
-__device__ __forceinline__ float load_f32(const T* __restrict__ p, size_t i) {
-  return static_cast<float>(p[i]);
-}
 
 // I1.
 template <typename T>
@@ -104,100 +72,6 @@ __global__ __launch_bounds__(kBlock) void intake_occupancy_kernel(const T* __res
   if (threadIdx.x == 0 && bad) atomicAdd(nonfinite, static_cast<unsigned long long>(bad));
 }
 
-// Voxel offset of cropped element (xi, yi, zi); an index outside the volume reads voxel 0 instead of
-// leaving the buffer (the host builds the lists from I1's flags, so this never happens there).
-__device__ __forceinline__ unsigned crop_offset(const int32_t* __restrict__ xs, const int32_t* __restrict__ ys,
-                                                const int32_t* __restrict__ zs, unsigned xi, unsigned yi, unsigned zi,
-                                                int X, int Y, int Z) {
-  const unsigned x = static_cast<unsigned>(xs[xi]), y = static_cast<unsigned>(ys[yi]),
-                 z = static_cast<unsigned>(zs[zi]);
-  if (x >= unsigned(X) || y >= unsigned(Y) || z >= unsigned(Z)) return 0;
-  return (z * Y + y) * X + x;
-}
-
-__global__ void intake_select_init_kernel(unsigned* __restrict__ hist, SelectState* __restrict__ st,
-                                          unsigned long long rank_lo, unsigned long long rank_hi) {
-  for (int i = threadIdx.x; i < kHist; i += blockDim.x) hist[i] = 0;
-  if (threadIdx.x < 2 * kChannels) {
-    const int c = threadIdx.x >> 1, r = threadIdx.x & 1;
-    st->prefix[c][r] = 0;
-    st->rank[c][r] = r ? rank_hi : rank_lo;
-  }
-}
-
-// I2, one pass: histogram of digit (key >> shift) & 255 over the elements whose higher digits equal
-// the rank's prefix.
-template <typename T>
-__global__ __launch_bounds__(kBlock) void intake_hist_kernel(const T* __restrict__ src, int X, int Y, int Z,
-                                                             const int32_t* __restrict__ xs, int cx,
-                                                             const int32_t* __restrict__ ys, int cy,
-                                                             const int32_t* __restrict__ zs,
-                                                             unsigned n, const SelectState* __restrict__ st,
-                                                             unsigned* __restrict__ hist, int shift) {
-  __shared__ unsigned h[kHist];
-  for (int i = threadIdx.x; i < kHist; i += kBlock) h[i] = 0;
-  const unsigned hi_mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
-  unsigned p0[kChannels], p1[kChannels];
-  bool both[kChannels];
-#pragma unroll
-  for (int c = 0; c < kChannels; ++c) {
-    p0[c] = st->prefix[c][0];
-    p1[c] = st->prefix[c][1];
-    both[c] = p0[c] != p1[c];
-  }
-  __syncthreads();
-  const size_t vol = static_cast<size_t>(X) * Y * Z;
-  for (unsigned e = blockIdx.x * kBlock + threadIdx.x; e < n; e += gridDim.x * kBlock) {
-    const unsigned xi = e % cx, r = e / cx;
-    const unsigned off = crop_offset(xs, ys, zs, xi, r % cy, r / cy, X, Y, Z);
-#pragma unroll
-    for (int c = 0; c < kChannels; ++c) {
-      const unsigned key = float_key(load_f32(src, c * vol + off));
-      const unsigned d = (key >> shift) & (kBins - 1);
-      if (((key ^ p0[c]) & hi_mask) == 0) atomicAdd(&h[(2 * c) * kBins + d], 1u);
-      if (both[c] && ((key ^ p1[c]) & hi_mask) == 0) atomicAdd(&h[(2 * c + 1) * kBins + d], 1u);
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < kHist; i += kBlock)
-    if (h[i]) atomicAdd(&hist[i], h[i]);
-}
-
-// I2, one step: each (channel, rank) walks its histogram to the bin that holds its rank, appends the
-// digit to its prefix, and the histogram is cleared for the next pass.  After the last pass the
-// prefix is the key of the order statistic.
-__global__ __launch_bounds__(kBlock) void intake_select_step_kernel(unsigned* __restrict__ hist,
-                                                                    SelectState* __restrict__ st, int shift,
-                                                                    float* __restrict__ out) {
-  const int t = threadIdx.x;
-  unsigned prefix = 0, digit = kBins - 1;
-  unsigned long long k = 0;
-  if (t < 2 * kChannels) {
-    const int c = t >> 1, r = t & 1;
-    const bool shared_hist = st->prefix[c][0] == st->prefix[c][1];
-    const unsigned* h = hist + (2 * c + (shared_hist ? 0 : r)) * kBins;
-    prefix = st->prefix[c][r];
-    k = st->rank[c][r];
-    unsigned long long acc = 0;
-    for (int b = 0; b < kBins; ++b) {
-      if (k < acc + h[b]) {
-        digit = b;
-        break;
-      }
-      acc += h[b];
-    }
-    k -= acc;
-    prefix |= digit << shift;
-  }
-  __syncthreads();  // every walk has read the prefixes and the histograms
-  if (t < 2 * kChannels) {
-    st->prefix[t >> 1][t & 1] = prefix;
-    st->rank[t >> 1][t & 1] = k;
-    if (out) out[t] = key_float(prefix);
-  }
-  for (int i = t; i < kHist; i += kBlock) hist[i] = 0;
-}
-
 struct StandardizeParams {
   float top[kChannels], mean[kChannels], std[kChannels];
 };
@@ -241,18 +115,8 @@ __global__ __launch_bounds__(kBlock) void intake_standardize_kernel(const T* __r
   }
 }
 
-inline bool volume_ok(int64_t X, int64_t Y, int64_t Z) {
-  return X >= 1 && Y >= 1 && Z >= 1 && X <= kMaxExtent && Y <= kMaxExtent && Z <= kMaxExtent &&
-         X * Y * Z < (int64_t{1} << 31);
-}
-
 inline bool crop_ok(int64_t X, int64_t Y, int64_t Z, int64_t cx, int64_t cy, int64_t cz) {
   return cx >= 1 && cy >= 1 && cz >= 1 && cx <= X && cy <= Y && cz <= Z;
-}
-
-inline int grid_for(int64_t n) {
-  const int64_t b = (n + kBlock - 1) / kBlock;
-  return static_cast<int>(b < kMaxBlocks ? b : kMaxBlocks);
 }
 
 }  // namespace
@@ -294,24 +158,13 @@ extern "C" int32_t gts_intake_order_stats(const void* src, int32_t dtype, int64_
   if (rank_lo < 0 || rank_hi < rank_lo || rank_hi >= n) return GTS_ERR_SHAPE;
   if (dtype != kI16 && dtype != kF32) return GTS_ERR_ARGKIND;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  char* ws = static_cast<char*>(workspace);
-  unsigned* hist = reinterpret_cast<unsigned*>(ws + kLayout.hist);
-  SelectState* state = reinterpret_cast<SelectState*>(ws + kLayout.state);
-  const int x = static_cast<int>(X), y = static_cast<int>(Y), z = static_cast<int>(Z);
-  const int grid = grid_for(n);
-  intake_select_init_kernel<<<1, kBlock, 0, st>>>(hist, state, static_cast<unsigned long long>(rank_lo),
-                                                  static_cast<unsigned long long>(rank_hi));
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    if (dtype == kI16)
-      intake_hist_kernel<int16_t><<<grid, kBlock, 0, st>>>(static_cast<const int16_t*>(src), x, y, z, xs,
-                                                           static_cast<int>(cx), ys, static_cast<int>(cy), zs,
-                                                           static_cast<unsigned>(n), state, hist, shift);
-    else
-      intake_hist_kernel<float><<<grid, kBlock, 0, st>>>(static_cast<const float*>(src), x, y, z, xs,
-                                                         static_cast<int>(cx), ys, static_cast<int>(cy), zs,
-                                                         static_cast<unsigned>(n), state, hist, shift);
-    intake_select_step_kernel<<<1, kBlock, 0, st>>>(hist, state, shift, shift == 0 ? out : nullptr);
-  }
+  const CropSource source{xs, ys, zs, static_cast<int>(cx), static_cast<int>(cy), static_cast<int>(X),
+                          static_cast<int>(Y), static_cast<int>(Z)};
+  const size_t vol = static_cast<size_t>(X * Y * Z);
+  if (dtype == kI16)
+    run_select(static_cast<const int16_t*>(src), vol, source, n, rank_lo, rank_hi, out, workspace, st);
+  else
+    run_select(static_cast<const float*>(src), vol, source, n, rank_lo, rank_hi, out, workspace, st);
   return launch_status();
 }
 

@@ -12,6 +12,11 @@ small thread pool meanwhile.  A scan that raises is reported and left out; the e
 when any scan was left out.
 
     python -m scripts.preprocess_dataset -d RAW_DIR -l _seg.nii.gz -o OUT_DIR
+
+Standardization uses the reference's BraTS-2021 constants unless --stats is given: --stats STATS.json takes
+the values of a file written by scripts.compute_dataset_stats; --stats compute takes them first over the
+input folder (needs -l), as the reference does when its constant is None, and writes
+OUT_DIR/standardization.json.
 """
 import argparse
 import glob
@@ -26,7 +31,7 @@ if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
 import Filepaths  # noqa: E402
-from data_processing import graph_io, nifti_io  # noqa: E402
+from data_processing import graph_io, nifti_io, standardization  # noqa: E402
 from data_processing.data_loader import save_crop  # noqa: E402
 from data_processing.image_processing import determine_brain_crop, normalize_img, standardize_img  # noqa: E402
 from data_processing.labels import LABEL_MAP, swap_labels_from_brats  # noqa: E402,F401
@@ -57,6 +62,9 @@ def build_parser():
     parser.add_argument("-l", "--label_extension", default=None,
                         help="file suffix of the label volume; without it no labels are read or written")
     parser.add_argument("-p", "--data_prefix", default="", help="common prefix of the scan folders, e.g. BraTS2021")
+    parser.add_argument("--stats", default=None, metavar="STATS.json|compute",
+                        help="standardization statistics: a file of scripts.compute_dataset_stats, or 'compute' to take "
+                             "them over the input folder first (default: the BraTS-2021 constants)")
     return parser
 
 
@@ -80,8 +88,23 @@ class DataPreprocessor:
         self.output_dir = os.path.expanduser(args.output_dir or default_output_dir(args))
         self.scans = find_scans(args.data_dir or Filepaths.INPUT_MRI_DIR, args.data_prefix)
         self.all_ids = sorted(self.scans)
-        self.mean, self.std = (np.array(s, dtype=np.float32) for s in STANDARDIZATION_STATS)
+        self.stats_failed = []
+        self.mean, self.std = self.standardization_stats(getattr(args, "stats", None))
         print(f"{len(self.all_ids)} scan folders found; graphs go to {self.output_dir}")
+
+    def standardization_stats(self, stats):
+        """(mean, std) float32: the constants, a statistics file's values, or ('compute') the input folder's own."""
+        if not stats:
+            return tuple(np.array(s, dtype=np.float32) for s in STANDARDIZATION_STATS)
+        if stats != "compute":
+            return standardization.load_stats(os.path.expanduser(stats), self.args.modality_extensions)
+        from scripts import compute_dataset_stats
+
+        path = os.path.join(self.output_dir, standardization.FILE_NAME)
+        mean, std, self.stats_failed = compute_dataset_stats.compute_and_save(
+            self.scans, self.args.modality_extensions, self.args.label_extension, path)
+        print(f"standardization statistics over {len(self.scans) - len(self.stats_failed)} scan(s) written to {path}")
+        return standardization.load_stats(path, self.args.modality_extensions)
 
     def load(self, scan_id):
         """Host stage: decode, crop, relabel, normalize, standardize."""
@@ -136,9 +159,14 @@ class DataPreprocessor:
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    failed = DataPreprocessor(args).run()
+    try:
+        gen = DataPreprocessor(args)
+    except standardization.StatsError as exc:   # a statistics file that does not fit this run, or none could be computed
+        print(f"preprocess_dataset: {exc}", file=sys.stderr)
+        return 2
+    failed = gen.run()
     print(f"preprocessing finished, {len(failed)} scan(s) skipped")
-    return 1 if failed else 0
+    return 1 if failed or gen.stats_failed else 0
 
 
 if __name__ == "__main__":

@@ -14,6 +14,10 @@ name without the suffix), or a folder of scan folders (found as preprocess_datas
 A scan that raises is reported and skipped; the exit status is 1 when any scan was skipped.
 
     python -m scripts.segment_scans -d INPUT -o OUT -g GNN.pt [-c CNN.pt] [-m GSpool] [-n 15000 -b 0.5 -k 10]
+
+--stats STATS.json standardizes with the values of a file written by scripts.compute_dataset_stats (the one the
+dataset the weights were trained on was preprocessed with) instead of the BraTS-2021 constants.  Explicit
+only: a standardization.json that happens to lie next to the weights is not picked up.
 """
 import argparse
 import os
@@ -27,7 +31,7 @@ _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
-from data_processing import nifti_io  # noqa: E402
+from data_processing import nifti_io, standardization  # noqa: E402
 from data_processing.image_processing import uncrop_to_brats_size  # noqa: E402
 from data_processing.labels import INTERNAL_TO_BRATS  # noqa: E402
 from gts import graphgen, intake, ops  # noqa: E402
@@ -54,6 +58,9 @@ def build_parser():
     parser.add_argument("-M", "--modality_extensions", nargs="+", default=list(prep.BRATS_MODALITIES),
                         help="file suffix of each modality, in channel order")
     parser.add_argument("-p", "--data_prefix", default="", help="common prefix of the scan folders, e.g. BraTS2021")
+    parser.add_argument("--stats", default=None, metavar="STATS.json",
+                        help="standardization statistics file of scripts.compute_dataset_stats "
+                             "(default: the BraTS-2021 constants)")
     return parser
 
 
@@ -83,7 +90,10 @@ class Segmenter:
         self.args = args
         self.device = _device()
         self.k = args.num_neighbors or 0
-        self.mean, self.std = (np.array(s, dtype=np.float32) for s in prep.STANDARDIZATION_STATS)
+        if getattr(args, "stats", None):
+            self.mean, self.std = standardization.load_stats(os.path.expanduser(args.stats), args.modality_extensions)
+        else:
+            self.mean, self.std = (np.array(s, dtype=np.float32) for s in prep.STANDARDIZATION_STATS)
         gnn = os.path.expanduser(args.gnn_weights)
         if args.cnn_weights:
             from scripts.generate_joint_predictions import load_nets
@@ -158,7 +168,12 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     scans = find_inputs(args.data_dir, args.modality_extensions, args.data_prefix)
     print(f"{len(scans)} scan(s) found; segmentations go to {args.output_dir}")
-    failed = Segmenter(args).run(scans, os.path.expanduser(args.output_dir))
+    try:
+        segmenter = Segmenter(args)
+    except standardization.StatsError as exc:   # a statistics file that does not fit this run
+        print(f"segment_scans: {exc}", file=sys.stderr)
+        return 2
+    failed = segmenter.run(scans, os.path.expanduser(args.output_dir))
     print(f"segmentation finished, {len(failed)} scan(s) skipped")
     return 1 if failed else 0
 

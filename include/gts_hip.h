@@ -699,6 +699,34 @@ int32_t gts_intake_standardize(const void* src, int32_t dtype, int64_t X, int64_
                                int64_t cx, const int32_t* ys, int64_t cy, const int32_t* zs, int64_t cz,
                                const float* params, float* out, void* stream);
 
+/* ---- D1-D3: per-scan standardization statistics ---------------------------------------------------------
+ * One scan's share of DataPreprocessor.compute_dataset_stats (scripts/preprocess_dataset.py:93-115), with the
+ * normalization of normalize_img(..., is_flat=True) (data_processing/image_processing.py:45-51), on the device:
+ *   healthy = (img[..., 0] > 0.001) & (lab == 0); y = img[healthy] / q995; mean(y, 0), std(y, 0).
+ * src, dtype and the extent limits: as for I1-I3, the WHOLE volume (nothing is cropped).  labels: int16
+ * [Z][Y][X] in raw BraTS coding.  member(v) = float32(src[0][v]) > float32(0.001) && labels[v] == 0.
+ * workspace: gts_dataset_stats_workspace(X, Y, Z) bytes (GTS_ERR_SHAPE for a rejected shape); the three calls
+ * of one scan share it: D1 leaves the member bit mask there for D2 and D3.  A workspace that is too small:
+ * GTS_ERR_SHAPE.  Nothing is launched for a rejected argument.
+ * gts_dataset_stats_mask (D1): counts (device uint64 [2], cleared by the call) = the number of members n and
+ * the number of members with a non-finite value in some channel.
+ * gts_dataset_stats_order_stats (D2): out (device float32 [4][2]) = the values at ranks rank_lo and rank_hi
+ * (0 <= rank_lo <= rank_hi < n, n = D1's count) of each channel's member values in ascending order; I2's radix
+ * select and its rule for -0.0.
+ * gts_dataset_stats_moments (D3): top = HOST float32 [4], copied at launch.  out (device float64 [4][4]): the
+ * sum of y_c = float32(v) / top_c (IEEE float32 division) over the members, the sum of y_c^2, the mean and
+ * the standard deviation sqrt(sum y^2 / n - mean^2), accumulated in float64 in a fixed order: the same bits
+ * on every run, whatever grid the launcher picks. */
+int64_t gts_dataset_stats_workspace(int64_t X, int64_t Y, int64_t Z);
+int32_t gts_dataset_stats_mask(const void* src, int32_t dtype, const int16_t* labels, int64_t X, int64_t Y, int64_t Z,
+                               uint64_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+int32_t gts_dataset_stats_order_stats(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, int64_t n,
+                                      int64_t rank_lo, int64_t rank_hi, float* out, void* workspace,
+                                      int64_t workspace_bytes, void* stream);
+int32_t gts_dataset_stats_moments(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, int64_t n,
+                                  const float* top, double* out, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
