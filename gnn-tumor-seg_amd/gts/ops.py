@@ -388,11 +388,24 @@ def _reduce_ws(n, cols, device):
 
 def gat_act_bwd(gout, out, activation, want_bias_grad):
     """(g_pre, g_bias): g_pre = gout * act'(out) (activation 1 = ELU, 2 = ReLU, through the output; 0 = none),
-    g_bias = g_pre.sum(0)."""
-    gout = gout.contiguous()
+    g_bias = g_pre.sum(0).  gout [N, ...] with N > 0 and a row of 4k floats; `out` (same shape) is read only when there is
+    an activation.  Strided operands are copied; with activation 0 and a contiguous gout, g_pre IS gout."""
+    if activation not in (0, 1, 2):
+        raise _lib.GtsError(f"gat_act_bwd: activation must be 0 (none), 1 (ELU) or 2 (ReLU), got {activation!r}")
+    if gout.dim() < 1 or gout.shape[0] == 0:
+        raise _lib.GtsError(f"gat_act_bwd: gout must be [N, ...] with N > 0, got {tuple(gout.shape)}")
+    if not activation:
+        out = None                       # never read
+    elif out is None:
+        raise _lib.GtsError("gat_act_bwd: the activation's output is needed to differentiate through it")
     n, cols = gout.shape[0], gout[0].numel()
-    if activation:
-        _expect(out, gout.shape, "out")
+    if cols == 0 or cols % 4:
+        raise _lib.GtsError(f"gat_act_bwd needs a row width that is a multiple of 4, got {cols}")
+    _expect(out, gout.shape, "out")
+    _f32(gout, out)
+    gout = gout.contiguous()
+    out = out.contiguous() if out is not None else None
+    require_device(gout, out)
     g_pre = torch.empty_like(gout) if activation else gout
     g_bias = torch.empty(cols, dtype=torch.float32, device=gout.device) if want_bias_grad else None
     ws = _reduce_ws(n, cols, gout.device) if want_bias_grad else None
@@ -403,10 +416,19 @@ def gat_act_bwd(gout, out, activation, want_bias_grad):
 
 
 def gat_param_grad(ft, gel, ger):
-    """(g_attn_l, g_attn_r) [H,D] = sum_n gel[n,h] ft[n,h,:], sum_n ger[n,h] ft[n,h,:]."""
+    """(g_attn_l, g_attn_r) [H,D] = sum_n gel[n,h] ft[n,h,:], sum_n ger[n,h] ft[n,h,:].  ft [N,H,D] with N > 0 and
+    D % 4 == 0, gel / ger [N,H]; strided operands are copied."""
+    if ft.dim() != 3:
+        raise _lib.GtsError(f"ft must be [N, H, D], got {tuple(ft.shape)}")
     n, h, dim = ft.shape
     _expect(gel, (n, h), "gel")
     _expect(ger, (n, h), "ger")
+    if n == 0 or h == 0 or dim == 0 or dim % 4:
+        raise _lib.GtsError(f"gat_param_grad needs N > 0, H > 0 and a head width that is a multiple of 4, "
+                            f"got {tuple(ft.shape)}")
+    _f32(ft, gel, ger)
+    ft, gel, ger = ft.contiguous(), gel.contiguous(), ger.contiguous()
+    require_device(ft, gel, ger)
     gl = torch.empty((h, dim), dtype=torch.float32, device=ft.device)
     gr = torch.empty_like(gl)
     ws = _reduce_ws(n, h * dim, ft.device)

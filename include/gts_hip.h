@@ -154,8 +154,11 @@ int32_t gts_gat_scores_f32(const float* ft, const float* attn_l, const float* at
  *      gradient of the score dot products), gel[u,h] = sum_e ge[pos(e)].
  *      t_pos[e] = absolute in-CSR position of out-edge e.
  *  (3) gts_gat_param_grad_f32: g_attn_l[h,:] = sum_n gel[n,h] ft[n,h,:], g_attn_r with ger.
- * (0) and (3) reduce over the node axis through `workspace`
- * (>= gts_gat_reduce_workspace(n, H*D) bytes) in a fixed order. */
+ * (0) and (3) reduce over the node axis through `workspace` in a fixed order (bitwise reproducible): per-chunk column
+ * sums of ceil(n / 512) rows each, then added 16 chunks abreast.  gts_gat_reduce_workspace(n, H*D) is the size of TWO
+ * such arrays of chunk sums (0 for n <= 0 or a width that is not a multiple of 4): (3) needs all of it, (0) needs half
+ * of it and only when g_bias is asked for.  A smaller workspace is refused before anything is launched.
+ * In (0) g_pre may be gout itself (each element is read, then written, by one thread). */
 int32_t gts_gat_bwd_edge_f32(const int32_t* indptr, const int32_t* indices, const float* ft,
                              const float* el, const float* er, const float* attn,
                              const float* gout, float negative_slope, float* ge, float* ger,
