@@ -11,12 +11,11 @@
 #include <algorithm>
 #include <vector>
 
-#include "gts_common.h"
+#include "gts_gemm_args.h"
 
 namespace {
 
 constexpr int kMaxLayers = 64;
-constexpr int kMaxWgradProblems = 32;   // kMaxProblems of gts_gemm.hip
 constexpr int kFlagChain = 1, kFlagReluBits = 2, kFlagTransposedIgrad = 4;
 
 inline int64_t align256(int64_t bytes) { return (bytes + 255) & ~255LL; }
@@ -125,8 +124,8 @@ inline BwdPlan plan_backward(int64_t n, const int64_t* w, int n_layers, int flag
   int64_t ws = 0;
   if (n > 0)
     for (const auto& gk : groups)
-      for (int first = 0; first < gk.count; first += kMaxWgradProblems)
-        ws = std::max(ws, gts_linear_bwd_weight_workspace(n, gk.n, gk.k, std::min(kMaxWgradProblems, gk.count - first)));
+      for (int first = 0; first < gk.count; first += gts::kMaxProblems)
+        ws = std::max(ws, gts_linear_bwd_weight_workspace(n, gk.n, gk.k, std::min(gts::kMaxProblems, gk.count - first)));
   p.workspace_bytes = ws;
   p.workspace = take(ws);
   p.counters = take(4 * GTS_CLUSTER_COUNTER_WORDS);
@@ -382,8 +381,8 @@ extern "C" int32_t gts_sage_pool_stack_bwd_f32(const int32_t* t_indptr, const in
   }
   for (const auto& grp : groups) {
     const int count = static_cast<int>(grp.g.size());
-    for (int first = 0; first < count; first += kMaxWgradProblems) {
-      const int q = std::min(kMaxWgradProblems, count - first);
+    for (int first = 0; first < count; first += gts::kMaxProblems) {
+      const int q = std::min(gts::kMaxProblems, count - first);
       GTS_TRY(gts_linear_bwd_weight_f32(grp.g.data() + first, grp.a.data() + first, grp.gw.data() + first,
                                         grp.gb.data() + first, q, f32(plan.workspace), plan.workspace_bytes, n_rows, grp.n,
                                         grp.k, stream));

@@ -41,7 +41,7 @@ __global__ __launch_bounds__(kBlock) void transpose_batch_kernel(const Transpose
   }
 }
 
-// Weights in FRAGMENT ORDER for the panel GEMMs (csrc/gts_gemm.hip): B [n, k] (the operand whose rows are output columns
+// Weights in FRAGMENT ORDER for the panel GEMMs (csrc/gts_gemm_panel.h): B [n, k] (the operand whose rows are output columns
 // and whose columns are the reduction) is cut into 16-row tiles and reduction groups of 16; the 16 x 16 block of tile T,
 // group g is stored as the 64 x 4 floats the 64 lanes of a wave feed to four v_mfma_f32_16x16x4_f32:
 //     packed[((T * G + g) * 64 + lane) * 4 + e] = B[16 T + (lane & 15)][16 g + 4 (lane >> 4) + e]      (0 past the edges)

@@ -385,7 +385,7 @@ def linear_bwd_input_t_act(g0, w0t, act_out, activation, g1=None, w1t=None, want
     return gin, g_bias
 
 
-MAX_WGRAD_PROBLEMS = 32   # kMaxProblems of csrc/gts_gemm.hip
+MAX_WGRAD_PROBLEMS = 32   # kMaxProblems of csrc/gts_gemm_args.h
 
 
 def linear_bwd_weight_multi(problems):

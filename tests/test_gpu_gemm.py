@@ -383,7 +383,7 @@ def test_weights_in_fragment_order_are_the_layout_the_header_states(rows, cols, 
                                           (1000, 64, 64, 256, 256), (49999, 132, 0, 256, 64)])
 def test_gemms_reading_weights_in_fragment_order_give_the_same_bits(m, k0, k1, n, n2):
     """Forward pair, chained forward (mask bits written), transposed input gradient and its chained form with the
-    `packed` copies of their weights (csrc/gts_gemm.hip: a fragment load = 1 KiB of consecutive bytes) against the same
+    `packed` copies of their weights (csrc/gts_gemm_panel.h: a fragment load = 1 KiB of consecutive bytes) against the same
     calls on the weights as torch stores them: bit for bit — at the reference's batch shape (35 000 rows: 144-row
     panels), at C2's (60 000: 240-row panels), with reduction tails (20, 132) and at a size where other kernels run and
     the copies are ignored — and against fp64."""
@@ -502,3 +502,68 @@ def test_input_gradient_through_the_activation_of_the_layer_below(m, k, n0, n1, 
         assert torch.all((bias.double() - sums64).abs() <= 2e-6 * bound + 1e-30)
     only, none = dense.linear_bwd_input_t_act(g0, w0t, act_out, activation, g1, w1t, want_bias_grad=False)
     assert none is None and torch.equal(only, want)
+
+
+@pytest.mark.parametrize("option,variant", [(1, 1), (1, 3), (1, 5), (1, 8), (3, 1), (3, 3), (3, 5), (3, 8)])
+def test_every_tile_variant_forced_against_fp64(hip_lib, option, variant):
+    """Each 32x32x2 tile the library carries (128x256, 64x256, 256x128, double-buffered 256x256), forced through
+    GTS_OPT_GEMM_TILE (forward: out [257, 256] = a [257, 64] w^T) / GTS_OPT_IGRAD_TILE (input gradient on weights as
+    stored, the strided B operand: gin [257, 256] = g [257, 64] wi [64, 256]) at the smallest shape that reaches the
+    choice: more than 128 OUTPUT columns either way, two row tiles with a 1-row tail."""
+    m, k, n = 257, 64, 256
+    a, w, b = _rand(m, k, seed=31), _rand(n, k, seed=32), _rand(n, seed=33)
+    g, wi = _rand(m, k, seed=34), _rand(k, n, seed=35)
+    try:
+        assert hip_lib.gts_set_option(option, variant) == 0
+        if option == 1:
+            got = dense.linear_fwd(a.to(DEV), w.to(DEV), bias=b.to(DEV), relu=True)
+        else:
+            got = dense.linear_bwd_input(g.to(DEV), wi.to(DEV))
+            assert got.shape == (m, n)
+    finally:
+        hip_lib.gts_set_option(option, -1 if option == 1 else 1)
+    if option == 1:
+        _check(got, (a.double() @ w.double().t() + b.double()).clamp(min=0), a.double().abs() @ w.double().abs().t() + b.double().abs())
+    else:
+        _check(got, g.double() @ wi.double(), g.double().abs() @ wi.double().abs())
+
+
+@pytest.mark.parametrize("rows", [240, 192, 144])
+def test_every_panel_height_forced_plain_and_chained_against_fp64(hip_lib, rows):
+    """The direct-to-fragment panels at each height (GTS_OPT_PANEL_ROWS), as one GEMM and as the chained pair in one
+    launch, at m = 241: one full 240-row panel and a 1-row one (two ragged panels at 192 / 144)."""
+    m, k, n, n2 = 241, 64, 256, 256
+    a, w, b = _rand(m, k, seed=41), _rand(n, k, seed=42), _rand(n, seed=43)
+    w2, b2 = _rand(n2, n, seed=44), _rand(n2, seed=45)
+    try:
+        assert hip_lib.gts_set_option(13, rows) == 0 and hip_lib.gts_set_option(1, 10) == 0
+        plain = dense.linear_fwd(a.to(DEV), w.to(DEV), bias=b.to(DEV), relu=True)
+        out, out2 = dense.linear_fwd_chain(a.to(DEV), w.to(DEV), None, None, b.to(DEV), True, w2.to(DEV), b2.to(DEV), True)
+    finally:
+        hip_lib.gts_set_option(13, 0)
+        hip_lib.gts_set_option(1, -1)
+    ref = (a.double() @ w.double().t() + b.double()).clamp(min=0)
+    bound = a.double().abs() @ w.double().abs().t() + b.double().abs()
+    _check(plain, ref, bound)
+    assert torch.equal(out, plain)
+    ref2 = (out.cpu().double() @ w2.double().t() + b2.double()).clamp(min=0)
+    _check(out2, ref2, out.cpu().double().abs() @ w2.double().abs().t() + b2.double().abs())
+
+
+@pytest.mark.parametrize("variant", [1, 2, 4, 6])
+def test_every_weight_gradient_tile_forced_against_fp64(hip_lib, variant):
+    """GTS_OPT_WGRAD_TILE 1 / 2 / 4 / 6 (128x128, 128x256, 256x256 through LDS, 256x256 streamed) on two problems of
+    257 rows: nine reduction tiles with a 1-row tail, one bias gradient asked for."""
+    m, n, k = 257, 256, 256
+    gs = [_rand(m, n, seed=51 + q) for q in range(2)]
+    acts = [_rand(m, k, seed=53 + q) for q in range(2)]
+    try:
+        assert hip_lib.gts_set_option(2, variant) == 0
+        out = dense.linear_bwd_weight_multi([(g.to(DEV), a.to(DEV), q == 0) for q, (g, a) in enumerate(zip(gs, acts))])
+    finally:
+        hip_lib.gts_set_option(2, -1)
+    for q, ((gw, gb), g, a) in enumerate(zip(out, gs, acts)):
+        _check(gw, g.double().t() @ a.double(), g.double().abs().t() @ a.double().abs())
+        assert (gb is not None) == (q == 0)
+        if gb is not None:
+            _check(gb, g.double().sum(0), g.double().abs().sum(0))

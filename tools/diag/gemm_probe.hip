@@ -1,9 +1,10 @@
 // Diagnostic translation unit (never part of libgts_hip.so): the K11 kernels of
-// gnn-tumor-seg_amd/csrc/gts_gemm.hip instantiated with a probe that records, per workgroup and
+// gnn-tumor-seg_amd/csrc/gts_gemm_{tiles,panel,wgrad}.h instantiated with a probe that records, per workgroup and
 // phase (0 start, 1 operands staged, 2 main loop done, 3 tile stored), the constant 100 MHz
 // s_memrealtime counter and the shader-clock s_memtime counter (their ratio = in-kernel clock).
 // Built and driven by tools/diag/gemm_stamps.py.
-#include "../../gnn-tumor-seg_amd/csrc/gts_gemm.hip"
+#include "gts_gemm_panel.h"
+#include "gts_gemm_wgrad.h"   // brings gts_gemm_tiles.h
 #include "gemm_rejected_forms.inc"   // the kernel forms measured and rejected: built here, never shipped
 
 namespace gts {

@@ -1,5 +1,6 @@
 // Kernel forms measured and REJECTED, kept out of libgts_hip.so (round 4): tools/diag/gemm_probe.hip includes this file behind
-// gnn-tumor-seg_amd/csrc/gts_gemm.hip to time them again.  Last results: profiles/r02_tune_gemm.log, r02_tune_wgrad.log, r03_tune_wgrad.log.
+// the kernel headers of gnn-tumor-seg_amd/csrc to time them again; to bring one back, paste gemm_rows240_kernel / launch_rows240 into
+// gts_gemm_panel.h and the two wgrad_* kernels into gts_gemm_wgrad.h.  Last results: profiles/r02_tune_gemm.log, r02_tune_wgrad.log, r03_tune_wgrad.log.
 //   gemm_rows240_kernel   240-row panels staged through LDS (forward tile 9): 73.1 / 134.3 us where the direct-to-fragment panels take 70.4 / 129.8
 //   wgrad_direct_kernel   256 x 256 weight-gradient tile, operands straight into fragments (tile 5): 110 TF against 126
 //   wgrad_dma_kernel      the same tile with LDS-DMA copies (tile 7): the cycles of register staging; wgrad_stream_kernel replaced it
