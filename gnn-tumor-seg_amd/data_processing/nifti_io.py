@@ -60,7 +60,11 @@ def _quaternion_bcd(affine):
 
 
 def _open(fp, mode):
-    return gzip.open(fp, mode) if str(fp).endswith(".gz") else open(fp, mode)
+    if not str(fp).endswith(".gz"):
+        return open(fp, mode)
+    # no time stamp in the gzip header: the same volume gives the same bytes whenever it is written (two datasets built from
+    # the same scans are compared byte for byte, and a second's tick between the two writes must not tell them apart)
+    return gzip.GzipFile(fp, mode, mtime=0) if "w" in mode else gzip.open(fp, mode)
 
 
 def save_as_nifti(img, fp, affine=BRATS_AFFINE):

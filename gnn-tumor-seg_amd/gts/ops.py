@@ -205,7 +205,8 @@ def spmm_reduce(g, x, mode):
 
 # ---------------------------------------------------------------- autograd: GAT
 def _gat_fwd(g, ft, el, er, slope, bias=None, residual=None, activation=0):
-    d = g.dev()
+    """(out, attn).  Operands are refused on the host (shape, dtype, device) before the library is loaded; strided
+    operands are copied."""
     if ft.dim() != 3 or ft.shape[0] != g.n:
         raise _lib.GtsError(f"ft must be [graph nodes = {g.n}, H, D], got {tuple(ft.shape)}")
     n, h, dim = ft.shape
@@ -214,6 +215,14 @@ def _gat_fwd(g, ft, el, er, slope, bias=None, residual=None, activation=0):
     _expect(bias, (h * dim,), "bias")
     if residual is not None and (residual.shape[0] != n or residual.numel() != n * h * dim):
         raise _lib.GtsError(f"residual must hold [{n}, {h}*{dim}] values, got {tuple(residual.shape)}")
+    if activation not in (0, 1):
+        raise _lib.GtsError(f"_gat_fwd: activation must be 0 (none) or 1 (ELU), got {activation!r}")
+    _f32(ft, el, er, bias, residual)
+    ft, el, er = ft.contiguous(), el.contiguous(), er.contiguous()
+    bias = bias.contiguous() if bias is not None else None
+    residual = residual.contiguous() if residual is not None else None
+    require_device(ft, el, er, bias, residual)
+    d = g.dev()
     out = torch.empty_like(ft)
     attn = torch.empty((g.number_of_edges(), h), dtype=torch.float32, device=ft.device)
     lib = _lib.load()
@@ -260,8 +269,8 @@ def _gat_cluster_schedule(g, which, n, heads, dim):
 
 
 def _gat_bwd(g, ft, el, er, attn, gout, slope, attn_l=None, attn_r=None):
-    """(gft, gel, ger); with attn_l/attn_r the score-dot-product gradient is folded into gft."""
-    d = g.dev()
+    """(gft, gel, ger); with attn_l/attn_r the score-dot-product gradient is folded into gft.  Operands are refused on
+    the host (shape, dtype, device) before the library is loaded; strided operands are copied."""
     if ft.dim() != 3 or ft.shape[0] != g.n:
         raise _lib.GtsError(f"ft must be [graph nodes = {g.n}, H, D], got {tuple(ft.shape)}")
     n, h, dim = ft.shape
@@ -271,6 +280,14 @@ def _gat_bwd(g, ft, el, er, attn, gout, slope, attn_l=None, attn_r=None):
     _expect(gout, (n, h, dim), "gout")
     _expect(attn_l, (h, dim), "attn_l")
     _expect(attn_r, (h, dim), "attn_r")
+    if (attn_l is None) != (attn_r is None):
+        raise _lib.GtsError("_gat_bwd: attn_l and attn_r come together or not at all")
+    _f32(ft, el, er, attn, gout, attn_l, attn_r)
+    ft, el, er, attn, gout = ft.contiguous(), el.contiguous(), er.contiguous(), attn.contiguous(), gout.contiguous()
+    attn_l = attn_l.contiguous() if attn_l is not None else None
+    attn_r = attn_r.contiguous() if attn_r is not None else None
+    require_device(ft, el, er, attn, gout, attn_l, attn_r)
+    d = g.dev()
     lib = _lib.load()
     ge = torch.empty_like(attn)
     ger = torch.empty_like(er)

@@ -2,8 +2,9 @@
 
 Bars: bit-exact for max aggregation (+ its argmax), for the sum/mean/gcn reducers (the
 kernels accumulate in the oracle's slot order and divide like it) and for the voxel
-projection; rtol/atol 1e-5 for the GAT attention path (device expf is not bit-identical
-to the host's)."""
+projection; rtol/atol 1e-5 against the fp32 oracle for the GAT attention path on benign random
+graphs here (device expf is not bit-identical to the host's) — the float64 bounds of that path, at
+its degree, geometry and score edges, are in tests/test_gpu_gat_edges.py."""
 import os
 
 import numpy as np
