@@ -45,3 +45,22 @@ def write_sample(root, sample_id, seed, shape=BRATS_SHAPE, label_ext="_seg.nii.g
         save_as_nifti(img[..., m].astype(np.int16), os.path.join(folder, sample_id + ext))
     save_as_nifti(labels, os.path.join(folder, sample_id + label_ext))
     return folder
+
+
+def make_prediction(seed, shape=BRATS_SHAPE, n_blobs=3, salt=0.001):
+    """A predicted label volume as a supervoxel GNN leaves it, int16 in BraTS coding: `n_blobs` nested
+    tumour blobs (edema 2 around enhancing 4 around core 1) plus salt noise, a fraction `salt` of the
+    voxels set to a random tumour label (the lone false positives a connected-component filter removes)."""
+    rng = np.random.default_rng(seed)
+    axes = [np.linspace(-1.0, 1.0, n, dtype=np.float32) for n in shape]
+    labels = np.zeros(shape, dtype=np.int16)
+    for _ in range(n_blobs):
+        c = rng.uniform(-0.45, 0.45, 3).astype(np.float32)
+        s = rng.uniform(0.6, 1.4, 3).astype(np.float32)
+        d2 = (((axes[0] - c[0]) / s[0]) ** 2)[:, None, None] + (((axes[1] - c[1]) / s[1]) ** 2)[None, :, None] \
+            + (((axes[2] - c[2]) / s[2]) ** 2)[None, None, :]
+        for radius2, lab in ((0.045, 2), (0.02, 4), (0.006, 1)):
+            labels[d2 < radius2] = lab
+    noise = rng.random(shape, dtype=np.float32) < salt
+    labels[noise] = rng.choice(np.array([1, 2, 4], dtype=np.int16), size=int(noise.sum()))
+    return labels

@@ -17,6 +17,7 @@ from data_processing.labels import INTERNAL_TO_BRATS
 from gts import dist as gdist
 from gts import ops
 from model.networks import init_graph_net
+from scripts import cleanup as cleanup_flags
 from utils.hyperparam_helpers import DEFAULT_BACKGROUND_NODE_LOGITS, EvalParamSet
 
 output_dir = None
@@ -47,18 +48,24 @@ def save_voxel_logits(mri_id, dataset, node_logits):
                            f"{output_dir}{os.sep}{mri_id}_logits.nii.gz")
 
 
-def save_voxel_preds(mri_id, dataset, node_logits):
+def save_voxel_preds(mri_id, dataset, node_logits, cleanup=None):
     dev = node_logits.device
     svs = torch.from_numpy(dataset.get_supervoxel_partitioning(mri_id)).to(dev)
     relabel = torch.from_numpy(INTERNAL_TO_BRATS).to(dev)
-    voxels = ops.project_argmax(svs, node_logits.detach().float(), relabel).cpu().numpy()
-    full = uncrop_to_brats_size(dataset.get_crop(mri_id), voxels)
+    voxels = ops.project_argmax(svs, node_logits.detach().float(), relabel)
+    if cleanup is not None:
+        voxels = cleanup(voxels)                 # on the device, in BraTS coding, before the copy and the uncrop
+    full = uncrop_to_brats_size(dataset.get_crop(mri_id), voxels.cpu().numpy())
     nifti_io.save_as_nifti(full, f"{output_dir}{os.sep}{mri_id}.nii.gz")
+    if cleanup is not None:
+        print(f"{mri_id}: {cleanup.report()}")
 
 
-def save_predictions(net, dataset, save_format="logits"):
+def save_predictions(net, dataset, save_format="logits", cleanup=None):
     if save_format not in ("preds", "logits"):
         raise ValueError(f"Unrecognized save format {save_format}")
+    if cleanup is not None and save_format != "preds":
+        raise ValueError("the component clean-up works on label volumes: use it with -f preds")
     device = _device()
     net = net.to(device)
     # under torchrun the samples are dealt round-robin over the ranks; every rank writes its own volumes
@@ -68,7 +75,10 @@ def save_predictions(net, dataset, save_format="logits"):
         feats = torch.FloatTensor(feats).to(device)
         with torch.no_grad():
             logits = net(graph, feats)
-        (save_voxel_preds if save_format == "preds" else save_voxel_logits)(mri_id, dataset, logits)
+        if save_format == "preds":
+            save_voxel_preds(mri_id, dataset, logits, cleanup)
+        else:
+            save_voxel_logits(mri_id, dataset, logits)
 
 
 _FLAGS = (
@@ -80,12 +90,16 @@ _FLAGS = (
 )
 
 
-def main(argv=None):
-    global output_dir
+def build_parser():
     parser = argparse.ArgumentParser(description="GNN inference + node-to-voxel projection on MI355X")
     for short, long_name, default, text in _FLAGS:
         parser.add_argument(short, long_name, default=default, type=str, help=text)
-    args = parser.parse_args(argv)
+    return cleanup_flags.add_flags(parser)
+
+
+def main(argv=None):
+    global output_dir
+    args = build_parser().parse_args(argv)
     rank, world_size, _ = gdist.init_from_env()
     fallback = Filepaths.GNN_LOGIT_DIR if args.save_format == "logits" else Filepaths.PRED_DIR
     output_dir = os.path.expanduser(args.output_dir or fallback)
@@ -95,7 +109,7 @@ def main(argv=None):
     dataset = data_loader.ImageGraphDataset(os.path.expanduser(args.data_dir), args.data_prefix,
                                             read_image=False, read_graph=True, read_label=False)
     net = load_net_and_weights(os.path.expanduser(args.weight_file))
-    save_predictions(net, dataset, args.save_format)
+    save_predictions(net, dataset, args.save_format, cleanup_flags.from_args(args))
     if world_size > 1:
         torch.distributed.barrier()        # every rank's volumes are on disk before any rank reports completion
     print(f"Finished saving {args.save_format} generated by {args.weight_file} in folder {output_dir}")

@@ -25,6 +25,7 @@ from data_processing.labels import INTERNAL_TO_BRATS
 from gts import ops
 from model.cnn_model import combine_node_logits_and_image
 from model.networks import CnnRefinementNet, init_graph_net
+from scripts import cleanup as cleanup_flags
 from utils.hyperparam_helpers import DEFAULT_BACKGROUND_NODE_LOGITS, EvalParamSet
 
 output_dir = None
@@ -58,11 +59,30 @@ def _on_device(x, device, dtype=None):
     return t.to(device=device, dtype=dtype or t.dtype)
 
 
-def predict_one_sample(graph_net, conv_net, graph, node_feats, img, supervoxel_partitioning, relabel=None):
+def gnn_crop_box(svs, node_logits, cleanup=None):
+    """The CNN's crop box: the (dilated) box around the GNN-predicted tumour, from K12's plane flags.
+    With a `cleanup` that drops components, the box of the prediction that SURVIVES it: the arg-max is
+    projected to voxels, filtered, and the plane flags are taken from what is left, so that one stray
+    supervoxel does not inflate the box.  Nothing left: as for an empty prediction, the whole volume."""
+    if cleanup is not None and cleanup.drops_components:
+        kept = cleanup.surviving(ops.project_argmax(svs, node_logits)) != 0
+        plane_flags = [torch.any(kept, dim=1).any(dim=1), torch.any(kept, dim=0).any(dim=1),
+                       torch.any(kept, dim=0).any(dim=0)]
+    else:
+        _, plane_flags = ops.project_argmax_occupancy(svs, node_logits)                     # K12
+    crop = tumor_crop_from_plane_flags(*[f.cpu().numpy() for f in plane_flags])
+    return ops.CropBox(*[c.reshape(-1) for c in crop], svs.shape, svs.device)
+
+
+def predict_one_sample(graph_net, conv_net, graph, node_feats, img, supervoxel_partitioning, relabel=None,
+                       cleanup=None):
     """int16 label volume of the partitioning's shape: GNN prediction refined by the CNN inside
     the (dilated) box around the GNN-predicted tumour, healthy outside (reference :59-73).
     `relabel` (optional int16 table on the device) maps the labels on the way out.  The features,
-    image and partitioning may be numpy arrays or tensors already on the device."""
+    image and partitioning may be numpy arrays or tensors already on the device.
+    `cleanup` (optional scripts.cleanup.Cleanup) removes small components on the device: from the GNN
+    prediction the crop box is taken from, and from the finished volume, which it expects in BraTS
+    coding (relabel = INTERNAL_TO_BRATS); its stats of the finished volume stay in cleanup.last_stats."""
     device = _device()
     with torch.no_grad():
         graph = graph.to(device)
@@ -70,15 +90,16 @@ def predict_one_sample(graph_net, conv_net, graph, node_feats, img, supervoxel_p
         img = _on_device(img, device, torch.float32)
         svs = _on_device(supervoxel_partitioning, device)
         node_logits = graph_net(graph, node_feats).float()
-        _, plane_flags = ops.project_argmax_occupancy(svs, node_logits)                     # K12
-        crop = tumor_crop_from_plane_flags(*[f.cpu().numpy() for f in plane_flags])
-        box = ops.CropBox(*[c.reshape(-1) for c in crop], svs.shape, device)
+        box = gnn_crop_box(svs, node_logits, cleanup)
         cnn_in = combine_node_logits_and_image(node_logits, DEFAULT_BACKGROUND_NODE_LOGITS, svs, img, box)  # K16
         refined_voxel_logits = conv_net(cnn_in)
-        return ops.argmax_scatter(refined_voxel_logits.float(), box, relabel).cpu().numpy()  # K17
+        pred = ops.argmax_scatter(refined_voxel_logits.float(), box, relabel)               # K17
+        if cleanup is not None:
+            pred = cleanup(pred)
+        return pred.cpu().numpy()
 
 
-def save_predictions(graph_net, conv_net, dataset):
+def save_predictions(graph_net, conv_net, dataset, cleanup=None):
     relabel = torch.from_numpy(INTERNAL_TO_BRATS).to(_device())
     for mri, graph, node_feats, img in dataset:
         try:
@@ -86,8 +107,11 @@ def save_predictions(graph_net, conv_net, dataset):
             raw_data_crop = dataset.get_crop(mri)
         except FileNotFoundError as e:
             raise FileNotFoundError(f"Couldnt predict {mri} because couldn't read in a required file: {e}")
-        pred = predict_one_sample(graph_net, conv_net, graph, node_feats, img, supervoxel_partitioning, relabel)
+        pred = predict_one_sample(graph_net, conv_net, graph, node_feats, img, supervoxel_partitioning, relabel,
+                                  cleanup=cleanup)
         nifti_io.save_as_nifti(uncrop_to_brats_size(raw_data_crop, pred), f"{output_dir}{os.sep}{mri}.nii.gz")
+        if cleanup is not None:
+            print(f"{mri}: {cleanup.report()}")
 
 
 _ARGUMENTS = [
@@ -100,12 +124,16 @@ _ARGUMENTS = [
 ]
 
 
-def main(argv=None):
-    global output_dir
+def build_parser():
     parser = argparse.ArgumentParser()
     for short, long_, default, text in _ARGUMENTS:
         parser.add_argument(short, long_, default=default, help=text, type=str)
-    args = parser.parse_args(argv)
+    return cleanup_flags.add_flags(parser)
+
+
+def main(argv=None):
+    global output_dir
+    args = build_parser().parse_args(argv)
     # the reference falls back on an attribute its parser never defines (:97); predictions go to PRED_DIR
     output_dir = os.path.expanduser(args.output_dir if args.output_dir else Filepaths.PRED_DIR)
     if not os.path.isdir(output_dir):
@@ -115,7 +143,7 @@ def main(argv=None):
                                             read_image=True, read_graph=True, read_label=False)
     graph_net, conv_net = load_nets(args.gnn_type, os.path.expanduser(args.gnn_weights),
                                     os.path.expanduser(args.cnn_weights))
-    save_predictions(graph_net, conv_net, dataset)
+    save_predictions(graph_net, conv_net, dataset, cleanup_flags.from_args(args))
     print(f"Finished saving predictions generated by {args.gnn_weights} and {args.cnn_weights} "
           f"in folder {output_dir}")
 

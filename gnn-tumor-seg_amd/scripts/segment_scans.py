@@ -14,6 +14,13 @@ name without the suffix), or a folder of scan folders (found as preprocess_datas
 A scan that raises is reported and skipped; the exit status is 1 when any scan was skipped.
 
     python -m scripts.segment_scans -d INPUT -o OUT -g GNN.pt [-c CNN.pt] [-m GSpool] [-n 15000 -b 0.5 -k 10]
+                                    [--min_component_voxels N --connectivity {6,26} --min_enhancing_voxels T]
+
+--min_component_voxels N drops connected components of the predicted whole tumour with fewer than N voxels,
+--min_enhancing_voxels T relabels the enhancing tumour to necrotic core when fewer than T voxels of it remain
+(gts.components, on the device before the volume is copied to the host; with -c the CNN's crop box is the box of
+the GNN prediction that survives the first rule).  Both are off by default, and the scan's line of output then
+carries the counts.
 
 --stats STATS.json standardizes with the values of a file written by scripts.compute_dataset_stats (the one the
 dataset the weights were trained on was preprocessed with) instead of the BraTS-2021 constants.  Explicit
@@ -35,6 +42,7 @@ from data_processing import nifti_io, standardization  # noqa: E402
 from data_processing.image_processing import uncrop_to_brats_size  # noqa: E402
 from data_processing.labels import INTERNAL_TO_BRATS  # noqa: E402
 from gts import graphgen, intake, ops  # noqa: E402
+from scripts import cleanup as cleanup_flags  # noqa: E402
 from scripts import preprocess_dataset as prep  # noqa: E402
 
 IO_WORKERS = 3     # threads for NIfTI decode / encode around the GPU work
@@ -61,7 +69,7 @@ def build_parser():
     parser.add_argument("--stats", default=None, metavar="STATS.json",
                         help="standardization statistics file of scripts.compute_dataset_stats "
                              "(default: the BraTS-2021 constants)")
-    return parser
+    return cleanup_flags.add_flags(parser)
 
 
 def find_inputs(data_dir, modality_exts, prefix=""):
@@ -90,6 +98,7 @@ class Segmenter:
         self.args = args
         self.device = _device()
         self.k = args.num_neighbors or 0
+        self.cleanup = cleanup_flags.from_args(args)       # None with the flags at their defaults
         if getattr(args, "stats", None):
             self.mean, self.std = standardization.load_stats(os.path.expanduser(args.stats), args.modality_extensions)
         else:
@@ -124,11 +133,15 @@ class Segmenter:
         if self.conv_net is not None:
             from scripts.generate_joint_predictions import predict_one_sample
 
-            pred = predict_one_sample(self.graph_net, self.conv_net, graph, feats, image, partition, self.relabel)
+            pred = predict_one_sample(self.graph_net, self.conv_net, graph, feats, image, partition, self.relabel,
+                                      cleanup=self.cleanup)
         else:
             with torch.no_grad():
                 logits = self.graph_net(graph.to(self.device), feats)
-            pred = ops.project_argmax(partition, logits.float(), self.relabel).cpu().numpy()
+            pred = ops.project_argmax(partition, logits.float(), self.relabel)
+            if self.cleanup is not None:
+                pred = self.cleanup(pred)        # cropped volume, BraTS coding, still on the device
+            pred = pred.cpu().numpy()
         tick("predict")
         return uncrop_to_brats_size(crop, pred)
 
@@ -149,15 +162,16 @@ class Segmenter:
                     pending[i + READ_AHEAD] = pool.submit(self.load, scans[ids[i + READ_AHEAD]])
                 try:
                     volume = self.segment(pending.pop(i).result())
+                    note = f" ({self.cleanup.report()})" if self.cleanup is not None else ""
                 except Exception as exc:
                     print(f"{scan_id}: skipped ({exc!r})")
                     failed.append(scan_id)
                     continue
-                writes.append((scan_id, pool.submit(self.store, scan_id, volume)))
-            for scan_id, job in writes:
+                writes.append((scan_id, note, pool.submit(self.store, scan_id, volume)))
+            for scan_id, note, job in writes:
                 try:
                     job.result()
-                    print(f"{scan_id}: done")
+                    print(f"{scan_id}: done{note}")
                 except Exception as exc:
                     print(f"{scan_id}: writing failed ({exc!r})")
                     failed.append(scan_id)

@@ -674,6 +674,30 @@ int32_t gts_hd95_order_stats_i16(const int16_t* pred, const int16_t* truth, int6
                                  int32_t all_border, int64_t* out, void* workspace, int64_t workspace_bytes,
                                  void* stream);
 
+/* ---- C1-C5: 3-D connected components and the small-island clean-up of a prediction ------------------
+ * The post-processing step a user otherwise runs on the host with scipy.ndimage.label + np.bincount.
+ * labels: int16 volume [X, Y, Z], Z contiguous; foreground is labels != 0, whatever the values.  connectivity
+ * 6 or 26 (scipy's generate_binary_structure(3, 1) / (3, 3)); an axis of extent 1 has no neighbours along it.
+ * Limits: every extent >= 0 and X * Y * Z < 2^31; a negative extent, a larger volume, another connectivity or
+ * a workspace below gts_components_workspace(X, Y, Z) bytes: GTS_ERR_SHAPE.  A volume of zero voxels returns
+ * GTS_OK without touching memory (its workspace size is 0, as for a rejected volume).
+ * gts_components_roots_i16: roots_out (int32 [X, Y, Z]) = 1 + the smallest linear index of the voxel's
+ *   component, 0 for background.
+ * gts_components_filter_i16: labels_out (may be labels_in) = labels_in with, in this order,
+ *   (a) every foreground voxel of a component of fewer than min_voxels voxels set to 0 (min_voxels <= 1: none);
+ *   (b) with n_et the number of voxels equal to et_label that survive (a): when 0 < n_et < et_min_voxels each
+ *       of them set to et_replacement (et_min_voxels <= 0: rule off).
+ *   stats (device int64 [4]) = {components found, components removed, voxels removed, ET voxels relabelled}.
+ * Lock-free union-find with integer atomics (no workgroup waits for another); the root of a component is its
+ * smallest index and every count is an integer sum: identical results on every run. */
+int64_t gts_components_workspace(int64_t X, int64_t Y, int64_t Z);
+int32_t gts_components_roots_i16(const int16_t* labels, int64_t X, int64_t Y, int64_t Z, int32_t connectivity,
+                                 int32_t* roots_out, void* workspace, int64_t workspace_bytes, void* stream);
+int32_t gts_components_filter_i16(const int16_t* labels_in, int64_t X, int64_t Y, int64_t Z, int32_t connectivity,
+                                  int64_t min_voxels, int32_t et_label, int64_t et_min_voxels, int32_t et_replacement,
+                                  int16_t* labels_out, int64_t* stats, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+
 /* ---- I1-I3: intake of a raw four-modality scan --------------------------------------------------------
  * The host step of DataPreprocessor.load (scripts/preprocess_dataset.py) on the device:
  *   crop = determine_brain_crop(image); image = standardize_img(normalize_img(image[crop]), mean, std).
