@@ -16,7 +16,6 @@
 namespace {
 
 constexpr int kMaxLayers = 64;
-constexpr int kFlagChain = 1, kFlagReluBits = 2, kFlagTransposedIgrad = 4;
 
 inline int64_t align256(int64_t bytes) { return (bytes + 255) & ~255LL; }
 
@@ -38,7 +37,7 @@ struct FwdPlan {
 // weights the panel GEMMs may read (outputs wider than 128 columns): kept in fragment order beside the activations
 inline bool packs(int64_t out_cols) { return out_cols > 128; }
 
-inline FwdPlan plan_forward(int64_t n, const int64_t* w, int n_layers, bool training, int arg_bytes, int flags) {
+inline FwdPlan plan_forward(int64_t n, const int64_t* w, int n_layers, bool training, int arg_bytes, bool relu_bits) {
   FwdPlan p{};
   int64_t at = 0, widest = 0;
   auto take = [&](int64_t bytes) { const int64_t o = at; at += align256(bytes); return o; };
@@ -48,7 +47,7 @@ inline FwdPlan plan_forward(int64_t n, const int64_t* w, int n_layers, bool trai
     p.m[i] = take(4 * n * w[i]);
     p.arg[i] = training ? take(static_cast<int64_t>(arg_bytes) * n * w[i]) : -1;
     p.out[i] = take(4 * n * w[i + 1]);
-    const bool bits = (flags & kFlagReluBits) && training && !last && gts_relu_bits_pay(n, w[i + 1]) == 1;
+    const bool bits = relu_bits && training && !last && gts_relu_bits_pay(n, w[i + 1]) == 1;
     p.bits[i] = bits ? take(gts_relu_bits_bytes(n, w[i + 1])) : -1;
   }
   p.p[0] = take(4 * n * widest);
@@ -68,12 +67,6 @@ inline bool chainable(int64_t n, int64_t k0, int64_t k1, int64_t n2) {
   return n % 4 == 0 && k0 % 4 == 0 && k1 % 4 == 0 && n <= 256 && n2 <= 256;
 }
 
-struct Schedule {
-  const int32_t* rec;
-  int64_t clusters;
-  int32_t rows, srcs, loc_words;
-};
-
 // weights the backward reads transposed (gts/nn.py: wide rows, both dimensions multiples of 4)
 inline bool turns(int64_t rows, int64_t cols) { return cols >= 128 && rows % 4 == 0 && cols % 4 == 0; }
 
@@ -87,50 +80,66 @@ struct BwdPlan {
   int64_t total;
 };
 
-struct WgradGroup {
-  int64_t n, k;
-  std::vector<const float*> g, a;
-  std::vector<float*> gw, gb;
+// Same-shape matrices share one launch: groups keyed by (rows, cols) in order of first appearance, members in the order
+// they were added; a group hands its launch parallel pointer vectors (the launches' input and output tables).
+struct ByShape {
+  struct Group {
+    int64_t rows, cols;
+    std::vector<const float*> in[2];
+    std::vector<float*> out[2];
+    int count() const { return static_cast<int>(in[0].size()); }
+  };
+  std::vector<Group> groups;
+  void add(int64_t rows, int64_t cols, const float* in0, const float* in1, float* out0, float* out1) {
+    auto it = std::find_if(groups.begin(), groups.end(), [&](const Group& c) { return c.rows == rows && c.cols == cols; });
+    if (it == groups.end()) it = groups.insert(it, Group{rows, cols, {}, {}});
+    it->in[0].push_back(in0), it->in[1].push_back(in1), it->out[0].push_back(out0), it->out[1].push_back(out1);
+  }
 };
 
-inline BwdPlan plan_backward(int64_t n, const int64_t* w, int n_layers, int flags) {
+// the weight matrices of layer i, q = 0 / 1 / 2: w_pool [w_i, w_i], w_self and w_neigh [w_{i+1}, w_i], at params[5 i + kWeightSlot[q]]
+constexpr int kWeightSlot[3] = {0, 2, 3};
+inline int64_t weight_rows(const int64_t* w, int i, int q) { return q == 0 ? w[i] : w[i + 1]; }
+
+inline BwdPlan plan_backward(int64_t n, const int64_t* w, int n_layers) {
   BwdPlan p{};
   int64_t at = 0, widest = 0;
   auto take = [&](int64_t bytes) { const int64_t o = at; at += align256(bytes); return o; };
-  const bool t = (flags & kFlagTransposedIgrad) != 0;
+  ByShape wgrads;   // the weight-gradient groups of the run below, for the size of their split-reduction slabs
   for (int i = 0; i < n_layers; ++i) {
-    const int64_t fin = w[i], fout = w[i + 1];
+    const int64_t fin = w[i];
     widest = std::max(widest, fin);
-    p.wt[i][0] = t && turns(fin, fin) ? take(4 * fin * fin) : -1;
-    p.wt[i][1] = t && turns(fout, fin) ? take(4 * fout * fin) : -1;
-    p.wt[i][2] = t && turns(fout, fin) ? take(4 * fout * fin) : -1;
-    p.wtp[i][0] = p.wt[i][0] >= 0 ? take(4 * gts_packed_weight_floats(fin, fin)) : -1;       // W^T is [fin, rows of W]
-    p.wtp[i][1] = p.wt[i][1] >= 0 ? take(4 * gts_packed_weight_floats(fin, fout)) : -1;
-    p.wtp[i][2] = p.wt[i][2] >= 0 ? take(4 * gts_packed_weight_floats(fin, fout)) : -1;
+    for (int q = 0; q < 3; ++q) p.wt[i][q] = turns(weight_rows(w, i, q), fin) ? take(4 * weight_rows(w, i, q) * fin) : -1;
+    for (int q = 0; q < 3; ++q)   // W^T is [fin, rows of W]
+      p.wtp[i][q] = p.wt[i][q] >= 0 ? take(4 * gts_packed_weight_floats(fin, weight_rows(w, i, q))) : -1;
     p.g[i] = i > 0 ? take(4 * n * fin) : -1;
     p.gp[i] = take(4 * n * fin);
+    for (int q = 0; q < 3; ++q) wgrads.add(weight_rows(w, i, q), fin, nullptr, nullptr, nullptr, nullptr);
   }
   p.gm[0] = take(4 * n * widest);
   p.gm[1] = take(4 * n * widest);
-  // split-reduction slabs: the largest request of any weight-gradient group (the grouping of the run below)
-  struct Key { int64_t n, k; int count; };
-  std::vector<Key> groups;
-  auto add = [&](int64_t nn, int64_t kk) {
-    for (auto& gk : groups)
-      if (gk.n == nn && gk.k == kk) { ++gk.count; return; }
-    groups.push_back({nn, kk, 1});
-  };
-  for (int i = n_layers - 1; i >= 0; --i) add(w[i], w[i]), add(w[i + 1], w[i]), add(w[i + 1], w[i]);
+  // split-reduction slabs: the largest request of any weight-gradient launch
   int64_t ws = 0;
   if (n > 0)
-    for (const auto& gk : groups)
-      for (int first = 0; first < gk.count; first += gts::kMaxProblems)
-        ws = std::max(ws, gts_linear_bwd_weight_workspace(n, gk.n, gk.k, std::min(gts::kMaxProblems, gk.count - first)));
+    for (const auto& grp : wgrads.groups)
+      for (int first = 0; first < grp.count(); first += gts::kMaxProblems)
+        ws = std::max(ws, gts_linear_bwd_weight_workspace(n, grp.rows, grp.cols, std::min(gts::kMaxProblems, grp.count() - first)));
   p.workspace_bytes = ws;
   p.workspace = take(ws);
   p.counters = take(4 * GTS_CLUSTER_COUNTER_WORDS);
   p.total = at;
   return p;
+}
+
+// The unit counters of the clustered K1 / K2 launches at `at`, zeroed once per call (every launch leaves them zero); null
+// in *counters when there is no schedule or its launches deal their units statically.
+inline int32_t zero_counters(const int32_t* sched_rec, int64_t clusters, int32_t rows, int32_t srcs, int32_t loc_words,
+                             int32_t backward, void* at, void* stream, uint32_t** counters) {
+  *counters = nullptr;
+  if (sched_rec == nullptr || gts_cluster_uses_counters(clusters, rows, srcs, loc_words, backward) == 0) return GTS_OK;
+  if (hipMemsetAsync(at, 0, 4 * GTS_CLUSTER_COUNTER_WORDS, static_cast<hipStream_t>(stream)) != hipSuccess) return gts::launch_status();
+  *counters = static_cast<uint32_t*>(at);
+  return GTS_OK;
 }
 
 #define GTS_TRY(call)                    \
@@ -142,9 +151,9 @@ inline BwdPlan plan_backward(int64_t n, const int64_t* w, int n_layers, int flag
 }  // namespace
 
 extern "C" int64_t gts_sage_pool_stack_fwd_arena(int64_t n_rows, const int64_t* widths, int32_t n_layers, int32_t training,
-                                                 int32_t arg_bytes, int32_t flags, int64_t* offsets) {
+                                                 int32_t arg_bytes, int32_t relu_bits, int64_t* offsets) {
   if (bad_stack(n_rows, widths, n_layers) || (training && arg_bytes != 1 && arg_bytes != 4)) return -1;
-  const FwdPlan p = plan_forward(n_rows, widths, n_layers, training != 0, arg_bytes, flags);
+  const FwdPlan p = plan_forward(n_rows, widths, n_layers, training != 0, arg_bytes, relu_bits != 0);
   if (offsets != nullptr) {
     for (int i = 0; i < n_layers; ++i)
       offsets[4 * i] = p.m[i], offsets[4 * i + 1] = p.arg[i], offsets[4 * i + 2] = p.out[i], offsets[4 * i + 3] = p.bits[i];
@@ -157,7 +166,7 @@ extern "C" int32_t gts_sage_pool_stack_fwd_f32(const int32_t* indptr, const int3
                                                int64_t sched_clusters, int32_t sched_rows, int32_t sched_srcs,
                                                int32_t sched_loc_words, const float* x, const float* const* params,
                                                int64_t n_rows, const int64_t* widths, int32_t n_layers, int32_t training,
-                                               int32_t arg_bytes, int32_t flags, void* arena, int64_t arena_bytes,
+                                               int32_t arg_bytes, int32_t relu_bits, void* arena, int64_t arena_bytes,
                                                void* stream) {
   if (!indptr || !x || !params || !arena) return GTS_ERR_NULL;
   if (bad_stack(n_rows, widths, n_layers)) return GTS_ERR_SHAPE;
@@ -165,38 +174,23 @@ extern "C" int32_t gts_sage_pool_stack_fwd_f32(const int32_t* indptr, const int3
   for (int i = 0; i < 5 * n_layers; ++i)
     if (!params[i]) return GTS_ERR_NULL;
   const bool train = training != 0;
-  const FwdPlan plan = plan_forward(n_rows, widths, n_layers, train, arg_bytes, flags);
+  const FwdPlan plan = plan_forward(n_rows, widths, n_layers, train, arg_bytes, relu_bits != 0);
   if (arena_bytes < plan.total) return GTS_ERR_SHAPE;
   if (n_rows == 0) return GTS_OK;
   char* base = static_cast<char*>(arena);
   auto f32 = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
-  uint32_t* counters = nullptr;   // unit counters of the clustered K1 launches: zeroed once here, every launch leaves them zero
-  if (sched_rec != nullptr && gts_cluster_uses_counters(sched_clusters, sched_rows, sched_srcs, sched_loc_words, 0) != 0) {
-    counters = reinterpret_cast<uint32_t*>(base + plan.counters);
-    if (hipMemsetAsync(counters, 0, 4 * GTS_CLUSTER_COUNTER_WORDS, static_cast<hipStream_t>(stream)) != hipSuccess) return GTS_ERR_SHAPE;
-  }
+  uint32_t* counters;
+  GTS_TRY(zero_counters(sched_rec, sched_clusters, sched_rows, sched_srcs, sched_loc_words, 0, base + plan.counters, stream, &counters));
   // the weights the panel GEMMs will read, in fragment order: one launch per weight shape (the weights change once per
   // optimizer step; 19 matrices of 256 KiB at C2)
   {
-    struct Batch { int64_t rows, cols; std::vector<const float*> src; std::vector<float*> dst; };
-    std::vector<Batch> batches;
-    for (int i = 0; i < n_layers; ++i) {
-      const int64_t fin = widths[i], fout = widths[i + 1];
-      const int64_t shape[3][2] = {{fin, fin}, {fout, fin}, {fout, fin}};
-      const int which[3] = {0, 2, 3};
-      for (int q = 0; q < 3; ++q) {
-        if (plan.wp[i][q] < 0) continue;
-        Batch* b = nullptr;
-        for (auto& c : batches)
-          if (c.rows == shape[q][0] && c.cols == shape[q][1]) b = &c;
-        if (b == nullptr) batches.push_back({shape[q][0], shape[q][1], {}, {}}), b = &batches.back();
-        b->src.push_back(params[5 * i + which[q]]);
-        b->dst.push_back(f32(plan.wp[i][q]));
-      }
-    }
-    for (const auto& b : batches)
-      GTS_TRY(gts_pack_weights_f32(b.src.data(), b.dst.data(), nullptr, static_cast<int32_t>(b.src.size()), b.rows, b.cols, 0,
-                                   stream));
+    ByShape packs;
+    for (int i = 0; i < n_layers; ++i)
+      for (int q = 0; q < 3; ++q)
+        if (plan.wp[i][q] >= 0)
+          packs.add(weight_rows(widths, i, q), widths[i], params[5 * i + kWeightSlot[q]], nullptr, f32(plan.wp[i][q]), nullptr);
+    for (const auto& b : packs.groups)
+      GTS_TRY(gts_pack_weights_f32(b.in[0].data(), b.out[0].data(), nullptr, b.count(), b.rows, b.cols, 0, stream));
   }
   auto wp = [&](int i, int q) -> const float* { return plan.wp[i][q] >= 0 ? f32(plan.wp[i][q]) : nullptr; };
   const float* h = x;
@@ -226,7 +220,7 @@ extern "C" int32_t gts_sage_pool_stack_fwd_f32(const int32_t* indptr, const int3
     }
     uint64_t* bits = plan.bits[i] >= 0 ? reinterpret_cast<uint64_t*>(base + plan.bits[i]) : nullptr;
     float* out = f32(plan.out[i]);
-    if ((flags & kFlagChain) && !last && chainable(fout, fin, fin, fout)) {
+    if (!last && chainable(fout, fin, fin, fout)) {
       // fc_self + fc_neigh of this layer and fc_pool of the next one in one launch
       float* p_next = f32(plan.p[cur ^ 1]);
       const float* packed[3] = {wp(i, 1), wp(i, 2), wp(i + 1, 0)};
@@ -243,16 +237,17 @@ extern "C" int32_t gts_sage_pool_stack_fwd_f32(const int32_t* indptr, const int3
   return GTS_OK;
 }
 
-extern "C" int64_t gts_sage_pool_stack_bwd_scratch(int64_t n_rows, const int64_t* widths, int32_t n_layers, int32_t flags) {
+extern "C" int64_t gts_sage_pool_stack_bwd_scratch(int64_t n_rows, const int64_t* widths, int32_t n_layers,
+                                                   int32_t /*relu_bits: the scratch holds no masks*/) {
   if (bad_stack(n_rows, widths, n_layers)) return -1;
-  return plan_backward(n_rows, widths, n_layers, flags).total;
+  return plan_backward(n_rows, widths, n_layers).total;
 }
 
 extern "C" int32_t gts_sage_pool_stack_bwd_f32(const int32_t* t_indptr, const int32_t* t_indices, const int32_t* t_slot,
                                                const int32_t* sched_rec, int64_t sched_clusters, int32_t sched_rows,
                                                int32_t sched_srcs, int32_t sched_loc_words, const float* gout, const float* x,
                                                const float* const* params, int64_t n_rows, const int64_t* widths,
-                                               int32_t n_layers, int32_t arg_bytes, int32_t flags, const void* fwd_arena,
+                                               int32_t n_layers, int32_t arg_bytes, int32_t relu_bits, const void* fwd_arena,
                                                float* const* grads, float* gx, void* scratch, int64_t scratch_bytes,
                                                void* stream) {
   if (!t_indptr || !gout || !x || !params || !fwd_arena || !grads || !scratch) return GTS_ERR_NULL;
@@ -270,43 +265,28 @@ extern "C" int32_t gts_sage_pool_stack_bwd_f32(const int32_t* t_indptr, const in
     }
     return GTS_OK;
   }
-  const FwdPlan fwd = plan_forward(n_rows, widths, n_layers, true, arg_bytes, flags);
-  const BwdPlan plan = plan_backward(n_rows, widths, n_layers, flags);
+  const FwdPlan fwd = plan_forward(n_rows, widths, n_layers, true, arg_bytes, relu_bits != 0);
+  const BwdPlan plan = plan_backward(n_rows, widths, n_layers);
   if (scratch_bytes < plan.total) return GTS_ERR_SHAPE;
   const char* acts = static_cast<const char*>(fwd_arena);
   char* base = static_cast<char*>(scratch);
   auto f32 = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
-  uint32_t* counters = nullptr;   // unit counters of the clustered K2 launches (as in the forward call)
-  if (sched_rec != nullptr && gts_cluster_uses_counters(sched_clusters, sched_rows, sched_srcs, sched_loc_words, 1) != 0) {
-    counters = reinterpret_cast<uint32_t*>(base + plan.counters);
-    if (hipMemsetAsync(counters, 0, 4 * GTS_CLUSTER_COUNTER_WORDS, static_cast<hipStream_t>(stream)) != hipSuccess) return GTS_ERR_SHAPE;
-  }
+  uint32_t* counters;
+  GTS_TRY(zero_counters(sched_rec, sched_clusters, sched_rows, sched_srcs, sched_loc_words, 1, base + plan.counters, stream, &counters));
   auto act = [&](int64_t off) { return reinterpret_cast<const float*>(acts + off); };
   auto input_of = [&](int i) { return i == 0 ? x : act(fwd.out[i - 1]); };
 
   // transposed weights: one batch per shape, in the order the shapes first appear (pool, self, neigh per layer)
   {
-    struct Batch { int64_t rows, cols; std::vector<const float*> src; std::vector<float*> dst, packed; };
-    std::vector<Batch> batches;
-    for (int i = 0; i < n_layers; ++i) {
-      const int64_t fin = widths[i], fout = widths[i + 1];
-      const int64_t shape[3][2] = {{fin, fin}, {fout, fin}, {fout, fin}};
-      const int which[3] = {0, 2, 3};
-      for (int q = 0; q < 3; ++q) {
-        if (plan.wt[i][q] < 0) continue;
-        Batch* b = nullptr;
-        for (auto& c : batches)
-          if (c.rows == shape[q][0] && c.cols == shape[q][1]) b = &c;
-        if (b == nullptr) batches.push_back({shape[q][0], shape[q][1], {}, {}, {}}), b = &batches.back();
-        b->src.push_back(params[5 * i + which[q]]);
-        b->dst.push_back(f32(plan.wt[i][q]));
-        b->packed.push_back(f32(plan.wtp[i][q]));
-      }
-    }
+    ByShape turned;   // out[0]: W^T row-major, out[1]: W^T in fragment order
+    for (int i = 0; i < n_layers; ++i)
+      for (int q = 0; q < 3; ++q)
+        if (plan.wt[i][q] >= 0)
+          turned.add(weight_rows(widths, i, q), widths[i], params[5 * i + kWeightSlot[q]], nullptr, f32(plan.wt[i][q]),
+                     f32(plan.wtp[i][q]));
     // W^T twice in one launch per shape: row-major (the tiles that stage through LDS) and in fragment order (the panel kernels)
-    for (const auto& b : batches)
-      GTS_TRY(gts_pack_weights_f32(b.src.data(), b.packed.data(), b.dst.data(), static_cast<int32_t>(b.src.size()), b.rows,
-                                   b.cols, 1, stream));
+    for (const auto& b : turned.groups)
+      GTS_TRY(gts_pack_weights_f32(b.in[0].data(), b.out[1].data(), b.out[0].data(), b.count(), b.rows, b.cols, 1, stream));
   }
   auto wt = [&](int i, int q) -> const float* { return plan.wt[i][q] >= 0 ? f32(plan.wt[i][q]) : nullptr; };
   auto wtp = [&](int i, int q) -> const float* { return plan.wtp[i][q] >= 0 ? f32(plan.wtp[i][q]) : nullptr; };
@@ -323,14 +303,7 @@ extern "C" int32_t gts_sage_pool_stack_bwd_f32(const int32_t* t_indptr, const in
     return gts_linear_bwd_input_f32(g0, w0, g1, g1 ? w1 : nullptr, relu_mask, gin, n_rows, k, n0, g1 ? n1 : 0, stream);
   };
 
-  std::vector<WgradGroup> groups;   // weight-gradient problems by shape, in order of first appearance
-  auto defer = [&](const float* g, int64_t n, const float* a, int64_t k, float* gw, float* gb) {
-    WgradGroup* grp = nullptr;
-    for (auto& c : groups)
-      if (c.n == n && c.k == k) grp = &c;
-    if (grp == nullptr) groups.push_back({n, k, {}, {}, {}, {}}), grp = &groups.back();
-    grp->g.push_back(g), grp->a.push_back(a), grp->gw.push_back(gw), grp->gb.push_back(gb);
-  };
+  ByShape wgrads;   // deferred weight-gradient problems by the weight's shape: in = g [n_rows, rows], a [n_rows, cols]; out = gw, gb
 
   const float* g = gout;    // gradient w.r.t. the pre-activation output of layer i
   const float* gm = nullptr;   // g @ W_neigh of the layer about to run, when the previous launch already made it
@@ -356,15 +329,15 @@ extern "C" int32_t gts_sage_pool_stack_bwd_f32(const int32_t* t_indptr, const in
       GTS_TRY(gts_spmm_max_bwd_f32(t_indptr, t_indices, t_slot, gm, arg, arg_bytes, nullptr, gp, n_rows, fin, stream));
     }
     gm = nullptr;
-    defer(gp, fin, h, fin, grads[5 * i], grads[5 * i + 1]);        // fc_pool.weight, fc_pool.bias
-    defer(g, fout, h, fin, grads[5 * i + 2], grads[5 * i + 4]);    // fc_self.weight, bias
-    defer(g, fout, m, fin, grads[5 * i + 3], nullptr);             // fc_neigh.weight
+    wgrads.add(fin, fin, gp, h, grads[5 * i], grads[5 * i + 1]);        // fc_pool.weight, fc_pool.bias
+    wgrads.add(fout, fin, g, h, grads[5 * i + 2], grads[5 * i + 4]);    // fc_self.weight, bias
+    wgrads.add(fout, fin, g, m, grads[5 * i + 3], nullptr);             // fc_neigh.weight
     if (i > 0) {   // h is layer i-1's ReLU output: its backward is the mask h > 0
       const int64_t below_in = widths[i - 1];
       const uint64_t* hbits = fwd.bits[i - 1] >= 0 ? reinterpret_cast<const uint64_t*>(acts + fwd.bits[i - 1]) : nullptr;
       float* g_next = f32(plan.g[i]);
       const float* below_t = wt(i - 1, 2);
-      if ((flags & kFlagChain) && wt(i, 1) && wt(i, 0) && below_t && chainable(fin, fout, fin, below_in)) {
+      if (wt(i, 1) && wt(i, 0) && below_t && chainable(fin, fout, fin, below_in)) {
         // this layer's input gradient and the next one's g @ W_neigh in one launch
         float* gm_next = f32(plan.gm[cur ^ 1]);
         const float* packed[3] = {wtp(i, 1), wtp(i, 0), wtp(i - 1, 2)};
@@ -379,14 +352,10 @@ extern "C" int32_t gts_sage_pool_stack_bwd_f32(const int32_t* t_indptr, const in
       GTS_TRY(igrad(g, w_self, wt(i, 1), fout, gp, w_pool, wt(i, 0), fin, nullptr, nullptr, gx, fin, wtp(i, 1), wtp(i, 0)));
     }
   }
-  for (const auto& grp : groups) {
-    const int count = static_cast<int>(grp.g.size());
-    for (int first = 0; first < count; first += gts::kMaxProblems) {
-      const int q = std::min(gts::kMaxProblems, count - first);
-      GTS_TRY(gts_linear_bwd_weight_f32(grp.g.data() + first, grp.a.data() + first, grp.gw.data() + first,
-                                        grp.gb.data() + first, q, f32(plan.workspace), plan.workspace_bytes, n_rows, grp.n,
-                                        grp.k, stream));
-    }
-  }
+  for (const auto& grp : wgrads.groups)
+    for (int first = 0; first < grp.count(); first += gts::kMaxProblems)
+      GTS_TRY(gts_linear_bwd_weight_f32(grp.in[0].data() + first, grp.in[1].data() + first, grp.out[0].data() + first,
+                                        grp.out[1].data() + first, std::min(gts::kMaxProblems, grp.count() - first),
+                                        f32(plan.workspace), plan.workspace_bytes, n_rows, grp.rows, grp.cols, stream));
   return GTS_OK;
 }

@@ -137,30 +137,6 @@ def _identity(n, device):
     return _identities[key]
 
 
-# GTS_OVERLAP_WGRAD=1 runs the weight gradients of the fused stack on a second, low-priority stream
-# (see _SagePoolStack.backward).  Off by default: with the current kernels the side stream takes
-# CUs from the input-gradient chain it was meant to fill in behind (757 graphs/s with it, 777-789
-# without, profiles/r01_tune_gemm.log).
-OVERLAP_WEIGHT_GRADS = os.environ.get("GTS_OVERLAP_WGRAD", "0") != "0"
-# GTS_TRANSPOSED_IGRAD=0 keeps the strided-weight input-gradient kernel in the fused stack (A/B runs).
-TRANSPOSED_IGRAD = os.environ.get("GTS_TRANSPOSED_IGRAD", "1") != "0"
-_side_streams = {}
-
-
-def _side_stream(device):
-    s = _side_streams.get(device)
-    if s is None:
-        try:
-            priority = torch.cuda.Stream.priority_range()[0]   # least urgent
-        except Exception:                                       # noqa: BLE001 - older runtimes
-            priority = 0
-        s = torch.cuda.Stream(device=device, priority=priority)
-        _side_streams[device] = s
-    return s
-
-
-# GTS_CHAIN_GEMMS=0 keeps one launch per GEMM in the fused stack (A/B runs).
-CHAIN_LAYER_GEMMS = os.environ.get("GTS_CHAIN_GEMMS", "1") != "0"
 # GTS_RELU_BITS=0: the backward of the fused stack reads its ReLU masks from the saved activations (floats)
 # instead of the bit masks the forward GEMMs record (A/B runs).
 RELU_MASK_BITS = os.environ.get("GTS_RELU_BITS", "1") != "0"
@@ -183,15 +159,20 @@ def _pool_layer_weight_grads(g, gp, h, m, w_pool, w_self):
     return g_ws, g_wn, g_wp, g_bias, g_bp
 
 
-def _pack_by_shape(weights, transposed):
-    """{id(w): fragment-order copy} of `weights`, one gts_pack_weights_f32 launch per weight shape."""
-    by_shape, out = {}, {}
+def _pack_by_shape(weights, transposed, want_plain=False):
+    """{id(w): fragment-order copy} of `weights` (of their transposes when `transposed`), one gts_pack_weights_f32 launch
+    per weight shape: shapes in order of first appearance, matrices in the given order inside a shape.  With
+    `want_plain` (transposed only) the same launches also leave W^T row-major: ({id(w): W^T}, {id(w): fragment copy})."""
+    by_shape, plain, fragment = {}, {}, {}
     for w in weights:
         by_shape.setdefault(tuple(w.shape), []).append(w)
     for ws in by_shape.values():
-        for w, wp in zip(ws, dense.pack_weights(ws, transposed=transposed)):
-            out[id(w)] = wp
-    return out
+        copies = dense.pack_weights(ws, transposed=transposed, want_plain=want_plain)
+        if want_plain:
+            plain.update((id(w), wt) for w, wt in zip(ws, copies[0]))
+            copies = copies[1]
+        fragment.update((id(w), wp) for w, wp in zip(ws, copies))
+    return (plain, fragment) if want_plain else fragment
 
 
 class _SagePoolStack(torch.autograd.Function):
@@ -223,7 +204,7 @@ class _SagePoolStack(torch.autograd.Function):
             nxt = params[5 * (i + 1):5 * (i + 1) + 2] if not last else None
             obits = dense.relu_bits_empty(h.shape[0], w_self.shape[0], h.device) \
                 if RELU_MASK_BITS and need_bwd and not last and dense.relu_bits_pay(h.shape[0], w_self.shape[0]) else None
-            if CHAIN_LAYER_GEMMS and nxt is not None and _chainable(h, w_self, m, nxt[0]):
+            if nxt is not None and _chainable(h, w_self, m, nxt[0]):
                 # fc_self + fc_neigh of this layer and fc_pool of the next one in one launch
                 out, p = dense.linear_fwd_chain(h, w_self, m, w_neigh, bias, True, nxt[0], nxt[1], True, relu_bits=obits,
                                                 packed=(fragment.get(id(w_self)), fragment.get(id(w_neigh)), fragment.get(id(nxt[0]))))
@@ -249,26 +230,14 @@ class _SagePoolStack(torch.autograd.Function):
         # by layer: every (gradient, activation) pair is kept and all problems of one shape go into
         # ONE split-reduction launch at the end (the 256-wide layers of C2: 19 problems).  Few long
         # reductions per workgroup instead of many short ones, one slab reduction instead of seven.
-        # (GTS_OVERLAP_WGRAD=1 restores the older scheme: per-layer launches on a second,
-        # low-priority stream.)
-        main = torch.cuda.current_stream()
-        side = _side_stream(g.device) if OVERLAP_WEIGHT_GRADS else None
-        keep_alive = []
         deferred = {}                    # (N, K) -> [(g [M,N], a [M,K], want_bias, grads slot, bias slot)]
 
         # Input gradients run in the forward GEMM's form on transposed weights (one batched
         # transpose per weight shape and backward pass; wide outputs only — the 4-wide first /
-        # last layers keep the strided-operand kernel).
-        turned, turned_fragment = {}, {}      # W^T row-major / in fragment order (the panel kernels), one launch per shape
-        if TRANSPOSED_IGRAD:
-            by_shape = {}
-            for w in (params[5 * i + j] for i in range(n) for j in (0, 2, 3)):
-                if w.shape[1] >= 128 and w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0:
-                    by_shape.setdefault(tuple(w.shape), []).append(w)
-            for ws in by_shape.values():
-                plain, packed = dense.pack_weights(ws, transposed=True, want_plain=True)
-                for w, wt, wp in zip(ws, plain, packed):
-                    turned[id(w)], turned_fragment[id(w)] = wt, wp
+        # last layers keep the strided-operand kernel).  W^T row-major / in fragment order (the panel kernels):
+        turned, turned_fragment = _pack_by_shape(
+            [w for w in (params[5 * i + j] for i in range(n) for j in (0, 2, 3))
+             if w.shape[1] >= 128 and w.shape[0] % 4 == 0 and w.shape[1] % 4 == 0], transposed=True, want_plain=True)
 
         def igrad(g0, w0, g1=None, w1=None, relu_mask=None, relu_bits=None):
             if id(w0) in turned and (w1 is None or id(w1) in turned) and g0.is_contiguous():
@@ -289,22 +258,12 @@ class _SagePoolStack(torch.autograd.Function):
                 gm = igrad(g, w_neigh)
             gp = ops.spmm_max_bwd(ctx.g, gm, arg)       # ReLU'(p) is already in the winner record
             gm = None
-            if side is None:
-                defer(gp, h, 5 * i, 5 * i + 1)          # fc_pool.weight, fc_pool.bias
-                defer(g, h, 5 * i + 2, 5 * i + 4)       # fc_self.weight, bias
-                defer(g, m, 5 * i + 3, None)            # fc_neigh.weight
-            else:
-                ready = torch.cuda.Event()
-                ready.record(main)                      # g and gp are complete on the main stream
-                with torch.cuda.stream(side):
-                    side.wait_event(ready)
-                    g_ws, g_wn, g_wp, g_bias, g_bp = _pool_layer_weight_grads(g, gp, h, m, w_pool, w_self)
-                keep_alive.append((g, gp))              # still being read by the side stream
-                grads[5 * i:5 * i + 5] = [g_wp, g_bp, g_ws, g_wn, g_bias]
+            defer(gp, h, 5 * i, 5 * i + 1)              # fc_pool.weight, fc_pool.bias
+            defer(g, h, 5 * i + 2, 5 * i + 4)           # fc_self.weight, bias
+            defer(g, m, 5 * i + 3, None)                # fc_neigh.weight
             if i > 0:      # h is layer i-1's ReLU output: its backward is the mask h > 0
                 below = params[5 * (i - 1) + 3]          # W_neigh of the layer below
-                if CHAIN_LAYER_GEMMS and all(id(w) in turned for w in (w_self, w_pool, below)) \
-                        and _chainable(g, w_self.t(), gp, below.t()):
+                if all(id(w) in turned for w in (w_self, w_pool, below)) and _chainable(g, w_self.t(), gp, below.t()):
                     # this layer's input gradient and the next one's g @ W_neigh in one launch
                     g, gm = dense.linear_bwd_input_chain_t(g, turned[id(w_self)], gp, turned[id(w_pool)], h,
                                                            turned[id(below)], relu_bits=hbits,
@@ -320,13 +279,6 @@ class _SagePoolStack(torch.autograd.Function):
                 grads[slot] = gw
                 if bias_slot is not None:
                     grads[bias_slot] = gb
-        if side is not None:
-            main.wait_stream(side)
-            for t in grads:
-                t.record_stream(main)                   # allocated on `side`, consumed on `main`
-            for pair in keep_alive:
-                for t in pair:
-                    t.record_stream(side)
         return (None, gx, None, *grads)
 
 
@@ -394,10 +346,6 @@ def _stack_table(params, in_feats):
     return hit
 
 
-def _stack_flags():
-    return (1 if CHAIN_LAYER_GEMMS else 0) | (2 if RELU_MASK_BITS else 0) | (4 if TRANSPOSED_IGRAD else 0)
-
-
 class _SagePoolStackCall(torch.autograd.Function):
     """`_SagePoolStack` behind one C-ABI call each way (gts_sage_pool_stack_fwd_f32 / _bwd_f32: the same launches in
     the same order, enqueued by the library; bit-identical, tests/test_gpu_stack.py).  Activations and winners live
@@ -414,10 +362,10 @@ class _SagePoolStackCall(torch.autograd.Function):
         x = x.contiguous()
         n, n_layers = x.shape[0], len(params) // 5
         table, c_widths, widths = _stack_table(params, x.shape[1])
-        flags, ab = _stack_flags(), g.arg_bytes
+        relu_bits, ab = 1 if RELU_MASK_BITS else 0, g.arg_bytes
         d = g.dev()
         offsets = (ctypes.c_int64 * (4 * n_layers + 2))()
-        total = lib.gts_sage_pool_stack_fwd_arena(n, c_widths, n_layers, 1 if need_bwd else 0, ab, flags, offsets)
+        total = lib.gts_sage_pool_stack_fwd_arena(n, c_widths, n_layers, 1 if need_bwd else 0, ab, relu_bits, offsets)
         if total < 0:
             raise _lib.GtsError("gts_sage_pool_stack_fwd_arena rejected the stack's shape")
         arena = torch.empty(max(int(total), 16), dtype=torch.uint8, device=x.device)
@@ -426,12 +374,12 @@ class _SagePoolStackCall(torch.autograd.Function):
         check(lib.gts_sage_pool_stack_fwd_f32(
             ptr(d.indptr), ptr(d.indices), ptr(ds.packed) if ds else None, h.n_clusters if h else 0,
             h.limits[0] if h else 0, h.limits[1] if h else 0, h.loc_words if h else 0, ptr(x), table, n, c_widths,
-            n_layers, 1 if need_bwd else 0, ab, flags, arena.data_ptr(), int(total), current_stream()),
+            n_layers, 1 if need_bwd else 0, ab, relu_bits, arena.data_ptr(), int(total), current_stream()),
             "gts_sage_pool_stack_fwd_f32")
         at = int(offsets[4 * (n_layers - 1) + 2])
         out = arena[at:at + 4 * n * widths[-1]].view(torch.float32).view(n, widths[-1])
         if need_bwd:
-            ctx.g, ctx.widths, ctx.flags, ctx.ab = g, widths, flags, ab
+            ctx.g, ctx.widths, ctx.relu_bits, ctx.ab = g, widths, relu_bits, ab
             ctx.param_ids = [id(p) for p in params]
             ctx.save_for_backward(x, arena, *params)
         return out
@@ -445,7 +393,7 @@ class _SagePoolStackCall(torch.autograd.Function):
 
         lib = _lib.load()
         x, arena, *params = ctx.saved_tensors
-        g, widths, flags, ab = ctx.g, ctx.widths, ctx.flags, ctx.ab
+        g, widths, relu_bits, ab = ctx.g, ctx.widths, ctx.relu_bits, ctx.ab
         n, n_layers = x.shape[0], len(params) // 5
         gout = gout.contiguous()
         d = g.dev()
@@ -467,7 +415,7 @@ class _SagePoolStackCall(torch.autograd.Function):
         base = flat.data_ptr()
         grads = (ctypes.c_void_p * (5 * n_layers))(*[base + 4 * s for s in starts])
         table, c_widths, _ = _stack_table(params, x.shape[1])
-        need = lib.gts_sage_pool_stack_bwd_scratch(n, c_widths, n_layers, flags)
+        need = lib.gts_sage_pool_stack_bwd_scratch(n, c_widths, n_layers, relu_bits)
         scratch = torch.empty(max(int(need), 16), dtype=torch.uint8, device=x.device)
         gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
         ds = ops._cluster_schedule(g, "out", n, 256, ab) if 256 in widths[:-1] else None
@@ -475,7 +423,7 @@ class _SagePoolStackCall(torch.autograd.Function):
         check(lib.gts_sage_pool_stack_bwd_f32(
             ptr(d.t_indptr), ptr(d.t_indices), ptr(d.t_slot), ptr(ds.packed) if ds else None, h.n_clusters if h else 0,
             h.limits[0] if h else 0, h.limits[1] if h else 0, h.loc_words if h else 0, ptr(gout), ptr(x), table, n,
-            c_widths, n_layers, ab, flags, arena.data_ptr(), grads, ptr(gx), scratch.data_ptr(), int(need),
+            c_widths, n_layers, ab, relu_bits, arena.data_ptr(), grads, ptr(gx), scratch.data_ptr(), int(need),
             current_stream()), "gts_sage_pool_stack_bwd_f32")
         if sink is not None:
             sink.filled = True
@@ -499,7 +447,7 @@ def sage_pool_stack(graph, features, layers):
         params += [layer.fc_pool.weight, layer.fc_pool.bias, layer.fc_self.weight,
                    layer.fc_neigh.weight, layer.bias]
     need_bwd = torch.is_grad_enabled() and (features.requires_grad or any(p.requires_grad for p in params))
-    one_call = STACK_IN_ONE_CALL and not ops.INSTRUMENTED and not OVERLAP_WEIGHT_GRADS and features.shape[1] % 4 == 0 \
+    one_call = STACK_IN_ONE_CALL and not ops.INSTRUMENTED and features.shape[1] % 4 == 0 \
         and all(p.shape[-1] % 4 == 0 and p.shape[0] % 4 == 0 and p.is_contiguous() for p in params) \
         and features.dtype == torch.float32 and features.is_cuda
     return (_SagePoolStackCall if one_call else _SagePoolStack).apply(graph, features, need_bwd, *params)
@@ -673,7 +621,7 @@ class _GATLayer(torch.autograd.Function):
         gft2 = gft.view(n, heads * dim)
         g_wres = None
         # wide layers: the input gradient runs in the forward GEMM's form on transposed weights
-        turn = TRANSPOSED_IGRAD and need[1] and w_fc.shape[1] >= 128 and w_fc.shape[0] % 4 == 0 \
+        turn = need[1] and w_fc.shape[1] >= 128 and w_fc.shape[0] % 4 == 0 \
             and w_fc.shape[1] % 4 == 0 and n >= 4096
         fold = turn and ctx.below is not None and ctx.below.armed == 1 and not ctx.identity_res and FOLD_GAT_ACT_BWD
         act_below = ctx.below.armed if fold else 0

@@ -429,8 +429,10 @@ int32_t gts_linear_bwd_weight_f32(const float* const* g, const float* const* a, 
  *                            fc_neigh.weight [w_{i+1}, w_i], bias [w_{i+1}]                       (device pointers)
  *   sched_*: optional cluster row schedule (gts_cluster_schedule) of the in-CSR (forward) / of the out-CSR tagged with
  *            t_slot (backward); NULL = plain K1 / K2.  Used by the 256-wide layers when arg_bytes allows.
- *   flags: 1 = chain consecutive GEMMs into one launch, 2 = record / read ReLU masks as bits, 4 = input gradients on
- *          transposed weights (7 = what the layer-by-layer path does by default).
+ *   relu_bits: 1 = the forward GEMMs record the ReLU masks as bits (where gts_relu_bits_pay says so) and the backward reads
+ *          them; 0 = the backward reads the masks from the saved activations.  The same value in all four calls of a step.
+ *   Which launches are chained (consecutive GEMMs in one) and which weights the backward reads transposed is decided by
+ *   shape alone: widths <= 256 chain, weights with >= 128 columns are transposed once per backward call.
  * Forward: everything it produces lives in `arena` (>= gts_sage_pool_stack_fwd_arena(...) bytes, which also reports the
  * byte offsets: offsets[4 i .. 4 i + 3] = max-pooled features m_i [n, w_i], winners arg_i [n, w_i] (arg_bytes each; -1
  * when not training), output out_i [n, w_{i+1}] (the next layer's input; the last one holds the logits), ReLU bits of out_i
@@ -439,18 +441,18 @@ int32_t gts_linear_bwd_weight_f32(const float* const* g, const float* const* a, 
  * gradients of params[5 i .. 5 i + 4] (any caller-chosen destinations, e.g. slices of one flat buffer); gx [n, w_0]
  * optional; scratch >= gts_sage_pool_stack_bwd_scratch(...) bytes. */
 int64_t gts_sage_pool_stack_fwd_arena(int64_t n_rows, const int64_t* widths, int32_t n_layers, int32_t training,
-                                      int32_t arg_bytes, int32_t flags, int64_t* offsets);
+                                      int32_t arg_bytes, int32_t relu_bits, int64_t* offsets);
 int32_t gts_sage_pool_stack_fwd_f32(const int32_t* indptr, const int32_t* indices, const int32_t* sched_rec,
                                     int64_t sched_clusters, int32_t sched_rows, int32_t sched_srcs,
                                     int32_t sched_loc_words, const float* x, const float* const* params,
                                     int64_t n_rows, const int64_t* widths, int32_t n_layers, int32_t training,
-                                    int32_t arg_bytes, int32_t flags, void* arena, int64_t arena_bytes, void* stream);
-int64_t gts_sage_pool_stack_bwd_scratch(int64_t n_rows, const int64_t* widths, int32_t n_layers, int32_t flags);
+                                    int32_t arg_bytes, int32_t relu_bits, void* arena, int64_t arena_bytes, void* stream);
+int64_t gts_sage_pool_stack_bwd_scratch(int64_t n_rows, const int64_t* widths, int32_t n_layers, int32_t relu_bits);
 int32_t gts_sage_pool_stack_bwd_f32(const int32_t* t_indptr, const int32_t* t_indices, const int32_t* t_slot,
                                     const int32_t* sched_rec, int64_t sched_clusters, int32_t sched_rows,
                                     int32_t sched_srcs, int32_t sched_loc_words, const float* gout, const float* x,
                                     const float* const* params, int64_t n_rows, const int64_t* widths,
-                                    int32_t n_layers, int32_t arg_bytes, int32_t flags, const void* fwd_arena,
+                                    int32_t n_layers, int32_t arg_bytes, int32_t relu_bits, const void* fwd_arena,
                                     float* const* grads, float* gx, void* scratch, int64_t scratch_bytes,
                                     void* stream);
 

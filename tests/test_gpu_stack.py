@@ -57,6 +57,8 @@ CASES = {
     "forward_plain_backward_clustered": (20, [256, 256], lambda: synth.lattice_graph((10, 10, 10)), 10 ** 9),
     "narrow_layers": (8, [64, 128, 32], lambda: synth.geometric_graph(1800, 8, 4), 0),                 # nothing 256 wide
     "one_layer": (20, [], lambda: synth.lattice_graph((8, 8, 8)), 0),
+    # a 320-wide intermediate is past what the chained launches take: the un-chained GEMMs in the middle of a stack
+    "unchained_wide": (8, [320, 64], lambda: synth.geometric_graph(1500, 8, 4), 0),
 }
 
 
@@ -153,20 +155,20 @@ def test_stack_entry_points_reject_bad_arguments():
     lib = gts._lib.load()
     widths = (ctypes.c_int64 * 3)(20, 256, 4)
     offsets = (ctypes.c_int64 * 10)()
-    assert lib.gts_sage_pool_stack_fwd_arena(1000, widths, 2, 1, 1, 7, offsets) > 0
+    assert lib.gts_sage_pool_stack_fwd_arena(1000, widths, 2, 1, 1, 1, offsets) > 0
     assert offsets[1] > 0 and offsets[5] > 0 and offsets[7] == -1          # winners kept; no bits behind the last layer
-    assert lib.gts_sage_pool_stack_fwd_arena(1000, widths, 2, 0, 1, 7, offsets) > 0 and offsets[1] == -1
+    assert lib.gts_sage_pool_stack_fwd_arena(1000, widths, 2, 0, 1, 1, offsets) > 0 and offsets[1] == -1
     bad = (ctypes.c_int64 * 3)(20, 255, 4)
-    assert lib.gts_sage_pool_stack_fwd_arena(1000, bad, 2, 1, 1, 7, None) == -1      # widths must be multiples of 4
-    assert lib.gts_sage_pool_stack_fwd_arena(1000, widths, 0, 1, 1, 7, None) == -1
-    assert lib.gts_sage_pool_stack_bwd_scratch(1000, widths, 2, 7) > 0
+    assert lib.gts_sage_pool_stack_fwd_arena(1000, bad, 2, 1, 1, 1, None) == -1      # widths must be multiples of 4
+    assert lib.gts_sage_pool_stack_fwd_arena(1000, widths, 0, 1, 1, 1, None) == -1
+    assert lib.gts_sage_pool_stack_bwd_scratch(1000, widths, 2, 1) > 0
     x = torch.zeros(1000, 20, device=DEV)
     table = (ctypes.c_void_p * 10)(*([x.data_ptr()] * 10))
     arena = torch.empty(64, dtype=torch.uint8, device=DEV)
     ip = torch.zeros(1001, dtype=torch.int32, device=DEV)
     code = lib.gts_sage_pool_stack_fwd_f32(ip.data_ptr(), ip.data_ptr(), None, 0, 0, 0, 0, x.data_ptr(), table, 1000, widths, 2,
-                                           1, 1, 7, arena.data_ptr(), 64, None)
+                                           1, 1, 1, arena.data_ptr(), 64, None)
     assert code == -2                                                      # arena too small
     code = lib.gts_sage_pool_stack_fwd_f32(ip.data_ptr(), ip.data_ptr(), None, 0, 0, 0, 0, None, table, 1000, widths, 2,
-                                           1, 1, 7, arena.data_ptr(), 64, None)
+                                           1, 1, 1, arena.data_ptr(), 64, None)
     assert code == -1
