@@ -1,0 +1,276 @@
+// F1: conform a scan to the pipeline's frame (LPS axis order and signs, 1 mm voxels) and carry label volumes
+// back onto the scan's own grid.  What a user otherwise does on the host with np.transpose / np.flip and
+// scipy.ndimage.map_coordinates in front of the reader (data_processing/nifti_io.py:42-57 of the reference).
+//
+// One gather, [C][Z][Y][X] x-fastest in and out.  Every output axis names the input axis it reads and carries
+// three host-computed tables over its own extent: the two input indices a sample lies between and the
+// float64 weight of the second.  The kernel divides nothing and rounds nothing but the final float32.
+//
+//   exact      out = in[idx0 ...], the stored dtype, bit for bit (pure reorientation, and the inverse map);
+//   trilinear  the eight neighbours (idx0 | idx1 per axis), lerped along input x, then y, then z, each lerp
+//              a + (b - a) * t in float64 (the library is built without contraction; t == 0 gives a itself),
+//              one rounding to float32;
+//   nearest    t < 0.5 ? idx0 : idx1 per axis, int16.
+//
+// Memory access.  Whatever the mode, the eight (or one) reads of an output voxel lie on input rows, so the
+// reads of neighbouring voxels ALONG THE INPUT'S x are the coalesced ones:
+//   rows   the output's x reads the input's x: one lane per output voxel in linear order.  Reads and writes
+//          both run along x (ascending, or descending for a flipped x).  An exact copy whose rows are whole
+//          16-byte groups moves 16 bytes per lane, reversed in registers when x is flipped;
+//   tiled  the output's x reads the input's y or z (4 of the 6 permutations): a 64 x 64 tile over (output x,
+//          the output axis that reads input x).  Loading, a wave's lanes run along input x; the finished values
+//          go through LDS; storing, the lanes run along output x.  LDS holds one 32-bit word per value with a
+//          pitch of 65 words: the row writes and the column reads (ds_write_b32 / ds_read_b32, 32 banks per
+//          32-lane group) both touch 32 distinct banks.
+// Table entries are clamped to the input extent before use, so no table can make a read leave the volume.
+#include "gts_common.h"
+
+namespace gts {
+namespace {
+
+constexpr int kModeExact = 0, kModeTrilinear = 1, kModeNearest = 2;
+constexpr int kTile = 64;
+constexpr int kPitch = kTile + 1;
+constexpr int64_t kMaxExtent = 65535;
+
+// Tables and extents ordered by INPUT axis j (0 = x, fastest): which output axis drives it, and that axis'
+// tables.  t is unused (may be NULL) in exact mode, idx1 likewise.
+struct ConformArgs {
+  const int32_t* idx0[3];
+  const int32_t* idx1[3];
+  const double* t[3];
+  int drive[3];  // output axis whose coordinate indexes input axis j's tables
+  int in[3];     // input extents X, Y, Z
+  int out[3];    // output extents OX, OY, OZ
+  int channels;
+};
+
+__device__ __forceinline__ int pick(int axis, int o0, int o1, int o2) { return axis == 0 ? o0 : (axis == 1 ? o1 : o2); }
+__device__ __forceinline__ int clamp_index(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+
+template <typename T>
+struct Lds;  // the 32-bit word a value travels through LDS as
+template <>
+struct Lds<int16_t> {
+  __device__ static uint32_t pack(int16_t v) { return static_cast<uint16_t>(v); }
+  __device__ static int16_t unpack(uint32_t w) { return static_cast<int16_t>(static_cast<uint16_t>(w)); }
+};
+template <>
+struct Lds<float> {
+  __device__ static uint32_t pack(float v) { return __float_as_uint(v); }
+  __device__ static float unpack(uint32_t w) { return __uint_as_float(w); }
+};
+
+// A sample that lies on a voxel (t == 0) IS that voxel: the sign of a -0.0 survives and a non-finite neighbour
+// that carries no weight does not turn the result into a NaN.  For finite values a + (b - a) * 0 is a anyway.
+__device__ __forceinline__ double lerp64(double a, double b, double t) { return t == 0.0 ? a : a + (b - a) * t; }
+
+// The value of output voxel (o0, o1, o2) of channel c.
+template <typename In, typename Out, int kMode>
+__device__ __forceinline__ Out fetch(const In* __restrict__ src, const ConformArgs& p, int c, int o0, int o1, int o2) {
+  const int ix = pick(p.drive[0], o0, o1, o2), iy = pick(p.drive[1], o0, o1, o2), iz = pick(p.drive[2], o0, o1, o2);
+  const int X = p.in[0], Y = p.in[1], Z = p.in[2];
+  const In* vol = src + static_cast<int64_t>(c) * Z * Y * X;
+  if (kMode == kModeTrilinear) {
+    const int x0 = clamp_index(p.idx0[0][ix], X), x1 = clamp_index(p.idx1[0][ix], X);
+    const int y0 = clamp_index(p.idx0[1][iy], Y), y1 = clamp_index(p.idx1[1][iy], Y);
+    const int z0 = clamp_index(p.idx0[2][iz], Z), z1 = clamp_index(p.idx1[2][iz], Z);
+    const double tx = p.t[0][ix], ty = p.t[1][iy], tz = p.t[2][iz];
+    const In* r00 = vol + (static_cast<int64_t>(z0) * Y + y0) * X;
+    const In* r01 = vol + (static_cast<int64_t>(z0) * Y + y1) * X;
+    const In* r10 = vol + (static_cast<int64_t>(z1) * Y + y0) * X;
+    const In* r11 = vol + (static_cast<int64_t>(z1) * Y + y1) * X;
+    const double v00 = lerp64(static_cast<double>(r00[x0]), static_cast<double>(r00[x1]), tx);
+    const double v01 = lerp64(static_cast<double>(r01[x0]), static_cast<double>(r01[x1]), tx);
+    const double v10 = lerp64(static_cast<double>(r10[x0]), static_cast<double>(r10[x1]), tx);
+    const double v11 = lerp64(static_cast<double>(r11[x0]), static_cast<double>(r11[x1]), tx);
+    return static_cast<Out>(static_cast<float>(lerp64(lerp64(v00, v01, ty), lerp64(v10, v11, ty), tz)));
+  }
+  int x, y, z;
+  if (kMode == kModeNearest) {
+    x = p.t[0][ix] < 0.5 ? p.idx0[0][ix] : p.idx1[0][ix];
+    y = p.t[1][iy] < 0.5 ? p.idx0[1][iy] : p.idx1[1][iy];
+    z = p.t[2][iz] < 0.5 ? p.idx0[2][iz] : p.idx1[2][iz];
+  } else {
+    x = p.idx0[0][ix];
+    y = p.idx0[1][iy];
+    z = p.idx0[2][iz];
+  }
+  return static_cast<Out>(vol[(static_cast<int64_t>(clamp_index(z, Z)) * Y + clamp_index(y, Y)) * X + clamp_index(x, X)]);
+}
+
+// rows: one lane per output voxel, linear order.
+template <typename In, typename Out, int kMode>
+__global__ __launch_bounds__(kBlock) void conform_rows_kernel(const In* __restrict__ src, Out* __restrict__ dst,
+                                                              const ConformArgs p, int64_t total) {
+  const int64_t i = int64_t{blockIdx.x} * kBlock + threadIdx.x;
+  if (i >= total) return;
+  const int o0 = static_cast<int>(i % p.out[0]);
+  const int64_t row = i / p.out[0];
+  const int o1 = static_cast<int>(row % p.out[1]);
+  const int64_t plane = row / p.out[1];
+  const int o2 = static_cast<int>(plane % p.out[2]);
+  dst[i] = fetch<In, Out, kMode>(src, p, static_cast<int>(plane / p.out[2]), o0, o1, o2);
+}
+
+// rows, exact, 16 bytes per lane: the host side has checked that the output's x reads the input's x, that both
+// row lengths are whole groups of kVec values and that both volumes start on a 16-byte boundary.  A group whose
+// x entries are the kVec consecutive indices of one aligned input group, ascending or descending, moves as one
+// load and one store; any other group falls back to kVec single reads.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void conform_rows_wide_kernel(const T* __restrict__ src, T* __restrict__ dst,
+                                                                   const ConformArgs p, int64_t groups) {
+  constexpr int kVec = 16 / static_cast<int>(sizeof(T));
+  typedef T Group __attribute__((ext_vector_type(kVec)));
+  const int64_t g = int64_t{blockIdx.x} * kBlock + threadIdx.x;
+  if (g >= groups) return;
+  const int per_row = p.out[0] / kVec;
+  const int o0 = static_cast<int>(g % per_row) * kVec;
+  const int64_t row = g / per_row;
+  const int o1 = static_cast<int>(row % p.out[1]);
+  const int64_t plane = row / p.out[1];
+  const int o2 = static_cast<int>(plane % p.out[2]);
+  const int c = static_cast<int>(plane / p.out[2]);
+  const int X = p.in[0], Y = p.in[1], Z = p.in[2];
+  const int iy = pick(p.drive[1], o0, o1, o2), iz = pick(p.drive[2], o0, o1, o2);
+  const int y = clamp_index(p.idx0[1][iy], Y), z = clamp_index(p.idx0[2][iz], Z);
+  const T* in_row = src + ((static_cast<int64_t>(c) * Z + z) * Y + y) * X;
+  int xs[kVec];
+  bool up = true, down = true;
+#pragma unroll
+  for (int k = 0; k < kVec; ++k) {
+    xs[k] = clamp_index(p.idx0[0][o0 + k], X);
+    up = up && xs[k] == xs[0] + k;
+    down = down && xs[k] == xs[0] - k;
+  }
+  Group v;
+  if (up && xs[0] % kVec == 0) {
+    v = *reinterpret_cast<const Group*>(in_row + xs[0]);
+  } else if (down && xs[kVec - 1] % kVec == 0) {
+    const Group w = *reinterpret_cast<const Group*>(in_row + xs[kVec - 1]);
+#pragma unroll
+    for (int k = 0; k < kVec; ++k) v[k] = w[kVec - 1 - k];
+  } else {
+#pragma unroll
+    for (int k = 0; k < kVec; ++k) v[k] = in_row[xs[k]];
+  }
+  *reinterpret_cast<Group*>(dst + g * kVec) = v;
+}
+
+// tiled: the output's x reads input y or z; output axis ka (1 or 2) reads input x, kb is the third one.
+// Block = one 64 x 64 tile over (output x, output ka) at one (kb, channel).
+template <typename In, typename Out, int kMode>
+__global__ __launch_bounds__(kBlock) void conform_tiled_kernel(const In* __restrict__ src, Out* __restrict__ dst,
+                                                               const ConformArgs p, int ka, int tiles_x, int tiles_a) {
+  __shared__ uint32_t tile[kTile * kPitch];
+  int64_t b = blockIdx.x;
+  const int tx0 = static_cast<int>(b % tiles_x) * kTile;
+  b /= tiles_x;
+  const int ta0 = static_cast<int>(b % tiles_a) * kTile;
+  b /= tiles_a;
+  const int OX = p.out[0], OA = ka == 1 ? p.out[1] : p.out[2], OB = ka == 1 ? p.out[2] : p.out[1];
+  const int ob = static_cast<int>(b % OB);
+  const int c = static_cast<int>(b / OB);
+  const int lane = threadIdx.x & (kTile - 1), wave_row = threadIdx.x / kTile;
+  // load: lanes along output axis ka (= input x), rows along output x
+  {
+    const int oa = ta0 + lane;
+    for (int r = wave_row; r < kTile; r += kBlock / kTile) {
+      const int ox = tx0 + r;
+      if (oa < OA && ox < OX) {
+        const int o1 = ka == 1 ? oa : ob, o2 = ka == 1 ? ob : oa;
+        tile[r * kPitch + lane] = Lds<Out>::pack(fetch<In, Out, kMode>(src, p, c, ox, o1, o2));
+      }
+    }
+  }
+  __syncthreads();
+  // store: lanes along output x, rows along output axis ka
+  {
+    const int ox = tx0 + lane;
+    for (int r = wave_row; r < kTile; r += kBlock / kTile) {
+      const int oa = ta0 + r;
+      if (oa < OA && ox < OX) {
+        const int o1 = ka == 1 ? oa : ob, o2 = ka == 1 ? ob : oa;
+        const int64_t at = ((static_cast<int64_t>(c) * p.out[2] + o2) * p.out[1] + o1) * OX + ox;
+        dst[at] = Lds<Out>::unpack(tile[lane * kPitch + r]);
+      }
+    }
+  }
+}
+
+template <typename In, typename Out, int kMode>
+int launch(const void* src, void* dst, const ConformArgs& p, hipStream_t st) {
+  const In* s = static_cast<const In*>(src);
+  Out* d = static_cast<Out*>(dst);
+  const int64_t per_channel = int64_t{p.out[0]} * p.out[1] * p.out[2];
+  const int64_t total = per_channel * p.channels;
+  if (p.drive[0] == 0) {
+    constexpr int kVec = 16 / static_cast<int>(sizeof(In));
+    const bool wide = kMode == kModeExact && p.in[0] % kVec == 0 && p.out[0] % kVec == 0 &&
+                      reinterpret_cast<uintptr_t>(src) % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 16 == 0;
+    if (wide) {
+      const int64_t groups = total / kVec;
+      conform_rows_wide_kernel<In><<<static_cast<unsigned>((groups + kBlock - 1) / kBlock), kBlock, 0, st>>>(
+          s, reinterpret_cast<In*>(d), p, groups);
+    } else {
+      conform_rows_kernel<In, Out, kMode><<<static_cast<unsigned>((total + kBlock - 1) / kBlock), kBlock, 0, st>>>(
+          s, d, p, total);
+    }
+    return launch_status();
+  }
+  const int ka = p.drive[0], kb = 3 - ka;
+  const int tiles_x = (p.out[0] + kTile - 1) / kTile, tiles_a = (p.out[ka] + kTile - 1) / kTile;
+  const int64_t blocks = int64_t{tiles_x} * tiles_a * p.out[kb] * p.channels;  // <= total < 2^31
+  conform_tiled_kernel<In, Out, kMode><<<static_cast<unsigned>(blocks), kBlock, 0, st>>>(s, d, p, ka, tiles_x, tiles_a);
+  return launch_status();
+}
+
+}  // namespace
+}  // namespace gts
+
+extern "C" int32_t gts_conform_gather(const void* src, int32_t dtype, int64_t C, int64_t X, int64_t Y, int64_t Z,
+                                      int32_t axis0, int32_t axis1, int32_t axis2, int64_t OX, int64_t OY, int64_t OZ,
+                                      const int32_t* idx0, const int32_t* idx1, const double* t, int32_t mode, void* dst,
+                                      void* stream) {
+  using namespace gts;
+  if (mode != kModeExact && mode != kModeTrilinear && mode != kModeNearest) return GTS_ERR_ARGKIND;
+  if (dtype != 4 && dtype != 16) return GTS_ERR_ARGKIND;
+  if (mode == kModeNearest && dtype != 4) return GTS_ERR_ARGKIND;
+  if (!src || !dst || !idx0) return GTS_ERR_NULL;
+  if (mode != kModeExact && (!idx1 || !t)) return GTS_ERR_NULL;
+  if (C < 0) return GTS_ERR_SHAPE;
+  const int64_t in_dims[3] = {X, Y, Z}, out_dims[3] = {OX, OY, OZ};
+  for (int k = 0; k < 3; ++k)
+    if (in_dims[k] <= 0 || out_dims[k] <= 0 || in_dims[k] > kMaxExtent || out_dims[k] > kMaxExtent) return GTS_ERR_SHAPE;
+  const int32_t axes[3] = {axis0, axis1, axis2};
+  int seen = 0;
+  for (int k = 0; k < 3; ++k) {
+    if (axes[k] < 0 || axes[k] > 2) return GTS_ERR_ARGKIND;
+    seen |= 1 << axes[k];
+  }
+  if (seen != 7) return GTS_ERR_ARGKIND;
+  if (C == 0) return GTS_OK;
+  constexpr int64_t kLimit = int64_t{1} << 31;
+  if (X * Y * Z >= kLimit || OX * OY * OZ >= kLimit || C >= kLimit) return GTS_ERR_SHAPE;  // extents <= 65535: no overflow
+  if (X * Y * Z * C >= kLimit || OX * OY * OZ * C >= kLimit) return GTS_ERR_SHAPE;
+  ConformArgs p;
+  int64_t at = 0;
+  for (int k = 0; k < 3; ++k) {  // output axis k reads input axis axes[k]; its tables start at `at`
+    const int j = axes[k];
+    p.idx0[j] = idx0 + at;
+    p.idx1[j] = idx1 ? idx1 + at : nullptr;
+    p.t[j] = t ? t + at : nullptr;
+    p.drive[j] = k;
+    p.in[k] = static_cast<int>(in_dims[k]);
+    p.out[k] = static_cast<int>(out_dims[k]);
+    at += out_dims[k];
+  }
+  p.channels = static_cast<int>(C);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (mode == kModeNearest) return launch<int16_t, int16_t, kModeNearest>(src, dst, p, st);
+  if (mode == kModeTrilinear)
+    return dtype == 4 ? launch<int16_t, float, kModeTrilinear>(src, dst, p, st)
+                      : launch<float, float, kModeTrilinear>(src, dst, p, st);
+  return dtype == 4 ? launch<int16_t, int16_t, kModeExact>(src, dst, p, st)
+                    : launch<float, float, kModeExact>(src, dst, p, st);
+}

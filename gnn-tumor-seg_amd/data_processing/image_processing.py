@@ -14,6 +14,14 @@ def uncrop_to_brats_size(crop, voxel_preds):
     return full
 
 
+def uncrop_to_shape(crop, voxel_preds, shape):
+    """uncrop_to_brats_size for a volume of any shape: the cropped predictions pasted into a zero (healthy)
+    int16 volume of `shape` (a scan conformed from another geometry has its own extents)."""
+    full = np.zeros(tuple(int(n) for n in shape), dtype=np.int16)
+    full[crop] = voxel_preds
+    return full
+
+
 def _any_along_other_axes(mask):
     return np.ix_(mask.any(axis=(1, 2)), mask.any(axis=(0, 2)), mask.any(axis=(0, 1)))
 

@@ -76,8 +76,10 @@ def save_as_nifti(img, fp, affine=BRATS_AFFINE):
     if not 1 <= img.ndim <= 7:
         raise ValueError("NIfTI supports 1 to 7 dimensions")
     dim = [img.ndim] + list(img.shape) + [1] * (7 - img.ndim)
+    affine = np.asarray(affine, dtype=np.float64)
     pixdim = [1.0] * 8
     pixdim[0] = -1.0 if np.linalg.det(affine[:3, :3]) < 0 else 1.0
+    pixdim[1:4] = [float(n) for n in np.sqrt((affine[:3, :3] ** 2).sum(axis=0))]   # voxel spacings: the column norms
     hdr = bytearray(348)
     struct.pack_into("<i", hdr, 0, 348)
     hdr[38:39] = b"r"                            # `regular`: unused by NIfTI-1, set by Analyze-lineage writers
@@ -116,6 +118,45 @@ def read_nifti(fp, data_type):
         if slope != 0.0 and not np.isnan(slope):
             data = data * slope + inter
     return np.array(data, dtype=data_type)
+
+
+def _quaternion_rotation(b, c, d):
+    """The rotation matrix of the unit quaternion (a, b, c, d), a = sqrt(1 - b^2 - c^2 - d^2) >= 0 (nifti1.h
+    "METHOD 2"): the inverse of _quaternion_bcd."""
+    a = np.sqrt(max(0.0, 1.0 - (b * b + c * c + d * d)))
+    return np.array([
+        [a * a + b * b - c * c - d * d, 2 * b * c - 2 * a * d, 2 * b * d + 2 * a * c],
+        [2 * b * c + 2 * a * d, a * a + c * c - b * b - d * d, 2 * c * d - 2 * a * b],
+        [2 * b * d - 2 * a * c, 2 * c * d + 2 * a * b, a * a + d * d - c * c - b * b],
+    ])
+
+
+def read_affine(fp):
+    """(affine, source): the 4x4 float64 voxel-to-world transform of a NIfTI-1 file and the header field it came
+    from, by the specification's order of preference: "sform" (sform_code > 0: the srow_* rows), else "qform"
+    (qform_code > 0: quaternion, pixdim[1..3], qfac = pixdim[0] with 0 counting as +1, and the qoffsets), else
+    "pixdim" (diag(pixdim[1..3]), origin 0)."""
+    with _open(fp, "rb") as f:
+        raw = f.read(348)
+    if len(raw) < 348:
+        raise ValueError(f"{fp}: shorter than a NIfTI-1 header")
+    endian = "<" if struct.unpack_from("<i", raw, 0)[0] == 348 else ">"
+    pixdim = struct.unpack_from(endian + "8f", raw, 76)
+    qform_code, sform_code = struct.unpack_from(endian + "hh", raw, 252)
+    affine = np.eye(4)
+    if sform_code > 0:
+        for r in range(3):
+            affine[r] = struct.unpack_from(endian + "4f", raw, 280 + 16 * r)
+        return affine, "sform"
+    if qform_code > 0:
+        b, c, d = (float(v) for v in struct.unpack_from(endian + "3f", raw, 256))
+        scale = np.array(pixdim[1:4], dtype=np.float64)
+        scale[2] *= -1.0 if pixdim[0] < 0 else 1.0
+        affine[:3, :3] = _quaternion_rotation(b, c, d) * scale
+        affine[:3, 3] = struct.unpack_from(endian + "3f", raw, 268)
+        return affine, "qform"
+    affine[:3, :3] = np.diag(np.array(pixdim[1:4], dtype=np.float64))
+    return affine, "pixdim"
 
 
 RAW_DTYPES = (np.dtype(np.int16), np.dtype(np.float32))

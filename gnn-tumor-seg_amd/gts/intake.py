@@ -136,16 +136,23 @@ def standardize(src, shape, lists, sizes, top, mean, std):
 def prepare_scan(volumes, mean, std, q=QUANTILE, timer=None):
     """Raw scan -> (image [cx, cy, cz, 4] float32 on the device, crop np.ix_ triple, tops float32 [4]).
 
-    volumes: four [X, Y, Z] arrays (as nifti_io.read_nifti_raw returns them) or the host tensor of
-    stage_scan.  Equal to determine_brain_crop, normalize_img's quantiles and
+    volumes: four [X, Y, Z] arrays (as nifti_io.read_nifti_raw returns them), the host tensor of
+    stage_scan, or a tensor of that layout already on the device ([4, Z, Y, X] int16 or float32, e.g. what
+    gts.conform.conform_scan returns), which is used where it lies.  Equal to determine_brain_crop, normalize_img's quantiles and
     standardize_img(normalize_img(image[crop]), mean, std) of the stacked float32 image.  A scan
     with a non-finite voxel, or without any voxel above 0.01, raises ValueError.
     timer(name) is called after each stage (host clock hooks for the measurement tool)."""
     tick = timer or (lambda name: None)
     host = volumes if isinstance(volumes, torch.Tensor) else stage_scan(volumes)
+    if host.dim() != 4 or host.shape[0] != CHANNELS or host.dtype not in (torch.int16, torch.float32):
+        raise ValueError(f"a staged scan is an int16 or float32 tensor [{CHANNELS}, Z, Y, X], got {host.dtype} "
+                         f"{tuple(host.shape)}")
     shape = tuple(int(d) for d in host.shape[1:][::-1])
-    dev = _device()
-    src = host.to(dev, non_blocking=True)
+    if host.is_cuda:
+        src = host.contiguous()
+    else:
+        src = host.to(_device(), non_blocking=True)
+    dev = src.device
     tick("upload")
     masks, bad = occupancy(src, shape)
     tick("I1")

@@ -15,6 +15,7 @@ A scan that raises is reported and skipped; the exit status is 1 when any scan w
 
     python -m scripts.segment_scans -d INPUT -o OUT -g GNN.pt [-c CNN.pt] [-m GSpool] [-n 15000 -b 0.5 -k 10]
                                     [--min_component_voxels N --connectivity {6,26} --min_enhancing_voxels T]
+                                    [--conform]
 
 --min_component_voxels N drops connected components of the predicted whole tumour with fewer than N voxels,
 --min_enhancing_voxels T relabels the enhancing tumour to necrotic core when fewer than T voxels of it remain
@@ -25,6 +26,14 @@ carries the counts.
 --stats STATS.json standardizes with the values of a file written by scripts.compute_dataset_stats (the one the
 dataset the weights were trained on was preprocessed with) instead of the BraTS-2021 constants.  Explicit
 only: a standardization.json that happens to lie next to the weights is not picked up.
+
+--conform reads each modality's affine from its NIfTI header and brings the scan into the frame the nets, SLIC and
+the standardization constants were built for (LPS axis order and signs, 1 mm voxels: BRATS_AFFINE's frame) on the
+device before the intake (gts.conform: permute, flip, trilinear resampling); the labels go back onto the scan's own
+grid (nearest neighbour) and OUT/{id}.nii.gz has the scan's own shape and the first modality's own affine.  The
+clean-up flags then count voxels of 1 mm^3.  The modalities of a scan must share one shape and agree in their
+affines to 1e-3, else the scan is skipped.  Without the flag headers are not read: scans are taken as BraTS-shaped
+LPS 1 mm volumes and written with the BraTS affine, as before.
 """
 import argparse
 import os
@@ -39,9 +48,9 @@ if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
 from data_processing import nifti_io, standardization  # noqa: E402
-from data_processing.image_processing import uncrop_to_brats_size  # noqa: E402
+from data_processing.image_processing import uncrop_to_brats_size, uncrop_to_shape  # noqa: E402
 from data_processing.labels import INTERNAL_TO_BRATS  # noqa: E402
-from gts import graphgen, intake, ops  # noqa: E402
+from gts import conform, graphgen, intake, ops  # noqa: E402
 from scripts import cleanup as cleanup_flags  # noqa: E402
 from scripts import preprocess_dataset as prep  # noqa: E402
 
@@ -69,6 +78,9 @@ def build_parser():
     parser.add_argument("--stats", default=None, metavar="STATS.json",
                         help="standardization statistics file of scripts.compute_dataset_stats "
                              "(default: the BraTS-2021 constants)")
+    parser.add_argument("--conform", action="store_true",
+                        help="read each scan's orientation and voxel spacing from its headers, segment it in the "
+                             "LPS 1 mm frame and write the labels on the scan's own grid with its own affine")
     return cleanup_flags.add_flags(parser)
 
 
@@ -99,6 +111,7 @@ class Segmenter:
         self.device = _device()
         self.k = args.num_neighbors or 0
         self.cleanup = cleanup_flags.from_args(args)       # None with the flags at their defaults
+        self.conform = bool(getattr(args, "conform", False))
         if getattr(args, "stats", None):
             self.mean, self.std = standardization.load_stats(os.path.expanduser(args.stats), args.modality_extensions)
         else:
@@ -115,12 +128,25 @@ class Segmenter:
         self.relabel = torch.from_numpy(INTERNAL_TO_BRATS).to(self.device)
 
     def load(self, folder):
-        """Host stage: decode the modalities and stage them for the upload."""
-        return intake.stage_scan(nifti_io.read_in_patient_sample_raw(folder, self.args.modality_extensions))
+        """Host stage: decode the modalities and stage them for the upload.  With --conform: (staged volumes, the
+        conform plan of their headers' geometry, the first modality's affine)."""
+        if not self.conform:
+            return intake.stage_scan(nifti_io.read_in_patient_sample_raw(folder, self.args.modality_extensions))
+        paths = nifti_io.find_modality_files(folder, self.args.modality_extensions)
+        volumes = [nifti_io.read_nifti_raw(p) for p in paths]
+        affines = [nifti_io.read_affine(p)[0] for p in paths]
+        plan = conform.plan_for_modalities(affines, [v.shape for v in volumes])
+        return intake.stage_scan(volumes), plan, affines[0]
 
     def segment(self, staged, timer=None):
-        """Device stage: int16 label volume at BraTS size in BraTS coding."""
+        """Device stage: int16 label volume in BraTS coding, at BraTS size; with --conform (staged is load's
+        triple) on the scan's own grid."""
         tick = timer or (lambda name: None)
+        plan = None
+        if self.conform:
+            staged, plan, _ = staged
+            staged = conform.conform_scan(staged.to(self.device, non_blocking=True), plan)
+            tick("conform")
         image, crop, _ = intake.prepare_scan(staged, self.mean, self.std, timer=tick)
         res = graphgen.build_graph(image, None, self.args.num_nodes, self.args.boxiness, self.k, keep_on_device=True)
         graph = graphgen.graph_from_edges(res["edges"], res["feats"].shape[0])
@@ -143,11 +169,18 @@ class Segmenter:
                 pred = self.cleanup(pred)        # cropped volume, BraTS coding, still on the device
             pred = pred.cpu().numpy()
         tick("predict")
-        return uncrop_to_brats_size(crop, pred)
+        if plan is None:
+            return uncrop_to_brats_size(crop, pred)
+        full = uncrop_to_shape(crop, pred, plan.out_shape)
+        if plan.is_identity:
+            return full
+        back = conform.unconform_labels(torch.from_numpy(full).to(self.device), plan, z_fastest=True)
+        tick("unconform")
+        return back.cpu().numpy().T          # [X, Y, Z], x fastest: the order the file stores
 
-    def store(self, scan_id, volume):
+    def store(self, scan_id, volume, affine=nifti_io.BRATS_AFFINE):
         """Host stage: gzip NIfTI encode."""
-        nifti_io.save_as_nifti(volume, os.path.join(self.output_dir, scan_id + ".nii.gz"))
+        nifti_io.save_as_nifti(volume, os.path.join(self.output_dir, scan_id + ".nii.gz"), affine)
 
     def run(self, scans, output_dir):
         """Segment every scan of {id: folder}; returns the ids that were skipped."""
@@ -161,13 +194,17 @@ class Segmenter:
                 if i + READ_AHEAD < len(ids):
                     pending[i + READ_AHEAD] = pool.submit(self.load, scans[ids[i + READ_AHEAD]])
                 try:
-                    volume = self.segment(pending.pop(i).result())
+                    staged = pending.pop(i).result()
+                    volume = self.segment(staged)
                     note = f" ({self.cleanup.report()})" if self.cleanup is not None else ""
+                    if self.conform:
+                        note += f" ({staged[1].describe()})"
                 except Exception as exc:
                     print(f"{scan_id}: skipped ({exc!r})")
                     failed.append(scan_id)
                     continue
-                writes.append((scan_id, note, pool.submit(self.store, scan_id, volume)))
+                affine = staged[2] if self.conform else nifti_io.BRATS_AFFINE
+                writes.append((scan_id, note, pool.submit(self.store, scan_id, volume, affine)))
             for scan_id, note, job in writes:
                 try:
                     job.result()

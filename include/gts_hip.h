@@ -756,6 +756,28 @@ int32_t gts_dataset_stats_moments(const void* src, int32_t dtype, int64_t X, int
                                   const float* top, double* out, void* workspace, int64_t workspace_bytes,
                                   void* stream);
 
+/* ---- F1: conform a scan to the pipeline's frame, and labels back onto the scan's grid ----------------------
+ * The reference reads and writes volumes as they are stored (data_processing/nifti_io.py:42-57, nibabel) and
+ * so only serves LPS 1 mm scans; this gather is the reorientation / resampling step in front of the intake.
+ * src: [C][Z][Y][X] (x fastest), dtype by its NIfTI code 4 (int16) or 16 (float32), else GTS_ERR_ARGKIND.
+ * dst: [C][OZ][OY][OX] (x fastest).  Output axis k (0 = x) reads input axis axis_k; (axis0, axis1, axis2) must
+ * be a permutation of 0..2, else GTS_ERR_ARGKIND.  idx0, idx1 (device int32) and t (device float64) hold
+ * OX + OY + OZ entries each: the tables of output axis x, then y, then z.  For output coordinate i of an axis,
+ * idx0[i] and idx1[i] are the two indices along the input axis it reads and t[i] the weight of the second;
+ * entries are clamped to the input extent before use.
+ * mode 0 (exact): dst = src[idx0 ...] in src's dtype, bit for bit; idx1 and t may be NULL.
+ * mode 1 (trilinear): dst float32 = the eight neighbours lerped along input x, then y, then z, each lerp
+ *   a + (b - a) * t in float64 without contraction (t == 0 gives a itself, whatever b is), rounded to float32
+ *   once at the end.
+ * mode 2 (nearest): int16 only (else GTS_ERR_ARGKIND); per axis t < 0.5 ? idx0 : idx1, a tie takes idx1.
+ * Another mode: GTS_ERR_ARGKIND.  Every extent in [1, 65535] and C * X * Y * Z, C * OX * OY * OZ < 2^31, C >= 0,
+ * else GTS_ERR_SHAPE; C == 0 returns GTS_OK without touching the device.  Nothing is launched for a rejected
+ * argument.  Reads and writes both run along their own fastest axes (a padded LDS tile when the fastest axis
+ * moves). */
+int32_t gts_conform_gather(const void* src, int32_t dtype, int64_t C, int64_t X, int64_t Y, int64_t Z, int32_t axis0,
+                           int32_t axis1, int32_t axis2, int64_t OX, int64_t OY, int64_t OZ, const int32_t* idx0,
+                           const int32_t* idx1, const double* t, int32_t mode, void* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
