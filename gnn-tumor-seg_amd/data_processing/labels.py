@@ -24,3 +24,14 @@ def swap_labels_from_brats(label_data):
 def swap_labels_to_brats(label_data):
     _check(label_data, [0, 1, 2, 3])
     return INTERNAL_TO_BRATS[np.asarray(label_data, dtype=np.int64)]
+
+
+def swap_labels_from_brats_any(label_data):
+    """swap_labels_from_brats for a file in either BraTS convention: {0, 1, 2, 4}, or the 2023 challenge's
+    {0, 1, 2, 3} (3 and 4 both mean enhancing tumour).  A volume holding both 3 and 4, or any other value, is
+    refused."""
+    values = np.unique(label_data)
+    if np.setdiff1d(values, [0, 1, 2, 3, 4]).size or (3 in values and 4 in values):
+        raise RuntimeError(f"unexpected labels {values.tolist()}: neither {{0, 1, 2, 4}} nor {{0, 1, 2, 3}}")
+    label_data = np.asarray(label_data)
+    return swap_labels_from_brats(np.where(label_data == 3, 4, label_data))

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GTS_LIB_PATH: another build of the same library (A/B runs of two builds in one session, tools/); the default is the in-tree build
 LIB_PATH = os.environ.get("GTS_LIB_PATH") or os.path.join(_HERE, "libgts_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "gts_hip.h")
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -108,6 +108,11 @@ SIGNATURES = {
     "gts_components_workspace": [_i64, _i64, _i64],
     "gts_components_roots_i16": [_p, _i64, _i64, _i64, _i32, _p, _p, _i64, _p],
     "gts_components_filter_i16": [_p, _i64, _i64, _i64, _i32, _i64, _i32, _i64, _i32, _p, _p, _p, _i64, _p],
+    "gts_lesionwise_workspace": [_i64, _i64, _i64],
+    "gts_lesionwise_table_ints": [_i64, _i64, _i64],
+    "gts_lesionwise_dilate_i16": [_p, _i64, _i64, _i64, _i32, _i32, _p, _p, _i64, _p],
+    "gts_lesionwise_tables_i16": [_p, _p, _p, _i64, _i64, _i64, _i32, _p, _i64, _p, _i64, _p],
+    "gts_lesionwise_masks_i16": [_p, _p, _p, _i64, _i64, _i64, _i32, _i32, _p, _i64, _p, _p, _p, _p],
     "gts_intake_occupancy": [_p, _i32, _i64, _i64, _i64, _p, _p, _p, _p, _p],
     "gts_intake_select_workspace": [],
     "gts_intake_order_stats": [_p, _i32, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _i64, _p],
@@ -127,7 +132,7 @@ _RESTYPE = {"gts_error_string": ctypes.c_char_p, "gts_linear_bwd_weight_workspac
             "gts_conv3d_fwd_workspace": _i64, "gts_conv3d_bwd_data_workspace": _i64,
             "gts_conv3d_bwd_weight_workspace": _i64, "gts_hd95_workspace": _i64,
             "gts_intake_select_workspace": _i64, "gts_dataset_stats_workspace": _i64,
-            "gts_components_workspace": _i64}
+            "gts_components_workspace": _i64, "gts_lesionwise_workspace": _i64, "gts_lesionwise_table_ints": _i64}
 
 COLLATE_MAX_SCHEDULES = 6      # GTS_COLLATE_MAX_SCHEDULES
 

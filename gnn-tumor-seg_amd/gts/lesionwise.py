@@ -1,0 +1,235 @@
+"""Lesion-wise Dice and HD95 of a written prediction against its ground truth, on the device (L1-L3,
+csrc/gts_lesionwise.hip; definition and deviations from the BraTS 2023 script: DESIGN.md 4o).
+
+Per region (WT, CT, ET): the truth mask G is dilated (L1), the 26-connected components of the dilated mask D
+are the lesions and those of the predicted mask P the predicted components (C1-C3); one pass (L2) gives each
+lesion's volume, true positives and box, each component's size and box, and the (component, lesion) pairs that
+touch.  The tables come to the host in one copy; per scored lesion the masks M_k and G_k are written over the
+lesion's box (L3) and go through the HD95 kernels (H1-H5).  The float arithmetic is one division per lesion,
+gts.metrics.percentile95_from_order_stats, and sequential float64 sums in lesion order.
+
+Labels are internal: 0 healthy, 1 edema, 2 NET, 3 ET.  Everything runs on the current stream.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib, metrics
+from ._lib import check, current_stream, ptr, require_device
+
+REGIONS = ("WT", "CT", "ET")
+DILATIONS = (0, 1, 2, 3)
+PENALTY_HD95 = 374.0         # HD95 of a missed lesion and of a false-positive component
+ROW_INTS = 9                 # root | count | tp | box (gts_lesionwise_tables_i16)
+FIRST_COPY_INTS = 1 << 14    # the tables of a real prediction fit here; a longer block takes a second copy
+
+
+def _region_index(region):
+    if region in REGIONS:
+        return REGIONS.index(region)
+    if isinstance(region, int) and not isinstance(region, bool) and 0 <= region < 3:
+        return region
+    raise _lib.GtsError(f"lesionwise: region {region!r} (one of {REGIONS} or 0..2)")
+
+
+def _volume(labels, what):
+    if not isinstance(labels, torch.Tensor):
+        raise _lib.GtsError(f"{what} takes torch tensors")
+    if labels.dtype != torch.int16:
+        raise _lib.GtsError(f"{what} takes int16 labels")
+    if labels.dim() != 3:
+        raise _lib.GtsError(f"{what} takes [X, Y, Z] volumes, got shape {tuple(labels.shape)}")
+    if labels.numel() == 0:
+        raise _lib.GtsError(f"{what}: empty volume")
+    if not labels.is_cuda:
+        require_device(labels)          # raises: there is no CPU route
+    return labels.contiguous()
+
+
+def _pair(pred, truth, what):
+    pred, truth = _volume(pred, what), _volume(truth, what)
+    if pred.shape != truth.shape:
+        raise _lib.GtsError(f"{what}: shapes {tuple(pred.shape)} and {tuple(truth.shape)} differ")
+    require_device(pred, truth)
+    return pred, truth
+
+
+def _dilation(dilation, what):
+    if isinstance(dilation, bool) or dilation not in DILATIONS:
+        raise _lib.GtsError(f"{what}: dilation {dilation!r} (one of {DILATIONS})")
+    return int(dilation)
+
+
+def _workspace(lib, labels, what):
+    x, y, z = labels.shape
+    size = lib.gts_lesionwise_workspace(x, y, z)
+    if size <= 0:
+        raise _lib.GtsError(f"{what}: volume {x}x{y}x{z} is outside the kernels' limits")
+    return torch.empty(size, dtype=torch.uint8, device=labels.device), size
+
+
+def _dilate(lib, labels, region, dilation, workspace, size):
+    x, y, z = labels.shape
+    out = torch.empty_like(labels)
+    check(lib.gts_lesionwise_dilate_i16(ptr(labels), x, y, z, region, dilation, ptr(out), ptr(workspace), size,
+                                        current_stream()), "gts_lesionwise_dilate_i16")
+    return out
+
+
+def _roots(lib, mask):
+    x, y, z = mask.shape
+    size = lib.gts_components_workspace(x, y, z)
+    workspace = torch.empty(size, dtype=torch.uint8, device=mask.device)
+    roots = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
+    check(lib.gts_components_roots_i16(ptr(mask), x, y, z, 26, ptr(roots), ptr(workspace), size, current_stream()),
+          "gts_components_roots_i16")
+    return roots
+
+
+def dilate_region(labels, region, dilation=3):
+    """int16 0 / 1 tensor of labels' shape: scipy's binary_dilation(region mask of labels,
+    generate_binary_structure(3, 2), iterations=dilation), clipped at the volume.  labels: int16 CUDA tensor
+    [X, Y, Z] of internal labels; region "WT", "CT" or "ET" (or 0..2); dilation 0..3."""
+    labels = _volume(labels, "dilate_region")
+    region, dilation = _region_index(region), _dilation(dilation, "dilate_region")
+    lib = _lib.load()
+    workspace, size = _workspace(lib, labels, "dilate_region")
+    return _dilate(lib, labels, region, dilation, workspace, size)
+
+
+def _box(row, shape):
+    """(begin, end) per axis of a table row's box."""
+    return [(shape[a] - int(row[4 + 2 * a]), int(row[3 + 2 * a])) for a in range(3)]
+
+
+class _RegionState:
+    """What one region's device pass leaves for the per-lesion masks."""
+
+    def __init__(self, lib, pred, truth, region, dilation):
+        what = "lesion_tables"
+        self.lib, self.truth, self.region, self.shape = lib, truth, region, tuple(truth.shape)
+        x, y, z = self.shape
+        workspace, size = _workspace(lib, truth, what)
+        self.roots_p = _roots(lib, _dilate(lib, pred, region, 0, workspace, size))
+        self.roots_d = _roots(lib, _dilate(lib, truth, region, dilation, workspace, size))
+        ints = lib.gts_lesionwise_table_ints(x, y, z)
+        block = torch.empty(ints, dtype=torch.int32, device=truth.device)
+        check(lib.gts_lesionwise_tables_i16(ptr(truth), ptr(self.roots_p), ptr(self.roots_d), x, y, z, region,
+                                            ptr(block), ints, ptr(workspace), size, current_stream()),
+              "gts_lesionwise_tables_i16")
+        head = block[:min(ints, FIRST_COPY_INTS)].cpu().numpy()
+        n_l, n_c, n_p = (int(v) for v in head[:3])
+        total = 4 + ROW_INTS * (n_l + n_c) + 2 * n_p
+        if total > head.size:
+            head = np.concatenate([head, block[head.size:total].cpu().numpy()])
+        rows = head[4:4 + ROW_INTS * (n_l + n_c)].reshape(n_l + n_c, ROW_INTS).astype(np.int64)
+        lesions, comps = rows[:n_l], rows[n_l:]
+        self.lesions = lesions[np.argsort(lesions[:, 0])]          # scipy's label order: by smallest index
+        self.comps = comps[np.argsort(comps[:, 0])]
+        pairs = head[4 + ROW_INTS * (n_l + n_c):total].reshape(n_p, 2).astype(np.int64)
+        self.pairs = np.unique(pairs, axis=0) if n_p else pairs      # (component root, lesion root), sorted
+        self.matched_dev = None
+
+    def tables(self):
+        lesion_of = {int(r): k for k, r in enumerate(self.lesions[:, 0])}
+        comp_of = {int(r): c for c, r in enumerate(self.comps[:, 0])}
+        matched = [[] for _ in lesion_of]
+        hit = np.zeros(len(comp_of), dtype=bool)
+        for comp_root, lesion_root in self.pairs.tolist():
+            matched[lesion_of[lesion_root]].append(comp_of[comp_root])          # ascending component order
+            hit[comp_of[comp_root]] = True
+        sizes = self.comps[:, 1]
+        return dict(lesion_roots=self.lesions[:, 0].tolist(), vol=self.lesions[:, 1].tolist(),
+                    tp=self.lesions[:, 2].tolist(),
+                    matched_voxels=[int(sizes[m].sum()) if m else 0 for m in matched],
+                    matched_components=matched, comp_roots=self.comps[:, 0].tolist(), comp_sizes=sizes.tolist(),
+                    n_fp=int((~hit).sum()))
+
+    def lesion_hd95(self, k, matched):
+        """hd95(M_k, G_k) over the union box of both, grown by one voxel and clamped: a mask voxel then lies on
+        a face of the crop only where that is a face of the volume, so the crop's borders are the volume's."""
+        lib = self.lib
+        boxes = [_box(self.lesions[k], self.shape)] + [_box(self.comps[c], self.shape) for c in matched]
+        crop = []
+        for a in range(3):
+            crop += [max(min(b[a][0] for b in boxes) - 1, 0), min(max(b[a][1] for b in boxes) + 1, self.shape[a])]
+        if self.matched_dev is None:            # every lesion's matched roots, one upload per region
+            order = np.argsort(self.pairs[:, 1], kind="stable")
+            self.by_lesion = self.pairs[order]
+            self.matched_dev = torch.from_numpy(self.by_lesion[:, 0].astype(np.int32)).to(self.truth.device)
+        root = int(self.lesions[k, 0])
+        first = int(np.searchsorted(self.by_lesion[:, 1], root, "left"))
+        count = int(np.searchsorted(self.by_lesion[:, 1], root, "right")) - first
+        dims = tuple(crop[2 * a + 1] - crop[2 * a] for a in range(3))
+        mask_m = torch.empty(dims, dtype=torch.int16, device=self.truth.device)
+        mask_g = torch.empty_like(mask_m)
+        x, y, z = self.shape
+        check(lib.gts_lesionwise_masks_i16(ptr(self.truth), ptr(self.roots_p), ptr(self.roots_d), x, y, z, self.region,
+                                           root, self.matched_dev.data_ptr() + 4 * first, count,
+                                           (ctypes.c_int64 * 6)(*crop), ptr(mask_m), ptr(mask_g), current_stream()),
+              "gts_lesionwise_masks_i16")
+        n, d2_lo, d2_hi, present = metrics.hd95_order_stats(mask_m, mask_g)[2].cpu().tolist()
+        if present != 3:
+            raise _lib.GtsError(f"lesionwise: lesion {k} lost a mask over its box {crop}")
+        return metrics.percentile95_from_order_stats(n, d2_lo, d2_hi)
+
+
+def lesion_tables(pred, truth, region, dilation=3):
+    """The integer tables of one region, as Python lists in lesion order (ascending smallest C-order index of
+    the dilated lesion, scipy's label order): lesion_roots, vol (|G_k|), tp (|P n G_k|), matched_voxels (|M_k|),
+    matched_components (indices into comp_roots / comp_sizes, which are in component order), n_fp."""
+    pred, truth = _pair(pred, truth, "lesion_tables")
+    region, dilation = _region_index(region), _dilation(dilation, "lesion_tables")
+    return _RegionState(_lib.load(), pred, truth, region, dilation).tables()
+
+
+def _region_scores(state, min_lesion_voxels):
+    t = state.tables()
+    lesions, dice_sum, hd_sum, n_scored, n_fn = [], 0.0, 0.0, 0, 0
+    for k, (vol, tp, m, matched) in enumerate(zip(t["vol"], t["tp"], t["matched_voxels"], t["matched_components"])):
+        scored = vol > min_lesion_voxels
+        dice = hd = None
+        if scored:
+            if m == 0:
+                dice, hd = 0.0, PENALTY_HD95
+                n_fn += 1
+            else:
+                dice = (2 * tp) / (m + vol)
+                hd = state.lesion_hd95(k, matched)
+            dice_sum += dice
+            hd_sum += hd
+            n_scored += 1
+        lesions.append(dict(vol=vol, tp=tp, matched_voxels=m, scored=scored, dice=dice, hd95=hd))
+    n_fp = t["n_fp"]
+    if n_scored + n_fp == 0:
+        lw_dice, lw_hd95 = 1.0, 0.0
+    else:
+        lw_dice = dice_sum / (n_scored + n_fp)
+        lw_hd95 = (hd_sum + PENALTY_HD95 * n_fp) / (n_scored + n_fp)
+    return dict(lw_dice=lw_dice, lw_hd95=lw_hd95, n_lesions=len(lesions), n_scored=n_scored, n_fp=n_fp, n_fn=n_fn,
+                lesions=lesions, lesion_roots=t["lesion_roots"])
+
+
+def lesionwise_scores(pred, truth, dilation=3, min_lesion_voxels=50):
+    """{"WT" | "CT" | "ET": record} for two int16 CUDA volumes [X, Y, Z] of internal labels.  A record holds
+    the legacy whole-region dice (from the confusion counts) and hd95 (gts.metrics.hd95s), lw_dice, lw_hd95,
+    n_lesions, n_scored, n_fp, n_fn and `lesions`: one dict per lesion in lesion order with vol, tp,
+    matched_voxels, scored, dice and hd95 (None for a lesion of at most min_lesion_voxels voxels, which is
+    not scored).  A scored lesion without a matched component has dice 0 and hd95 374, and so does every
+    predicted component matched to no lesion."""
+    from model import evaluation
+
+    from . import ops
+
+    pred, truth = _pair(pred, truth, "lesionwise_scores")
+    dilation = _dilation(dilation, "lesionwise_scores")
+    lib = _lib.load()
+    dices = evaluation.dices_from_confusion(ops.label_confusion(pred, truth).cpu().numpy())
+    hd95s = metrics.hd95s(pred, truth)
+    out = {}
+    for r, name in enumerate(REGIONS):
+        record = _region_scores(_RegionState(lib, pred, truth, r, dilation), min_lesion_voxels)
+        record["dice"], record["hd95"] = float(dices[r]), float(hd95s[r])
+        out[name] = record
+    return out

@@ -1,0 +1,145 @@
+"""Written predictions + ground truth -> legacy and lesion-wise BraTS scores, on the MI355X.
+
+For each scan folder under DATA_DIR the label volume (the file ending with the label extension) and
+PRED_DIR/{id}.nii.gz, as segment_scans and the two generate_* scripts write it, are decoded, mapped to the
+internal labels and scored per region (WT, CT, ET) by gts.lesionwise.lesionwise_scores: the legacy whole-region
+Dice and HD95, and the BraTS 2023 lesion-wise Dice and HD95 (definition, and how it deviates from the
+challenge's script: DESIGN.md 4o).  Files may hold {0, 1, 2, 4} or the 2023 convention {0, 1, 2, 3}; a file with
+both 3 and 4, or any other value, is refused.  Volumes are scored as stored: prediction and truth must share a
+shape.
+
+One CSV row per scan and a final `mean` row over the scans; the same means are printed.  The GPU takes one scan
+at a time while a small thread pool decodes the next ones.  A scan whose prediction is missing, whose shape
+differs from its truth or that raises is reported and left out; the exit status is 1 when any scan was left out.
+
+    python -m scripts.score_predictions -d DATA_DIR -l _seg.nii.gz -s PRED_DIR -o scores.csv
+"""
+import argparse
+import os
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+_PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _PKG not in sys.path:
+    sys.path.insert(0, _PKG)
+
+import numpy as np  # noqa: E402
+
+import Filepaths  # noqa: E402
+from data_processing import labels as label_maps  # noqa: E402
+from data_processing import nifti_io  # noqa: E402
+from scripts import preprocess_dataset as prep  # noqa: E402
+
+IO_WORKERS = 3     # threads for NIfTI decode around the GPU work
+READ_AHEAD = 2     # scans decoded ahead of the one on the GPU
+REGIONS = ("WT", "CT", "ET")
+FIELDS = ("dice", "hd95", "lw_dice", "lw_hd95", "n_scored", "n_fp", "n_fn")
+COUNTS = ("n_scored", "n_fp", "n_fn")
+HEADER = ["id"] + [f"{region}_{field}" for region in REGIONS for field in FIELDS]
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description="Legacy and lesion-wise BraTS scores of written predictions on MI355X")
+    parser.add_argument("-d", "--data_dir", default=None, type=str,
+                        help="folder holding the scan folders (default: Filepaths.INPUT_MRI_DIR)")
+    parser.add_argument("-l", "--label_extension", default="_seg.nii.gz", help="file suffix of the label volume")
+    parser.add_argument("-s", "--pred_dir", required=True, help="folder holding the predictions, {id}.nii.gz")
+    parser.add_argument("-p", "--data_prefix", default="", help="common prefix of the scan folders, e.g. BraTS2021")
+    parser.add_argument("-o", "--output", required=True, help="the CSV file to write")
+    parser.add_argument("--dilation", type=int, default=3, choices=(0, 1, 2, 3),
+                        help="dilation steps that merge ground-truth components into lesions")
+    parser.add_argument("--min_lesion_voxels", type=int, default=50,
+                        help="a ground-truth lesion is scored when it has more voxels than this")
+    return parser
+
+
+def load_pair(folder, scan_id, label_extension, pred_dir):
+    """Host stage: both volumes as internal int16 labels, C-contiguous."""
+    pred_path = os.path.join(pred_dir, scan_id + ".nii.gz")
+    if not os.path.exists(pred_path):
+        raise FileNotFoundError(f"no prediction {pred_path}")
+    truth = label_maps.swap_labels_from_brats_any(nifti_io.read_in_labels(folder, label_extension))
+    pred = label_maps.swap_labels_from_brats_any(nifti_io.read_nifti(pred_path, np.int16))
+    if pred.shape != truth.shape:
+        raise ValueError(f"prediction {pred.shape} and ground truth {truth.shape} differ in shape")
+    if pred.ndim != 3:
+        raise ValueError(f"label volumes have {pred.ndim} axes, expected 3")
+    return np.ascontiguousarray(pred), np.ascontiguousarray(truth)
+
+
+def row_of(scores):
+    """The CSV fields of one scan's lesionwise_scores record, in HEADER's order (without the id)."""
+    return [scores[region][field] for region in REGIONS for field in FIELDS]
+
+
+def mean_row(rows):
+    """Column means over the scans' rows (plain float64 means; counts become averages per scan)."""
+    return [float(np.mean([row[c] for row in rows])) for c in range(len(HEADER) - 1)]
+
+
+def format_value(field, value):
+    return str(int(value)) if field.split("_", 1)[1] in COUNTS and float(value).is_integer() else repr(float(value))
+
+
+def format_row(name, values):
+    return ",".join([name] + [format_value(field, value) for field, value in zip(HEADER[1:], values)])
+
+
+def write_csv(path, rows):
+    """rows: {id: values}; the ids in sorted order, then the mean row (when any scan was scored)."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        f.write(",".join(HEADER) + "\n")
+        for scan_id in sorted(rows):
+            f.write(format_row(scan_id, rows[scan_id]) + "\n")
+        if rows:
+            f.write(format_row("mean", mean_row([rows[s] for s in sorted(rows)])) + "\n")
+
+
+def score(scans, label_extension, pred_dir, dilation=3, min_lesion_voxels=50):
+    """({id: CSV values}, ids left out) of {id: folder}."""
+    import torch
+
+    from gts import lesionwise
+
+    ids = sorted(scans)
+    rows, failed = {}, []
+    with ThreadPoolExecutor(max_workers=IO_WORKERS) as pool:
+        def submit(i):
+            return pool.submit(load_pair, scans[ids[i]], ids[i], label_extension, pred_dir)
+
+        pending = {i: submit(i) for i in range(min(READ_AHEAD, len(ids)))}
+        for i, scan_id in enumerate(ids):
+            if i + READ_AHEAD < len(ids):
+                pending[i + READ_AHEAD] = submit(i + READ_AHEAD)
+            try:
+                pred, truth = pending.pop(i).result()
+                rows[scan_id] = row_of(lesionwise.lesionwise_scores(torch.from_numpy(pred).cuda(),
+                                                                    torch.from_numpy(truth).cuda(), dilation,
+                                                                    min_lesion_voxels))
+            except Exception as exc:
+                print(f"{scan_id}: left out ({exc!r})")
+                failed.append(scan_id)
+    return rows, failed
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    scans = prep.find_scans(args.data_dir or Filepaths.INPUT_MRI_DIR, args.data_prefix)
+    print(f"{len(scans)} scan folders found; scores go to {args.output}")
+    rows, failed = score(scans, args.label_extension, os.path.expanduser(args.pred_dir), args.dilation,
+                         args.min_lesion_voxels)
+    write_csv(os.path.expanduser(args.output), rows)
+    if rows:
+        means = mean_row([rows[s] for s in sorted(rows)])
+        for r, region in enumerate(REGIONS):
+            part = dict(zip(FIELDS, means[r * len(FIELDS):(r + 1) * len(FIELDS)]))
+            print(f"{region}: Dice {part['dice']:.4f}, HD95 {part['hd95']:.3f}, lesion-wise Dice {part['lw_dice']:.4f}, "
+                  f"lesion-wise HD95 {part['lw_hd95']:.3f} (per scan: {part['n_scored']:.2f} scored lesions, "
+                  f"{part['n_fp']:.2f} false positives, {part['n_fn']:.2f} missed)")
+    print(f"{len(rows)} scan(s) scored, {len(failed)} left out")
+    return 1 if failed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

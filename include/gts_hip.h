@@ -700,6 +700,45 @@ int32_t gts_components_filter_i16(const int16_t* labels_in, int64_t X, int64_t Y
                                   int16_t* labels_out, int64_t* stats, void* workspace, int64_t workspace_bytes,
                                   void* stream);
 
+/* ---- L1-L3: lesion-wise scoring of a prediction (BraTS 2023 lesion-wise Dice / HD95) ----------------------
+ * The device half of gts/lesionwise.py: what a user otherwise does on the host with scipy's binary_dilation,
+ * two ndimage.label calls and one np.isin per lesion.  Label volumes are int16 [X, Y, Z], Z contiguous, in the
+ * internal coding; region 0 = WT (v != 0), 1 = CT (v in {2, 3}), 2 = ET (v == 3), as in H1; another region:
+ * GTS_ERR_ARGKIND.  Limits: every extent >= 1 and X * Y * Z < 2^31, else GTS_ERR_SHAPE; a workspace below
+ * gts_lesionwise_workspace(X, Y, Z) bytes (0 for a rejected shape): GTS_ERR_SHAPE.  Nothing is launched for a
+ * rejected argument.  Roots are those of gts_components_roots_i16 at connectivity 26: 1 + the smallest linear
+ * index of the voxel's component, 0 for background.
+ * gts_lesionwise_dilate_i16 (L1): mask_out (int16 0 / 1) = scipy's binary_dilation(region mask,
+ *   generate_binary_structure(3, 2), iterations = dilation, border_value = 0), in one pass by the footprint
+ *   { o : max |o_i| <= n, sum |o_i| <= 2 n }, clipped at every face; dilation 0 is the region mask itself.
+ *   dilation outside 0..3: GTS_ERR_ARGKIND.
+ * gts_lesionwise_tables_i16 (L2): pred_roots = the roots of the prediction's region mask P, dilated_roots = the
+ *   roots of L1's mask D of the truth.  tables_out (device int32, tables_ints >= gts_lesionwise_table_ints(X, Y, Z),
+ *   else GTS_ERR_SHAPE) = { n_lesions, n_components, n_pairs, 0 }, then n_lesions rows of 9 (one per component of
+ *   D: root, |G_k| with G_k the truth region voxels in it, |P n G_k|, box of G_k), n_components rows of 9 (one
+ *   per component of P: root, size, 0, box), then n_pairs pairs (component root, lesion root) that cover every
+ *   pair with a common voxel at least once.  A box is { x_end, X - x_begin, y_end, Y - y_begin, z_end,
+ *   Z - z_begin } (ends exclusive; all 0 when empty).  Rows and pairs come in arrival order, which may differ
+ *   between runs; as sets they are the same on every run.  No list can outgrow its buffer: each holds at most
+ *   one entry per 2 x 2 x 2 cell of the volume.
+ * gts_lesionwise_masks_i16 (L3): over the box { x_begin, x_end, y_begin, y_end, z_begin, z_end } (HOST int64
+ *   [6], read at launch; inside the volume and not empty, else GTS_ERR_SHAPE), mask_m and mask_g (int16, C-order
+ *   over the box) = 3 where pred_roots is one of matched_roots (device int32 [n_matched], ascending), resp.
+ *   where the voxel is in the truth region and its dilated root is lesion_root; 0 elsewhere.  The pair H1 takes.
+ * Integer arithmetic and integer atomics throughout: identical results on every run. */
+int64_t gts_lesionwise_workspace(int64_t X, int64_t Y, int64_t Z);
+int64_t gts_lesionwise_table_ints(int64_t X, int64_t Y, int64_t Z);
+int32_t gts_lesionwise_dilate_i16(const int16_t* labels, int64_t X, int64_t Y, int64_t Z, int32_t region,
+                                  int32_t dilation, int16_t* mask_out, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+int32_t gts_lesionwise_tables_i16(const int16_t* truth, const int32_t* pred_roots, const int32_t* dilated_roots,
+                                  int64_t X, int64_t Y, int64_t Z, int32_t region, int32_t* tables_out,
+                                  int64_t tables_ints, void* workspace, int64_t workspace_bytes, void* stream);
+int32_t gts_lesionwise_masks_i16(const int16_t* truth, const int32_t* pred_roots, const int32_t* dilated_roots,
+                                 int64_t X, int64_t Y, int64_t Z, int32_t region, int32_t lesion_root,
+                                 const int32_t* matched_roots, int64_t n_matched, const int64_t* box, int16_t* mask_m,
+                                 int16_t* mask_g, void* stream);
+
 /* ---- I1-I3: intake of a raw four-modality scan --------------------------------------------------------
  * The host step of DataPreprocessor.load (scripts/preprocess_dataset.py) on the device:
  *   crop = determine_brain_crop(image); image = standardize_img(normalize_img(image[crop]), mean, std).
