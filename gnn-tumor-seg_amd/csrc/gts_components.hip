@@ -20,8 +20,9 @@
 //   C5  filter: counts (components, removed components, removed voxels, surviving ET voxels), then the
 //       output volume.  Two launches, because the ET rule needs the count over the whole volume first.
 //
-// Every result is an integer that does not depend on scheduling.
-#include "gts_common.h"
+// Every result is an integer that does not depend on scheduling.  The volume limit, the workspace rounding
+// and the wave and workgroup counting idioms of C4 and C5 are gts_volume.h's.
+#include "gts_volume.h"
 
 namespace gts {
 namespace {
@@ -29,7 +30,6 @@ namespace {
 constexpr int kBackground = -1;
 constexpr int kSizeChunks = 16;     // C4: 64-voxel chunks one wave walks
 constexpr int kCountBlocks = 2048;  // C5: grid cap of the counting pass
-constexpr int64_t kHeaderBytes = 256;
 
 // Parents change under the merge pass's feet.  A value read late is still an ancestor-or-self that was
 // valid once (links are only ever replaced by the thread that then unites the old target with the new
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(kBlock) void components_merge_kernel(const int16_t*
   if (i64 >= n || lab[i64] == 0) return;
   const int i = static_cast<int>(i64);
   const int yz = Y * Z;  // < 2^31: a factor of n
-  const int z = i % Z, y = (i / Z) % Y, x = i / yz;
+  const auto [x, y, z] = split_xyz(i, Y, Z);
   const bool prev = z > 0 && lab[i - 1] != 0;
   if (prev && (i & (kWave - 1)) == 0) unite(parent, i, i - 1);  // a run that C1 saw cut at the wave's edge
   if (y > 0) unite_with_line<kDiag>(lab, parent, i, i - Z, z, Z, prev);
@@ -155,10 +155,7 @@ __global__ __launch_bounds__(kBlock) void components_sizes_kernel(const int* __r
   for (int c = 0; c < kSizeChunks && base + c * kWave < n; ++c) {
     const int64_t i = base + c * kWave + lane;
     const int r = i < n ? roots[i] : 0;
-    unsigned long long todo = __ballot(r != 0);
-    while (todo) {
-      const int key = __shfl(r, __ffsll(static_cast<long long>(todo)) - 1, kWave);
-      const unsigned long long same = __ballot(r == key);
+    wave_for_each_key(r != 0, r, [&](int key, unsigned long long same, bool) {
       const int count = __popcll(same);
       if (key == run_root) {
         run_count += count;
@@ -167,8 +164,7 @@ __global__ __launch_bounds__(kBlock) void components_sizes_kernel(const int* __r
         run_root = key;
         run_count = count;
       }
-      todo &= ~same;
-    }
+    });
   }
   if (run_count && lane == 0) atomicAdd(&sizes[run_root - 1], run_count);
 }
@@ -179,9 +175,6 @@ __global__ __launch_bounds__(kBlock) void components_count_kernel(const int16_t*
                                                                   const int* __restrict__ sizes,
                                                                   unsigned long long* __restrict__ counters, int64_t n,
                                                                   int64_t min_voxels, int et_label, int et_on) {
-  __shared__ unsigned block_counts[4];
-  if (threadIdx.x < 4) block_counts[threadIdx.x] = 0;
-  __syncthreads();
   unsigned mine[4] = {0, 0, 0, 0};
   for (int64_t i = int64_t{blockIdx.x} * kBlock + threadIdx.x; i < n; i += int64_t{gridDim.x} * kBlock) {
     const int r = roots[i];
@@ -193,16 +186,7 @@ __global__ __launch_bounds__(kBlock) void components_count_kernel(const int16_t*
     mine[2] += small;
     mine[3] += et_on && !small && lab[i] == et_label;
   }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    unsigned s = mine[c];
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, kWave);
-    if ((threadIdx.x & (kWave - 1)) == 0 && s) atomicAdd(&block_counts[c], s);
-  }
-  __syncthreads();
-  if (threadIdx.x < 4 && block_counts[threadIdx.x])
-    atomicAdd(&counters[threadIdx.x], static_cast<unsigned long long>(block_counts[threadIdx.x]));
+  block_add_counters(mine, counters);
 }
 
 // C5, output.  in and out may be one buffer: a lane reads and writes its own voxel only.
@@ -234,28 +218,16 @@ __global__ __launch_bounds__(kBlock) void components_apply_kernel(const int16_t*
   out[i] = v;
 }
 
-inline int64_t round256(int64_t b) { return (b + 255) & ~int64_t{255}; }
-
-// 1: a volume the kernels take (*n its voxel count, 0 allowed), 0: negative extents or X * Y * Z >= 2^31
-inline bool components_voxels(int64_t X, int64_t Y, int64_t Z, int64_t* n) {
-  constexpr int64_t kLimit = int64_t{1} << 31;
-  if (X < 0 || Y < 0 || Z < 0) return false;
-  *n = 0;
-  if (X == 0 || Y == 0 || Z == 0) return true;
-  if (X >= kLimit || Y >= kLimit || Z >= kLimit || X * Y >= kLimit || X * Y * Z >= kLimit) return false;
-  *n = X * Y * Z;
-  return true;
-}
+// an empty volume is a volume: the entry points return at once
+inline bool components_voxels(int64_t X, int64_t Y, int64_t Z, int64_t* n) { return volume_voxels(X, Y, Z, true, n); }
 
 // header (the four counters) | parent int32[n] | roots int32[n] | sizes int32[n]
 inline int64_t components_bytes(int64_t n) { return kHeaderBytes + 3 * round256(4 * n); }
 
-inline int components_blocks(int64_t n) { return static_cast<int>((n + kBlock - 1) / kBlock); }
-
 // C1-C3 into roots (int32[n]); sizes (may be NULL) is cleared on the way
 int components_label(const int16_t* lab, int64_t n, int Y, int Z, int connectivity, int* parent, int* roots, int* sizes,
                      hipStream_t st) {
-  const int blocks = components_blocks(n);
+  const int blocks = blocks_for(n, kBlock);
   components_init_kernel<<<blocks, kBlock, 0, st>>>(lab, parent, sizes, n, Z);
   if (connectivity == 26)
     components_merge_kernel<true><<<blocks, kBlock, 0, st>>>(lab, parent, n, Y, Z);
@@ -309,12 +281,10 @@ extern "C" int32_t gts_components_filter_i16(const int16_t* labels_in, int64_t X
   const int status = components_label(labels_in, n, static_cast<int>(Y), static_cast<int>(Z), connectivity, parent,
                                       roots, sizes, st);
   if (status != GTS_OK) return status;
-  const int64_t size_blocks = (n + int64_t{kBlock} * kSizeChunks - 1) / (int64_t{kBlock} * kSizeChunks);
-  components_sizes_kernel<<<static_cast<int>(size_blocks), kBlock, 0, st>>>(roots, sizes, n);
-  const int blocks = components_blocks(n);
-  components_count_kernel<<<blocks < kCountBlocks ? blocks : kCountBlocks, kBlock, 0, st>>>(
+  components_sizes_kernel<<<blocks_for(n, int64_t{kBlock} * kSizeChunks), kBlock, 0, st>>>(roots, sizes, n);
+  components_count_kernel<<<blocks_for(n, kBlock, kCountBlocks), kBlock, 0, st>>>(
       labels_in, roots, sizes, counters, n, min_voxels, et_label, et_min_voxels > 0 ? 1 : 0);
-  components_apply_kernel<<<blocks, kBlock, 0, st>>>(labels_in, labels_out, roots, sizes, counters,
+  components_apply_kernel<<<blocks_for(n, kBlock), kBlock, 0, st>>>(labels_in, labels_out, roots, sizes, counters,
                                                      reinterpret_cast<long long*>(stats), n, min_voxels, et_label,
                                                      et_min_voxels, et_replacement);
   return launch_status();

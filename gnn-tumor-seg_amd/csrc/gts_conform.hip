@@ -23,7 +23,7 @@
 //          pitch of 65 words: the row writes and the column reads (ds_write_b32 / ds_read_b32, 32 banks per
 //          32-lane group) both touch 32 distinct banks.
 // Table entries are clamped to the input extent before use, so no table can make a read leave the volume.
-#include "gts_common.h"
+#include "gts_volume.h"
 
 namespace gts {
 namespace {
@@ -210,11 +210,10 @@ int launch(const void* src, void* dst, const ConformArgs& p, hipStream_t st) {
                       reinterpret_cast<uintptr_t>(src) % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 16 == 0;
     if (wide) {
       const int64_t groups = total / kVec;
-      conform_rows_wide_kernel<In><<<static_cast<unsigned>((groups + kBlock - 1) / kBlock), kBlock, 0, st>>>(
+      conform_rows_wide_kernel<In><<<blocks_for(groups, kBlock), kBlock, 0, st>>>(
           s, reinterpret_cast<In*>(d), p, groups);
     } else {
-      conform_rows_kernel<In, Out, kMode><<<static_cast<unsigned>((total + kBlock - 1) / kBlock), kBlock, 0, st>>>(
-          s, d, p, total);
+      conform_rows_kernel<In, Out, kMode><<<blocks_for(total, kBlock), kBlock, 0, st>>>(s, d, p, total);
     }
     return launch_status();
   }
@@ -250,9 +249,9 @@ extern "C" int32_t gts_conform_gather(const void* src, int32_t dtype, int64_t C,
   }
   if (seen != 7) return GTS_ERR_ARGKIND;
   if (C == 0) return GTS_OK;
-  constexpr int64_t kLimit = int64_t{1} << 31;
-  if (X * Y * Z >= kLimit || OX * OY * OZ >= kLimit || C >= kLimit) return GTS_ERR_SHAPE;  // extents <= 65535: no overflow
-  if (X * Y * Z * C >= kLimit || OX * OY * OZ * C >= kLimit) return GTS_ERR_SHAPE;
+  int64_t n_in, n_out, all;  // a lane's linear index covers every channel: C volumes are one volume of C planes
+  if (!volume_voxels(X, Y, Z, false, &n_in) || !volume_voxels(OX, OY, OZ, false, &n_out)) return GTS_ERR_SHAPE;
+  if (!volume_voxels(n_in, C, 1, false, &all) || !volume_voxels(n_out, C, 1, false, &all)) return GTS_ERR_SHAPE;
   ConformArgs p;
   int64_t at = 0;
   for (int k = 0; k < 3; ++k) {  // output axis k reads input axis axes[k]; its tables start at `at`

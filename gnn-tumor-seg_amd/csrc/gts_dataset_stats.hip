@@ -50,11 +50,8 @@ __global__ __launch_bounds__(kBlock) void dstats_mask_kernel(const T* __restrict
                                                              const int16_t* __restrict__ lab, unsigned vol,
                                                              unsigned long long* __restrict__ bits,
                                                              unsigned long long* __restrict__ counts) {
-  __shared__ unsigned s_n, s_bad;
-  if (threadIdx.x == 0) s_n = s_bad = 0;
-  __syncthreads();
   const unsigned padded = (vol + 63u) & ~63u;         // whole waves: every lane of a wave takes the same trips
-  unsigned mine = 0, bad = 0;
+  unsigned mine[2] = {0, 0};  // members, members with a non-finite value
   for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < padded; i += gridDim.x * kBlock) {
     bool member = false;
     if (i < vol) {
@@ -63,27 +60,14 @@ __global__ __launch_bounds__(kBlock) void dstats_mask_kernel(const T* __restrict
         bool finite = true;
 #pragma unroll
         for (int c = 0; c < kChannels; ++c) finite &= __builtin_isfinite(load_f32(src, static_cast<size_t>(c) * vol + i));
-        bad += finite ? 0u : 1u;
+        mine[1] += finite ? 0u : 1u;
       }
     }
     const unsigned long long word = __ballot(member);
     if ((threadIdx.x & (kWave - 1)) == 0) bits[i >> 6] = word;
-    mine += member ? 1u : 0u;
+    mine[0] += member ? 1u : 0u;
   }
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    mine += __shfl_xor(mine, off, kWave);
-    bad += __shfl_xor(bad, off, kWave);
-  }
-  if ((threadIdx.x & (kWave - 1)) == 0) {
-    if (mine) atomicAdd(&s_n, mine);
-    if (bad) atomicAdd(&s_bad, bad);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (s_n) atomicAdd(&counts[0], static_cast<unsigned long long>(s_n));
-    if (s_bad) atomicAdd(&counts[1], static_cast<unsigned long long>(s_bad));
-  }
+  block_add_counters(mine, counts);
 }
 
 struct Tops {
@@ -119,10 +103,7 @@ __global__ __launch_bounds__(kBlock) void dstats_moments_kernel(const T* __restr
       }
     }
 #pragma unroll
-    for (int j = 0; j < kSums; ++j) {
-#pragma unroll
-      for (int off = kWave / 2; off > 0; off >>= 1) acc[j] += __shfl_xor(acc[j], off, kWave);
-    }
+    for (int j = 0; j < kSums; ++j) acc[j] = wave_sum(acc[j]);
     if (lane == 0) {
 #pragma unroll
       for (int j = 0; j < kSums; ++j) red[wave][j] = acc[j];
@@ -163,8 +144,6 @@ __global__ __launch_bounds__(kBlock) void dstats_final_kernel(const double* __re
   }
 }
 
-inline int units_grid(int64_t units) { return static_cast<int>(units < kMaxBlocks ? units : kMaxBlocks); }
-
 }  // namespace
 }  // namespace gts
 
@@ -188,7 +167,7 @@ extern "C" int32_t gts_dataset_stats_mask(const void* src, int32_t dtype, const 
   if (hipMemsetAsync(counts, 0, 16, st) != hipSuccess) return launch_status();
   auto* bits = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + l.mask);
   auto* cnt = reinterpret_cast<unsigned long long*>(counts);
-  const int grid = grid_for(vol);
+  const int grid = blocks_for(vol, kBlock, kMaxBlocks);
   if (dtype == kI16)
     dstats_mask_kernel<int16_t><<<grid, kBlock, 0, st>>>(static_cast<const int16_t*>(src), labels,
                                                          static_cast<unsigned>(vol), bits, cnt);
@@ -238,10 +217,10 @@ extern "C" int32_t gts_dataset_stats_moments(const void* src, int32_t dtype, int
   double* partial = reinterpret_cast<double*>(ws + l.partial);
   const unsigned units = static_cast<unsigned>(l.units), words = static_cast<unsigned>(l.words);
   if (dtype == kI16)
-    dstats_moments_kernel<int16_t><<<units_grid(l.units), kBlock, 0, st>>>(
+    dstats_moments_kernel<int16_t><<<blocks_for(l.units, 1, kMaxBlocks), kBlock, 0, st>>>(
         static_cast<const int16_t*>(src), static_cast<unsigned>(vol), bits, words, p, units, partial);
   else
-    dstats_moments_kernel<float><<<units_grid(l.units), kBlock, 0, st>>>(
+    dstats_moments_kernel<float><<<blocks_for(l.units, 1, kMaxBlocks), kBlock, 0, st>>>(
         static_cast<const float*>(src), static_cast<unsigned>(vol), bits, words, p, units, partial);
   dstats_final_kernel<<<1, kBlock, 0, st>>>(partial, units, static_cast<unsigned long long>(n), out);
   return launch_status();

@@ -9,8 +9,8 @@
 // p in B(r, side) and select two order statistics of that multiset; the host takes the square roots
 // and interpolates.  Everything here is integer arithmetic: results do not depend on scheduling.
 //
-//   H1  border bits, one byte per voxel, plus the 6 border counts (wave sums, one atomic per
-//       workgroup and channel);
+//   H1  border bits (the region rule is gts_volume.h's region_bits), one byte per voxel, plus the 6
+//       border counts (block_add_counters: wave sums, one atomic per workgroup and channel);
 //   H2  1-D distance along Z (the contiguous axis) to the nearest border voxel of each channel: the
 //       lines of a workgroup are one contiguous byte range, staged in LDS and swept forward and back
 //       by one lane per line; uint16 out (extents <= 4097), 0xFFFF = no feature in the line;
@@ -22,7 +22,7 @@
 //       volume itself is never written;
 //   H5  (selection) prefix sums over each region's histogram find the ranks np.percentile(., 95)
 //       interpolates between.
-#include "gts_common.h"
+#include "gts_volume.h"
 
 namespace gts {
 namespace {
@@ -36,23 +36,16 @@ constexpr int kLdsBudget = 64 * 1024;              // dynamic LDS of one H2-H4 w
 constexpr int kSmallBins = 1024;                   // H4's per-workgroup LDS histogram
 constexpr int kSelectThreads = 1024;
 
-__device__ __forceinline__ unsigned region_bits(int v) {
-  return (v != 0 ? 1u : 0u) | ((v == 2 || v == 3) ? 2u : 0u) | (v == 3 ? 4u : 0u);
-}
-
 // H1.  A region voxel is border when a 6-neighbour inside the volume lies outside the region, or when
 // it lies on a face of an axis longer than 1; with all_border every region voxel is border.
 __global__ __launch_bounds__(kBlock) void hd95_border_kernel(const int16_t* __restrict__ pred,
                                                              const int16_t* __restrict__ truth,
                                                              uint8_t* __restrict__ bits, unsigned* __restrict__ counts,
                                                              int X, int Y, int Z, int all_border) {
-  __shared__ unsigned block_counts[kChannels];
-  if (threadIdx.x < kChannels) block_counts[threadIdx.x] = 0;
-  __syncthreads();
   const unsigned n = static_cast<unsigned>(X) * Y * Z, yz = static_cast<unsigned>(Y) * Z;
   unsigned mine[kChannels] = {0, 0, 0, 0, 0, 0};
   for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-    const unsigned z = i % Z, y = (i / Z) % Y, x = i / yz;
+    const auto [x, y, z] = split_xyz(i, Y, Z);
     unsigned out = 0;
 #pragma unroll
     for (int side = 0; side < 2; ++side) {
@@ -71,15 +64,7 @@ __global__ __launch_bounds__(kBlock) void hd95_border_kernel(const int16_t* __re
 #pragma unroll
     for (int c = 0; c < kChannels; ++c) mine[c] += (out >> c) & 1u;
   }
-#pragma unroll
-  for (int c = 0; c < kChannels; ++c) {
-    unsigned s = mine[c];
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, kWave);
-    if ((threadIdx.x & (kWave - 1)) == 0 && s) atomicAdd(&block_counts[c], s);
-  }
-  __syncthreads();
-  if (threadIdx.x < kChannels && block_counts[threadIdx.x]) atomicAdd(&counts[threadIdx.x], block_counts[threadIdx.x]);
+  block_add_counters(mine, counts);
 }
 
 // H2.  Lines line0 .. line0 + lines - 1 (flattened (x, y)) are the contiguous bytes [line0 * Z, ...).
@@ -298,17 +283,14 @@ struct Hd95Layout {
   int64_t bins, n, hist, bits, g1, g2, total;
 };
 
-inline int64_t round256(int64_t b) { return (b + 255) & ~int64_t{255}; }
-
 // false for extents < 1, X * Y * Z >= 2^31 or (X-1)^2 + (Y-1)^2 + (Z-1)^2 > 2^24
 inline bool hd95_layout(int64_t X, int64_t Y, int64_t Z, Hd95Layout* l) {
-  if (X < 1 || Y < 1 || Z < 1 || X > kMaxBound || Y > kMaxBound || Z > kMaxBound) return false;
+  if (!volume_voxels(X, Y, Z, false, &l->n)) return false;
+  // X + Y + Z - 3 <= X * Y * Z < 2^31 for extents >= 1, so the sum of squares stays below 2^62
   const int64_t bound = (X - 1) * (X - 1) + (Y - 1) * (Y - 1) + (Z - 1) * (Z - 1);
   if (bound > kMaxBound) return false;  // every extent is then <= 4097
-  l->n = X * Y * Z;
-  if (l->n >= (int64_t{1} << 31)) return false;
   l->bins = bound + 1;
-  l->hist = 256;  // counts: 6 uint32 in the first 256 bytes
+  l->hist = kHeaderBytes;  // counts: 6 uint32 in the header
   l->bits = l->hist + round256(3 * l->bins * 4);
   l->g1 = l->bits + round256(l->n);
   l->g2 = l->g1 + round256(kChannels * l->n * 2);
@@ -349,9 +331,7 @@ extern "C" int32_t gts_hd95_order_stats_i16(const int16_t* pred, const int16_t* 
   const size_t n = static_cast<size_t>(l.n);
 
   if (hipMemsetAsync(ws, 0, l.bits, st) != hipSuccess) return launch_status();
-  const int64_t h1_blocks = (l.n + kBlock - 1) / kBlock;
-  hd95_border_kernel<<<static_cast<int>(h1_blocks < 2048 ? h1_blocks : 2048), kBlock, 0, st>>>(
-      pred, truth, bits, counts, x, y, z, all_border);
+  hd95_border_kernel<<<blocks_for(l.n, kBlock, 2048), kBlock, 0, st>>>(pred, truth, bits, counts, x, y, z, all_border);
 
   // H2: bytes (1) + distances (2) per element of a line; the distances start 16-byte aligned
   const int lz = lanes_for(3 * Z + 16, kLdsBudget);

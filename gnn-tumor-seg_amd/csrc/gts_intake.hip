@@ -59,8 +59,7 @@ __global__ __launch_bounds__(kBlock) void intake_occupancy_kernel(const T* __res
       sz[r / Y] = 1;
     }
   }
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) mine += __shfl_xor(mine, off, kWave);
+  mine = wave_sum(mine);
   if ((threadIdx.x & (kWave - 1)) == 0 && mine) atomicAdd(&bad, mine);
   __syncthreads();
   for (int i = threadIdx.x; i < X; i += kBlock)
@@ -135,7 +134,7 @@ extern "C" int32_t gts_intake_occupancy(const void* src, int32_t dtype, int64_t 
     return launch_status();
   const int x = static_cast<int>(X), y = static_cast<int>(Y), z = static_cast<int>(Z);
   auto* bad = reinterpret_cast<unsigned long long*>(nonfinite);
-  const int grid = grid_for(X * Y * Z);
+  const int grid = blocks_for(X * Y * Z, kBlock, kMaxBlocks);
   if (dtype == kI16)
     intake_occupancy_kernel<int16_t><<<grid, kBlock, 0, st>>>(static_cast<const int16_t*>(src), x, y, z, flag_x,
                                                               flag_y, flag_z, bad);

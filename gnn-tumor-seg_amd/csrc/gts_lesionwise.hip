@@ -19,8 +19,9 @@
 //   L3  lesion masks: M_k (the predicted voxels whose root is in a sorted list) and G_k (the truth region
 //       voxels whose D root is the lesion's) as label 3 over a box of the volume, the input pair of H1.
 //
-// Integer arithmetic and integer atomics (add, max) only: identical results on every run.
-#include "gts_common.h"
+// Integer arithmetic and integer atomics (add, max) only: identical results on every run.  The region rule
+// (in_region, the one H1 uses), the volume limit and the per-key wave loop of L2 are gts_volume.h's.
+#include "gts_volume.h"
 
 namespace gts {
 namespace {
@@ -29,14 +30,9 @@ constexpr int kRowInts = 9;  // root | count | tp | x_hi x_lo y_hi y_lo z_hi z_l
 constexpr int kTileX = 8, kTileY = 8, kTileW = 4;  // L1: rows and words of one workgroup, kBlock in all
 constexpr int kMaxDilation = 3;
 constexpr int kMaxBlocks = 1 << 20;  // grid cap of the strided kernels
-constexpr int64_t kHeaderBytes = 256;
 typedef unsigned long long word_t;
 
 static_assert(kTileX * kTileY * kTileW == kBlock, "one thread per output word");
-
-__device__ __forceinline__ bool in_region(int v, int region) {
-  return region == 0 ? v != 0 : region == 1 ? (v == 2 || v == 3) : v == 3;
-}
 
 // L1, packing.  Wave u owns word u = (row, w): voxels z = 64 w + lane of the row.
 __global__ __launch_bounds__(kBlock) void lesion_pack_kernel(const int16_t* __restrict__ lab,
@@ -137,11 +133,7 @@ __global__ __launch_bounds__(kBlock) void lesion_slots_kernel(const int* __restr
 // box by their own.  Lanes of one slot are summed in the wave first: a large lesion would otherwise put
 // eight atomics per voxel on one row.
 __device__ __forceinline__ void wave_add_rows(int* table, bool on, int slot, bool tp, const int (&box)[6], int lane) {
-  word_t todo = __ballot(on);
-  while (todo) {
-    const int key = __shfl(slot, __ffsll(static_cast<long long>(todo)) - 1, kWave);
-    const bool mine = on && slot == key;
-    const word_t same = __ballot(mine);
+  wave_for_each_key(on, slot, [&](int key, word_t same, bool mine) {
     const int count = __popcll(same);
     const int hits = __popcll(__ballot(mine && tp));
     int top[6];
@@ -162,8 +154,7 @@ __device__ __forceinline__ void wave_add_rows(int* table, bool on, int slot, boo
 #pragma unroll
       for (int k = 0; k < 6; ++k) atomicMax(row + 3 + k, top[k]);
     }
-    todo &= ~same;
-  }
+  });
 }
 
 // L2, the tables.  Box entries are kept as maxima of coordinate + 1 and of extent - coordinate, so a cleared
@@ -180,7 +171,7 @@ __global__ __launch_bounds__(kBlock) void lesion_tables_kernel(const int16_t* __
   const bool inside = i64 < n;
   const int i = inside ? static_cast<int>(i64) : 0;
   const int yz = Y * Z;  // < 2^31: a factor of n
-  const int z = i % Z, y = (i / Z) % Y, x = i / yz;
+  const auto [x, y, z] = split_xyz(i, Y, Z);
   const int rp = inside ? roots_p[i] : 0;
   const int rd = inside ? roots_d[i] : 0;
   const bool g = inside && rd != 0 && in_region(truth[i], region);
@@ -249,8 +240,8 @@ __global__ __launch_bounds__(kBlock) void lesion_masks_kernel(const int16_t* __r
                                                               int16_t* __restrict__ mask_g) {
   const int64_t e = int64_t{blockIdx.x} * kBlock + threadIdx.x;
   if (e >= count) return;
-  const int64_t z = z0 + e % cz, y = y0 + (e / cz) % cy, x = x0 + e / (int64_t{cz} * cy);
-  const int64_t i = (x * Y + y) * Z + z;
+  const auto at = split_xyz(e, cy, cz);  // inside the box
+  const int64_t i = ((x0 + at.x) * Y + y0 + at.y) * Z + z0 + at.z;
   const int rp = roots_p[i];
   bool member = false;
   if (rp != 0) {
@@ -268,16 +259,8 @@ __global__ __launch_bounds__(kBlock) void lesion_masks_kernel(const int16_t* __r
   mask_g[e] = roots_d[i] == lesion_root && in_region(truth[i], region) ? 3 : 0;
 }
 
-inline int64_t round256(int64_t b) { return (b + 255) & ~int64_t{255}; }
-
-// 1: a volume the kernels take (every extent >= 1, X * Y * Z < 2^31)
-inline bool lesion_voxels(int64_t X, int64_t Y, int64_t Z, int64_t* n) {
-  constexpr int64_t kLimit = int64_t{1} << 31;
-  if (X < 1 || Y < 1 || Z < 1) return false;
-  if (X >= kLimit || Y >= kLimit || Z >= kLimit || X * Y >= kLimit || X * Y * Z >= kLimit) return false;
-  *n = X * Y * Z;
-  return true;
-}
+// every extent >= 1: the dilation tiles and the 2 x 2 x 2 cells below have no empty case
+inline bool lesion_voxels(int64_t X, int64_t Y, int64_t Z, int64_t* n) { return volume_voxels(X, Y, Z, false, n); }
 
 inline int64_t lesion_words(int64_t X, int64_t Y, int64_t Z) { return X * Y * ((Z + kWave - 1) / kWave); }
 
@@ -293,8 +276,8 @@ template <int N>
 void launch_dilate(const word_t* bits, int16_t* out, int X, int Y, int Z, int W, hipStream_t st) {
   const int tiles_y = (Y + kTileY - 1) / kTileY, tiles_w = (W + kTileW - 1) / kTileW;
   const int64_t tiles = int64_t{(X + kTileX - 1) / kTileX} * tiles_y * tiles_w;
-  const int blocks = static_cast<int>(tiles < kMaxBlocks ? tiles : kMaxBlocks);
-  lesion_dilate_kernel<N><<<blocks, kBlock, 0, st>>>(bits, out, X, Y, Z, W, tiles_y, tiles_w, tiles);
+  lesion_dilate_kernel<N><<<blocks_for(tiles, 1, kMaxBlocks), kBlock, 0, st>>>(bits, out, X, Y, Z, W, tiles_y, tiles_w,
+                                                                               tiles);
 }
 
 }  // namespace
@@ -327,9 +310,8 @@ extern "C" int32_t gts_lesionwise_dilate_i16(const int16_t* labels, int64_t X, i
   hipStream_t st = static_cast<hipStream_t>(stream);
   word_t* bits = static_cast<word_t*>(workspace);
   const int W = static_cast<int>((Z + kWave - 1) / kWave);
-  const int64_t pack_blocks = (words + kWavesPerBlock - 1) / kWavesPerBlock;
-  lesion_pack_kernel<<<static_cast<int>(pack_blocks < kMaxBlocks ? pack_blocks : kMaxBlocks), kBlock, 0, st>>>(
-      labels, bits, words, W, static_cast<int>(Z), region);
+  lesion_pack_kernel<<<blocks_for(words, kWavesPerBlock, kMaxBlocks), kBlock, 0, st>>>(labels, bits, words, W,
+                                                                                      static_cast<int>(Z), region);
   const int x = static_cast<int>(X), y = static_cast<int>(Y), z = static_cast<int>(Z);
   switch (dilation) {
     case 0: launch_dilate<0>(bits, mask_out, x, y, z, W, st); break;
@@ -365,7 +347,7 @@ extern "C" int32_t gts_lesionwise_tables_i16(const int16_t* truth, const int32_t
 
   if (hipMemsetAsync(cursors, 0, kHeaderBytes, st) != hipSuccess) return launch_status();
   if (hipMemsetAsync(rows, 0, 2 * row_bytes, st) != hipSuccess) return launch_status();
-  const int blocks = static_cast<int>((n + kBlock - 1) / kBlock);
+  const int blocks = blocks_for(n, kBlock);
   const int cap = static_cast<int>(cells);
   lesion_slots_kernel<<<blocks, kBlock, 0, st>>>(pred_roots, dilated_roots, slot_p, slot_d, lesions, comps, cursors, n,
                                                  cap);
@@ -393,7 +375,7 @@ extern "C" int32_t gts_lesionwise_masks_i16(const int16_t* truth, const int32_t*
     if (box[2 * a] < 0 || box[2 * a] >= box[2 * a + 1] || box[2 * a + 1] > extent[a]) return GTS_ERR_SHAPE;
   const int64_t cx = box[1] - box[0], cy = box[3] - box[2], cz = box[5] - box[4];
   const int64_t count = cx * cy * cz;  // <= n
-  lesion_masks_kernel<<<static_cast<int>((count + kBlock - 1) / kBlock), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
+  lesion_masks_kernel<<<blocks_for(count, kBlock), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
       truth, pred_roots, dilated_roots, matched_roots, static_cast<int>(n_matched), lesion_root, region,
       static_cast<int>(Y), static_cast<int>(Z), static_cast<int>(box[0]), static_cast<int>(box[2]),
       static_cast<int>(box[4]), static_cast<int>(cy), static_cast<int>(cz), count, mask_m, mask_g);

@@ -9,7 +9,7 @@
 // the columns are summed per workgroup into one row of caller-owned scratch, and a one-workgroup
 // second kernel adds the rows to the caller's int64 table (thousands of same-address atomics
 // from the first kernel would cost more than the whole streaming pass).  Integer sums: exact.
-#include "gts_common.h"
+#include "gts_volume.h"
 
 namespace gts {
 namespace {
@@ -53,8 +53,7 @@ __global__ __launch_bounds__(kBlock) void label_confusion_kernel(
     unsigned long long s = 0;
 #pragma unroll
     for (int c = lane; c < kBlock; c += kWave) s += hist[b][c];
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, kWave);
+    s = wave_sum(s);
     if (lane == 0) partial[static_cast<size_t>(blockIdx.x) * kBins + b] = s;
   }
 }

@@ -3,7 +3,7 @@
 // by a voxel bit mask) share.  The element source is a template parameter of the histogram kernel; the
 // select state, the step kernel and the workspace layout are the same for both.
 #pragma once
-#include "gts_common.h"
+#include "gts_volume.h"
 
 namespace gts {
 namespace {
@@ -159,11 +159,6 @@ inline bool volume_ok(int64_t X, int64_t Y, int64_t Z) {
          X * Y * Z < (int64_t{1} << 31);
 }
 
-inline int grid_for(int64_t n) {
-  const int64_t b = (n + kBlock - 1) / kBlock;
-  return static_cast<int>(b < kMaxBlocks ? b : kMaxBlocks);
-}
-
 // The four passes over n elements of `source`; out (device float32 [4][2]) is written by the last step.
 template <typename T, typename Source>
 inline void run_select(const T* src, size_t vol, const Source& source, int64_t n, int64_t rank_lo, int64_t rank_hi,
@@ -171,7 +166,7 @@ inline void run_select(const T* src, size_t vol, const Source& source, int64_t n
   char* ws = static_cast<char*>(workspace);
   unsigned* hist = reinterpret_cast<unsigned*>(ws + kLayout.hist);
   SelectState* state = reinterpret_cast<SelectState*>(ws + kLayout.state);
-  const int grid = grid_for(n);
+  const int grid = blocks_for(n, kBlock, kMaxBlocks);
   intake_select_init_kernel<<<1, kBlock, 0, st>>>(hist, state, static_cast<unsigned long long>(rank_lo),
                                                   static_cast<unsigned long long>(rank_hi));
   for (int shift = 24; shift >= 0; shift -= 8) {

@@ -1,0 +1,54 @@
+"""What the wrappers of the label-volume kernels (csrc/gts_volume.h's includers) share: the shape rule, the
+checks on an int16 label tensor and the workspace of an entry point.  `what` is the caller's public name and
+leads every message."""
+import torch
+
+from . import _lib
+from ._lib import require_device
+
+
+def lift_shape(shape, what):
+    """(X, Y, Z, all_border) of an array shape: the axes of extent 1 dropped, the rest right-aligned in 3-D.
+    A unit axis has no neighbours along it, so components are the same; it makes scipy's erosion (border_value
+    0, cross footprint of the full rank) remove every voxel, so every region voxel is then border (all_border).
+    More than three axes longer than 1: GtsError."""
+    shape = tuple(int(s) for s in shape) or (1,)
+    long_axes = [s for s in shape if s != 1]
+    if len(long_axes) > 3:
+        raise _lib.GtsError(f"{what}: {len(long_axes)} axes longer than 1 in {shape} (at most 3)")
+    x, y, z = [1] * (3 - len(long_axes)) + long_axes
+    return x, y, z, any(s == 1 for s in shape)
+
+
+def label_volume(t, what, three_d=False):
+    """t, contiguous, after the checks every kernel needs: an int16 CUDA tensor with at least one element
+    ([X, Y, Z] where three_d)."""
+    if not isinstance(t, torch.Tensor):
+        raise _lib.GtsError(f"{what} takes a torch tensor")
+    if t.dtype != torch.int16:
+        raise _lib.GtsError(f"{what} takes int16 labels")
+    if three_d and t.dim() != 3:
+        raise _lib.GtsError(f"{what} takes [X, Y, Z] volumes, got shape {tuple(t.shape)}")
+    if t.numel() == 0:
+        raise _lib.GtsError(f"{what}: empty volume")
+    if not t.is_cuda:
+        require_device(t)          # raises: there is no CPU route
+    return t.contiguous()
+
+
+def label_pair(pred, truth, what, three_d=False):
+    """label_volume of both, of one shape and on one device."""
+    pred, truth = label_volume(pred, what, three_d), label_volume(truth, what, three_d)
+    if pred.shape != truth.shape:
+        raise _lib.GtsError(f"{what}: shapes {tuple(pred.shape)} and {tuple(truth.shape)} differ")
+    require_device(pred, truth)
+    return pred, truth
+
+
+def workspace(size_fn, x, y, z, device, what):
+    """(uint8 tensor, its size) for a volume, size_fn being the library's gts_*_workspace(X, Y, Z); a size of
+    0 is the library's refusal."""
+    size = size_fn(x, y, z)
+    if size <= 0:
+        raise _lib.GtsError(f"{what}: volume {x}x{y}x{z} is outside the kernels' limits")
+    return torch.empty(size, dtype=torch.uint8, device=device), size

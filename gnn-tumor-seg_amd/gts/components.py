@@ -8,48 +8,38 @@ give on the host, voxel for voxel, and run on the current stream.
 """
 import torch
 
-from . import _lib
+from . import _lib, _volume
 from ._lib import check, current_stream, ptr, require_device
 
 
 def lift_shape(shape):
-    """(X, Y, Z) of an array shape as gts.metrics.lift_shape lifts it: the axes of extent 1 dropped, the rest
-    right-aligned in 3-D.  A unit axis has no neighbours along it, so the components are the same."""
-    shape = tuple(int(s) for s in shape) or (1,)
-    long_axes = [s for s in shape if s != 1]
-    if len(long_axes) > 3:
-        raise _lib.GtsError(f"components: {len(long_axes)} axes longer than 1 in {shape} (at most 3)")
-    return tuple([1] * (3 - len(long_axes)) + long_axes)
+    """(X, Y, Z) of an array shape: gts._volume.lift_shape without the border flag."""
+    return _volume.lift_shape(shape, "components")[:3]
 
 
 def _prepare(labels, connectivity, what):
-    if not isinstance(labels, torch.Tensor):
-        raise _lib.GtsError(f"{what} takes a torch tensor")
-    if labels.dtype != torch.int16:
-        raise _lib.GtsError(f"{what} takes int16 labels")
-    if labels.numel() == 0:
-        raise _lib.GtsError(f"{what}: empty volume")
     if connectivity not in (6, 26):
         raise _lib.GtsError(f"{what}: connectivity {connectivity!r} (6 or 26)")
-    if not labels.is_cuda:
-        require_device(labels)          # raises: there is no CPU route
-    x, y, z = lift_shape(labels.shape)
+    labels = _volume.label_volume(labels, what)
+    return labels, lift_shape(labels.shape)
+
+
+def roots_unchecked(labels, extents, connectivity, what):
+    """C1-C3 of a volume label_volume has passed, with (X, Y, Z) = extents."""
     lib = _lib.load()
-    size = lib.gts_components_workspace(x, y, z)
-    if size <= 0:
-        raise _lib.GtsError(f"{what}: volume {x}x{y}x{z} is outside the kernels' limits")
-    labels = labels.contiguous()
-    return lib, labels, (x, y, z), torch.empty(size, dtype=torch.uint8, device=labels.device), size
+    x, y, z = extents
+    workspace, size = _volume.workspace(lib.gts_components_workspace, x, y, z, labels.device, what)
+    roots = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
+    check(lib.gts_components_roots_i16(ptr(labels), x, y, z, connectivity, ptr(roots), ptr(workspace), size,
+                                       current_stream()), "gts_components_roots_i16")
+    return roots
 
 
 def component_roots(labels, connectivity=26):
     """int32 tensor of labels' shape: 1 + the smallest C-order linear index of the voxel's component of
     labels != 0, 0 for background.  labels: int16 CUDA tensor, at most three axes longer than 1."""
-    lib, labels, (x, y, z), workspace, size = _prepare(labels, connectivity, "component_roots")
-    roots = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
-    check(lib.gts_components_roots_i16(ptr(labels), x, y, z, connectivity, ptr(roots), ptr(workspace), size,
-                                       current_stream()), "gts_components_roots_i16")
-    return roots
+    labels, extents = _prepare(labels, connectivity, "component_roots")
+    return roots_unchecked(labels, extents, connectivity, "component_roots")
 
 
 def remove_small_components(labels, min_voxels, connectivity=26, *, et_label=None, et_min_voxels=0,
@@ -58,7 +48,9 @@ def remove_small_components(labels, min_voxels, connectivity=26, *, et_label=Non
     min_voxels voxels set to 0, then (b) when et_min_voxels > 0 and fewer than that many (but some) voxels equal
     to et_label remain, each of them set to et_replacement.  stats: device int64 [4] = components found,
     components removed, voxels removed, ET voxels relabelled.  `out` may be labels itself (in place)."""
-    lib, src, (x, y, z), workspace, size = _prepare(labels, connectivity, "remove_small_components")
+    src, (x, y, z) = _prepare(labels, connectivity, "remove_small_components")
+    lib = _lib.load()
+    workspace, size = _volume.workspace(lib.gts_components_workspace, x, y, z, src.device, "remove_small_components")
     et_min_voxels = int(et_min_voxels)
     if et_min_voxels > 0 and (et_label is None or et_replacement is None):
         raise _lib.GtsError("remove_small_components: et_min_voxels needs et_label and et_replacement")

@@ -15,8 +15,8 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, metrics
-from ._lib import check, current_stream, ptr, require_device
+from . import _lib, _volume, components, metrics
+from ._lib import check, current_stream, ptr
 
 REGIONS = ("WT", "CT", "ET")
 DILATIONS = (0, 1, 2, 3)
@@ -33,28 +33,6 @@ def _region_index(region):
     raise _lib.GtsError(f"lesionwise: region {region!r} (one of {REGIONS} or 0..2)")
 
 
-def _volume(labels, what):
-    if not isinstance(labels, torch.Tensor):
-        raise _lib.GtsError(f"{what} takes torch tensors")
-    if labels.dtype != torch.int16:
-        raise _lib.GtsError(f"{what} takes int16 labels")
-    if labels.dim() != 3:
-        raise _lib.GtsError(f"{what} takes [X, Y, Z] volumes, got shape {tuple(labels.shape)}")
-    if labels.numel() == 0:
-        raise _lib.GtsError(f"{what}: empty volume")
-    if not labels.is_cuda:
-        require_device(labels)          # raises: there is no CPU route
-    return labels.contiguous()
-
-
-def _pair(pred, truth, what):
-    pred, truth = _volume(pred, what), _volume(truth, what)
-    if pred.shape != truth.shape:
-        raise _lib.GtsError(f"{what}: shapes {tuple(pred.shape)} and {tuple(truth.shape)} differ")
-    require_device(pred, truth)
-    return pred, truth
-
-
 def _dilation(dilation, what):
     if isinstance(dilation, bool) or dilation not in DILATIONS:
         raise _lib.GtsError(f"{what}: dilation {dilation!r} (one of {DILATIONS})")
@@ -62,11 +40,7 @@ def _dilation(dilation, what):
 
 
 def _workspace(lib, labels, what):
-    x, y, z = labels.shape
-    size = lib.gts_lesionwise_workspace(x, y, z)
-    if size <= 0:
-        raise _lib.GtsError(f"{what}: volume {x}x{y}x{z} is outside the kernels' limits")
-    return torch.empty(size, dtype=torch.uint8, device=labels.device), size
+    return _volume.workspace(lib.gts_lesionwise_workspace, *labels.shape, labels.device, what)
 
 
 def _dilate(lib, labels, region, dilation, workspace, size):
@@ -77,21 +51,11 @@ def _dilate(lib, labels, region, dilation, workspace, size):
     return out
 
 
-def _roots(lib, mask):
-    x, y, z = mask.shape
-    size = lib.gts_components_workspace(x, y, z)
-    workspace = torch.empty(size, dtype=torch.uint8, device=mask.device)
-    roots = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
-    check(lib.gts_components_roots_i16(ptr(mask), x, y, z, 26, ptr(roots), ptr(workspace), size, current_stream()),
-          "gts_components_roots_i16")
-    return roots
-
-
 def dilate_region(labels, region, dilation=3):
     """int16 0 / 1 tensor of labels' shape: scipy's binary_dilation(region mask of labels,
     generate_binary_structure(3, 2), iterations=dilation), clipped at the volume.  labels: int16 CUDA tensor
     [X, Y, Z] of internal labels; region "WT", "CT" or "ET" (or 0..2); dilation 0..3."""
-    labels = _volume(labels, "dilate_region")
+    labels = _volume.label_volume(labels, "dilate_region", three_d=True)
     region, dilation = _region_index(region), _dilation(dilation, "dilate_region")
     lib = _lib.load()
     workspace, size = _workspace(lib, labels, "dilate_region")
@@ -111,8 +75,9 @@ class _RegionState:
         self.lib, self.truth, self.region, self.shape = lib, truth, region, tuple(truth.shape)
         x, y, z = self.shape
         workspace, size = _workspace(lib, truth, what)
-        self.roots_p = _roots(lib, _dilate(lib, pred, region, 0, workspace, size))
-        self.roots_d = _roots(lib, _dilate(lib, truth, region, dilation, workspace, size))
+        mask_p, mask_d = (_dilate(lib, v, region, n, workspace, size) for v, n in ((pred, 0), (truth, dilation)))
+        self.roots_p = components.roots_unchecked(mask_p, self.shape, 26, what)
+        self.roots_d = components.roots_unchecked(mask_d, self.shape, 26, what)
         ints = lib.gts_lesionwise_table_ints(x, y, z)
         block = torch.empty(ints, dtype=torch.int32, device=truth.device)
         check(lib.gts_lesionwise_tables_i16(ptr(truth), ptr(self.roots_p), ptr(self.roots_d), x, y, z, region,
@@ -179,7 +144,7 @@ def lesion_tables(pred, truth, region, dilation=3):
     """The integer tables of one region, as Python lists in lesion order (ascending smallest C-order index of
     the dilated lesion, scipy's label order): lesion_roots, vol (|G_k|), tp (|P n G_k|), matched_voxels (|M_k|),
     matched_components (indices into comp_roots / comp_sizes, which are in component order), n_fp."""
-    pred, truth = _pair(pred, truth, "lesion_tables")
+    pred, truth = _volume.label_pair(pred, truth, "lesion_tables", three_d=True)
     region, dilation = _region_index(region), _dilation(dilation, "lesion_tables")
     return _RegionState(_lib.load(), pred, truth, region, dilation).tables()
 
@@ -222,7 +187,7 @@ def lesionwise_scores(pred, truth, dilation=3, min_lesion_voxels=50):
 
     from . import ops
 
-    pred, truth = _pair(pred, truth, "lesionwise_scores")
+    pred, truth = _volume.label_pair(pred, truth, "lesionwise_scores", three_d=True)
     dilation = _dilation(dilation, "lesionwise_scores")
     lib = _lib.load()
     dices = evaluation.dices_from_confusion(ops.label_confusion(pred, truth).cpu().numpy())

@@ -8,8 +8,8 @@ import math
 
 import torch
 
-from . import _lib
-from ._lib import check, current_stream, ptr, require_device
+from . import _lib, _volume
+from ._lib import check, current_stream, ptr
 
 ABSENT_FROM_ONE = 300     # calculate_hd95_from_logical_array: the region is missing from one side only
 ABSENT_FROM_BOTH = 0
@@ -32,15 +32,8 @@ def percentile95_from_order_stats(n, d2_lo, d2_hi):
 
 
 def lift_shape(shape):
-    """(X, Y, Z, all_border) of an array shape: the axes of extent 1 dropped, the rest right-aligned in 3-D.
-    A unit axis makes scipy's erosion (border_value 0, cross footprint of the full rank) remove every voxel,
-    so every region voxel is then border.  More than three axes longer than 1: GtsError."""
-    shape = tuple(int(s) for s in shape) or (1,)
-    long_axes = [s for s in shape if s != 1]
-    if len(long_axes) > 3:
-        raise _lib.GtsError(f"hd95s: {len(long_axes)} axes longer than 1 in {shape} (at most 3)")
-    x, y, z = [1] * (3 - len(long_axes)) + long_axes
-    return x, y, z, any(s == 1 for s in shape)
+    """(X, Y, Z, all_border) of an array shape: gts._volume.lift_shape."""
+    return _volume.lift_shape(shape, "hd95s")
 
 
 def hd95_order_stats(pred, truth):
@@ -48,20 +41,10 @@ def hd95_order_stats(pred, truth):
     ranks np.percentile(., 95) interpolates between, and the presence bits (1 pred, 2 truth) — see
     gts_hd95_order_stats_i16 in include/gts_hip.h.  pred / truth: int16 CUDA tensors of one shape with at
     most three axes longer than 1, at least one element."""
-    if pred.dtype != torch.int16 or truth.dtype != torch.int16:
-        raise _lib.GtsError("hd95s takes int16 labels")
-    if pred.shape != truth.shape:
-        raise _lib.GtsError(f"hd95s: shapes {tuple(pred.shape)} and {tuple(truth.shape)} differ")
-    if pred.numel() == 0:
-        raise _lib.GtsError("hd95s: empty volumes")
-    pred, truth = pred.contiguous(), truth.contiguous()
-    require_device(pred, truth)
+    pred, truth = _volume.label_pair(pred, truth, "hd95s")
     x, y, z, all_border = lift_shape(pred.shape)
     lib = _lib.load()
-    size = lib.gts_hd95_workspace(x, y, z)
-    if size <= 0:
-        raise _lib.GtsError(f"hd95s: volume {x}x{y}x{z} is outside the kernels' limits")
-    workspace = torch.empty(size, dtype=torch.uint8, device=pred.device)
+    workspace, size = _volume.workspace(lib.gts_hd95_workspace, x, y, z, pred.device, "hd95s")
     out = torch.empty((3, 4), dtype=torch.int64, device=pred.device)
     check(lib.gts_hd95_order_stats_i16(ptr(pred), ptr(truth), x, y, z, int(all_border), ptr(out), ptr(workspace),
                                        size, current_stream()), "gts_hd95_order_stats_i16")
