@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GTS_LIB_PATH: another build of the same library (A/B runs of two builds in one session, tools/); the default is the in-tree build
 LIB_PATH = os.environ.get("GTS_LIB_PATH") or os.path.join(_HERE, "libgts_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "gts_hip.h")
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -83,6 +83,9 @@ SIGNATURES = {
     "gts_get_option": [_i32],
     "gts_weighted_ce_workspace": [_i64],
     "gts_weighted_ce_f32": [_p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _p],
+    "gts_dice_ce_workspace": [_i64, _i32],
+    "gts_dice_ce_fwd_f32": [_p, _p, _p, _p, _i32, _f64, _f64, _f64, _p, _p, _i64, _i64, _i64, _p],
+    "gts_dice_ce_bwd_f32": [_p, _p, _p, _p, _i32, _f64, _f64, _f64, _p, _p, _p, _i64, _i64, _p],
     "gts_collate_plan": [_p, _i32, _i64, _p, _i32, _p],
     "gts_collate_batch": [_p, _i32, _i64, _p, _i32, _p, _i64, _i32, _p],
     "gts_gg_gaussian_f64": [_p, _p, _p, _p, _i32, _f64, _i64, _i64, _i64, _i64, _p],
@@ -125,6 +128,7 @@ SIGNATURES = {
 }
 _RESTYPE = {"gts_error_string": ctypes.c_char_p, "gts_linear_bwd_weight_workspace": _i64,
             "gts_weighted_ce_workspace": _i64, "gts_gat_reduce_workspace": _i64,
+            "gts_dice_ce_workspace": _i64,
             "gts_label_confusion_workspace": _i64, "gts_gat_fc_scores_workspace": _i64,
             "gts_relu_bits_bytes": _i64, "gts_cluster_record_words": _i64, "gts_sage_pool_stack_fwd_arena": _i64, "gts_sage_pool_stack_bwd_scratch": _i64, "gts_cluster_lds_bytes": _i64,
             "gts_linear_bwd_input_t_act_workspace": _i64, "gts_gat_cluster_workspace": _i64,

@@ -3,6 +3,8 @@
 Every function here enqueues on torch's current HIP stream and returns torch tensors that
 own the memory; nothing falls back to PyTorch or the CPU when the library is missing.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -775,6 +777,93 @@ def weighted_cross_entropy(logits, labels, class_w=None, reduction="mean"):
     if reduction == "sum":
         return total
     raise ValueError(reduction)
+
+
+# ---------------------------------------------------------------- soft Dice + class-weighted cross-entropy
+DICE_MAX_GROUPS = 8            # GTS_DICE_CE_MAX_GROUPS
+DICE_STATS_FLOATS = 40         # GTS_DICE_CE_STATS_FLOATS; offsets below as in include/gts_hip.h
+_DICE_LOSS, _DICE_CE, _DICE_LDICE, _DICE_DICE = 0, 1, 2, 8
+
+
+def dice_region_masks(regions, n_classes):
+    """Bitmasks over the classes of a named region set or of a sequence of class-index sequences.
+    "brats": WT {1,2,3}, CT {2,3}, ET {3} of the internal labels (needs 4 classes); "classes": one region per
+    class 1..C-1, background left out."""
+    if isinstance(regions, str):
+        if regions == "brats":
+            if n_classes != 4:
+                raise _lib.GtsError(f'regions "brats" are sets of the 4 internal labels: got {n_classes} classes')
+            regions = ((1, 2, 3), (2, 3), (3,))
+        elif regions == "classes":
+            regions = tuple((c,) for c in range(1, n_classes))
+        else:
+            raise _lib.GtsError(f'unknown region set "{regions}": "brats", "classes" or a sequence of class sets')
+    masks = []
+    for members in regions:
+        members = [int(c) for c in members]
+        if not members or min(members) < 0 or max(members) >= n_classes:
+            raise _lib.GtsError(f"a Dice region is a non-empty set of classes in [0, {n_classes}): got {members}")
+        masks.append(sum(1 << c for c in set(members)))
+    if not 1 <= len(masks) <= DICE_MAX_GROUPS:
+        raise _lib.GtsError(f"1 to {DICE_MAX_GROUPS} Dice regions, got {len(masks)}")
+    return tuple(masks)
+
+
+class _DiceCE(torch.autograd.Function):
+    """(logits [N,C], labels int64 [N], class_w [C] or None, region masks, weights) -> (loss, stats [40]).
+    The forward runs the statistics pass (D1) alone; the gradient pass (D2) is launched from backward, takes the
+    upstream gradient as a device scalar and writes the final gradient once."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, class_w, masks, ce_weight, dice_weight, smooth):
+        logits, labels = logits.contiguous(), labels.contiguous()
+        _f32(logits, class_w)
+        require_device(logits, labels, class_w)
+        if logits.dim() != 2 or labels.dtype != torch.int64 or labels.shape != logits.shape[:1]:
+            raise _lib.GtsError("Dice + CE takes logits [N, C] and int64 labels [N]")
+        n, c = logits.shape
+        _expect(class_w, (c,), "class_w")
+        lib = _lib.load()
+        host_masks = (ctypes.c_uint32 * len(masks))(*masks)
+        ws = torch.empty(max(1, lib.gts_dice_ce_workspace(n, len(masks)) // 4), dtype=torch.float32,
+                         device=logits.device)
+        stats = torch.empty(DICE_STATS_FLOATS, dtype=torch.float32, device=logits.device)
+        check(lib.gts_dice_ce_fwd_f32(ptr(logits), ptr(labels), ptr(class_w), host_masks, len(masks), ce_weight,
+                                      dice_weight, smooth, ptr(stats), ptr(ws), ws.numel() * 4, n, c,
+                                      current_stream()), "gts_dice_ce_fwd_f32")
+        ctx.save_for_backward(logits, labels, class_w, stats)
+        ctx.terms = (host_masks, len(masks), ce_weight, dice_weight, smooth)
+        ctx.mark_non_differentiable(stats)
+        return stats[_DICE_LOSS].clone(), stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, _g_stats):
+        logits, labels, class_w, stats = ctx.saved_tensors
+        host_masks, n_groups, ce_weight, dice_weight, smooth = ctx.terms
+        scale = g_loss.to(torch.float32).contiguous()
+        grad = torch.empty_like(logits)
+        check(_lib.load().gts_dice_ce_bwd_f32(ptr(logits), ptr(labels), ptr(class_w), host_masks, n_groups,
+                                              ce_weight, dice_weight, smooth, ptr(stats), ptr(scale), ptr(grad),
+                                              logits.shape[0], logits.shape[1], current_stream()),
+              "gts_dice_ce_bwd_f32")
+        return grad, None, None, None, None, None, None
+
+
+def dice_ce_loss(logits, labels, class_w=None, *, regions="brats", ce_weight=1.0, dice_weight=1.0, smooth=1.0,
+                 return_parts=False):
+    """ce_weight * weighted cross-entropy + dice_weight * (1 - mean soft Dice over `regions`) of voxel logits
+    [N, C] against int64 labels [N], as two fused HIP passes.  Rows labelled -100 are ignored.
+    regions: "brats", "classes" or a sequence of class-index sequences (dice_region_masks).  A term of weight 0
+    is skipped.  return_parts: also a tensor [CE, L_dice, dice_0 .. dice_{G-1}] that carries no gradient."""
+    ce_weight, dice_weight, smooth = float(ce_weight), float(dice_weight), float(smooth)
+    if logits.dim() != 2:
+        raise _lib.GtsError("Dice + CE takes logits [N, C] and int64 labels [N]")
+    masks = dice_region_masks(regions, logits.shape[1])
+    loss, stats = _DiceCE.apply(logits, labels, class_w, masks, ce_weight, dice_weight, smooth)
+    if not return_parts:
+        return loss
+    return loss, torch.cat([stats[_DICE_CE:_DICE_LDICE + 1], stats[_DICE_DICE:_DICE_DICE + len(masks)]])
 
 
 def weighted_ce_numerator_grad(logits, labels, class_w=None):

@@ -19,6 +19,7 @@ from gts.conv3d import refinement_logits
 from gts.optim import FlatAdamW
 
 from . import evaluation
+from .losses import make_voxel_loss
 from .networks import CnnRefinementNet
 
 
@@ -37,13 +38,16 @@ class RefinementModel:
       * a sample whose logit file is missing is skipped (FileNotFoundError), in training and in evaluation;
       * in `evaluate` the row of such a sample stays all zeros and is still averaged into the returned mean.
     HD95 is computed, as in the reference, on the [1, cx, cy, cz] arrays of the crop.
+    `voxel_loss`: a callable (logits, labels) -> loss from model.losses.make_voxel_loss (soft Dice + cross-entropy);
+    None is the reference's class-weighted cross-entropy.  Column 0 of `evaluate` is the configured loss.
     """
 
-    def __init__(self, hyperparameters, train_dataset, logit_dataset, prefetch=True):
+    def __init__(self, hyperparameters, train_dataset, logit_dataset, prefetch=True, voxel_loss=None):
         if not torch.cuda.is_available():
             raise RuntimeError("RefinementModel trains on an AMD GPU only (no CPU path)")
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.class_weights = torch.tensor(hyperparameters.class_weights, dtype=torch.float32, device=self.device)
+        self.voxel_loss = voxel_loss if voxel_loss is not None else make_voxel_loss("ce", self.class_weights)
         self.net = CnnRefinementNet(hyperparameters.in_feats, hyperparameters.out_classes,
                                     hyperparameters.layer_sizes).to(self.device)
         self.optimizer = FlatAdamW(self.net.parameters(), lr=hyperparameters.lr,
@@ -114,7 +118,7 @@ class RefinementModel:
         """One forward / backward / AdamW step on a cropped sample already on the device; returns the loss
         as a device scalar."""
         logits = refinement_logits(x, self.net)
-        loss = ops.weighted_cross_entropy(logits, y, self.class_weights)
+        loss = self.voxel_loss(logits, y)
         self.optimizer.zero_grad()
         loss.backward()
         self.optimizer.step()
@@ -146,7 +150,7 @@ class RefinementModel:
             shape = tuple(sample[0].shape[:3])
             x, y = (t.to(self.device) for t in sample)
             logits = refinement_logits(x, self.net)
-            loss = ops.weighted_cross_entropy(logits, y, self.class_weights)
+            loss = self.voxel_loss(logits, y)
             pred = torch.argmax(logits, dim=1).to(torch.int16)
             truth = y.to(torch.int16)
             confusion = ops.label_confusion(pred, truth)

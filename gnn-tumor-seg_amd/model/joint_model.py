@@ -26,6 +26,7 @@ from gts.optim import FlatAdamW
 from utils.hyperparam_helpers import DEFAULT_BACKGROUND_NODE_LOGITS
 
 from . import evaluation
+from .losses import make_voxel_loss
 from .networks import CnnRefinementNet, init_graph_net
 
 MAX_CACHED_SAMPLES = 32     # samples whose partitioning and voxel lists stay on the device between epochs
@@ -43,9 +44,12 @@ class JointModel:
     set, those of the node loss from the GNN set.  `gnn_loss_weight = 0` trains both networks on the voxel
     loss alone.  `gnn_weights` / `cnn_weights`: optional checkpoints to start from (the intended use is
     fine-tuning a trained pair: an untrained GNN predicts tumour everywhere, so the crop is the whole
-    brain).  Single GPU only."""
+    brain).  `voxel_loss`: a callable (logits, labels) -> loss from model.losses.make_voxel_loss (soft Dice +
+    cross-entropy) that replaces the voxel cross-entropy, in training and in column 0 of `evaluate`; None keeps the
+    cross-entropy.  The node loss stays cross-entropy.  Single GPU only."""
 
-    def __init__(self, gnn_type, gnn_hp, cnn_hp, dataset, gnn_loss_weight=1.0, gnn_weights=None, cnn_weights=None):
+    def __init__(self, gnn_type, gnn_hp, cnn_hp, dataset, gnn_loss_weight=1.0, gnn_weights=None, cnn_weights=None,
+                 voxel_loss=None):
         if not torch.cuda.is_available():
             raise RuntimeError("JointModel needs an AMD GPU (MI355X): the HIP kernels have no CPU fallback")
         if gdist.world()[1] > 1:
@@ -62,6 +66,7 @@ class JointModel:
             self.conv_net.load_state_dict(torch.load(cnn_weights, map_location=self.device, weights_only=True))
         self.gnn_class_weights = torch.tensor(gnn_hp.class_weights, dtype=torch.float32, device=self.device)
         self.cnn_class_weights = torch.tensor(cnn_hp.class_weights, dtype=torch.float32, device=self.device)
+        self.voxel_loss = voxel_loss if voxel_loss is not None else make_voxel_loss("ce", self.cnn_class_weights)
         self.bg_row = torch.tensor(DEFAULT_BACKGROUND_NODE_LOGITS, dtype=torch.float32, device=self.device).reshape(-1)
         self.gnn_optimizer = FlatAdamW(self.graph_net.parameters(), lr=gnn_hp.lr, weight_decay=gnn_hp.w_decay)
         self.cnn_optimizer = FlatAdamW(self.conv_net.parameters(), lr=cnn_hp.lr, weight_decay=cnn_hp.w_decay)
@@ -121,7 +126,7 @@ class JointModel:
         as a device scalar."""
         node_logits, box, voxel_logits = self._voxel_logits(graph, feats, img, svs, lists)
         self.last_box, self.last_node_logits = box, node_logits.detach()
-        loss = ops.weighted_cross_entropy(voxel_logits, self.cropped_labels(voxel_labels, box), self.cnn_class_weights)
+        loss = self.voxel_loss(voxel_logits, self.cropped_labels(voxel_labels, box))
         if self.gnn_loss_weight:
             loss = loss + self.gnn_loss_weight * ops.weighted_cross_entropy(node_logits, node_labels,
                                                                             self.gnn_class_weights)
@@ -151,7 +156,7 @@ class JointModel:
     # ---------------------------------------------------------------- evaluation
     @torch.no_grad()
     def evaluate(self, dataset):
-        """Mean over `dataset` of [voxel cross-entropy, WT / CT / ET voxel Dice, WT / CT / ET HD95] inside each
+        """Mean over `dataset` of [voxel loss, WT / CT / ET voxel Dice, WT / CT / ET HD95] inside each
         sample's own crop, from the joint forward (the columns of RefinementModel.evaluate)."""
         self.graph_net.eval()
         self.conv_net.eval()
@@ -164,7 +169,7 @@ class JointModel:
             x = ops.crop_concat_rows(img, svs, node_logits.contiguous(), self.bg_row, box)
             logits = refinement_logits(x, self.conv_net)
             y = self.cropped_labels(voxel_labels, box)
-            loss = ops.weighted_cross_entropy(logits, y, self.cnn_class_weights)
+            loss = self.voxel_loss(logits, y)
             pred = torch.argmax(logits, dim=1).to(torch.int16)
             truth = y.to(torch.int16)
             confusion = ops.label_confusion(pred, truth)

@@ -1,7 +1,8 @@
 """Train the GNN and the refinement CNN end to end (k-fold validation or the full dataset) on MI355X.
 
   python -m scripts.train_joint -d DATA -o OUT -r RUN [-k FOLDS] [-p PREFIX] [-m GSpool] [-g GNN.pt] [-c CNN.pt]
-                                [-w GNN_LOSS_WEIGHT] [-x]
+                                [-w GNN_LOSS_WEIGHT] [-x] [--loss {ce,dice_ce}] [--dice_weight W]
+                                [--dice_smooth S] [--dice_regions {brats,classes}]
 
 The reference has no such script (its scripts/train_refinement_cnn.py:21-22 names joint training and declines
 to build it); flags, console report, progress file and folds follow scripts/train_refinement_cnn.py.  DATA is
@@ -9,7 +10,8 @@ a preprocessed dataset with graphs, images and labels.  -g / -c are optional che
 intended use is fine-tuning a pair trained by train_gnn and train_refinement_cnn, because an untrained GNN
 predicts tumour everywhere and the crop becomes the whole brain (correct, only slow).  The number of epochs
 comes from the GNN hyper-parameter set.  Checkpoints: `{run}_f{k}_gnn.pt` and `{run}_f{k}_cnn.pt`, which
-generate_joint_predictions and segment_scans load as they load separately trained ones.
+generate_joint_predictions and segment_scans load as they load separately trained ones.  `--loss dice_ce` replaces
+the voxel cross-entropy by cross-entropy + soft Dice (model/losses.py); the node loss stays cross-entropy.
 """
 import argparse
 import os
@@ -18,7 +20,8 @@ from torch.utils.data import Subset
 
 from data_processing.data_loader import ImageGraphDataset
 from model.joint_model import JointModel
-from scripts.train_refinement_cnn import document_metrics, fold_splits
+from scripts.train_refinement_cnn import (add_voxel_loss_arguments, document_metrics, fold_splits,
+                                          voxel_loss_from_args)
 from utils.hyperparam_helpers import generate_random_hyperparameters, populate_hardcoded_hyperparameters
 from utils.training_helpers import create_run_progress_file, train_on_fold
 
@@ -27,7 +30,8 @@ def _model(args, hyperparams, dataset):
     gnn_hp, cnn_hp = hyperparams
     return JointModel(args.gnn_type, gnn_hp, cnn_hp, dataset, gnn_loss_weight=args.gnn_loss_weight,
                       gnn_weights=os.path.expanduser(args.gnn_weights) if args.gnn_weights else None,
-                      cnn_weights=os.path.expanduser(args.cnn_weights) if args.cnn_weights else None)
+                      cnn_weights=os.path.expanduser(args.cnn_weights) if args.cnn_weights else None,
+                      voxel_loss=voxel_loss_from_args(args, cnn_hp.class_weights))
 
 
 def train_on_full_dataset(args, hyperparams, progress_file_fd, dataset):
@@ -72,12 +76,21 @@ def build_parser():
     return parser
 
 
+def build_cli_parser():
+    """The command line `main` takes: the flags above plus the choice of the voxel objective."""
+    parser = build_parser()
+    add_voxel_loss_arguments(parser)
+    return parser
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_cli_parser().parse_args(argv)
     if args.num_folds < 1:
         raise ValueError("Number of folds must be a positive integer")
     if args.gnn_loss_weight < 0:
         raise ValueError("The weight of the node-level loss must not be negative")
+    if args.dice_weight < 0 or not args.dice_smooth > 0:
+        raise ValueError("--dice_weight must not be negative and --dice_smooth must be positive")
     dataset = ImageGraphDataset(os.path.expanduser(args.data_dir), args.data_prefix, read_image=True,
                                 read_graph=True, read_label=True)
     draw = generate_random_hyperparameters if args.random_hyperparams else populate_hardcoded_hyperparameters

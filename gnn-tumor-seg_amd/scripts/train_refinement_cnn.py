@@ -3,11 +3,17 @@
 Command line, console report, progress file and checkpoint names (`{run}_f{k}.pt`) match
 /root/reference/scripts/train_refinement_cnn.py:
   python -m scripts.train_refinement_cnn -d DATA -l LOGITS -o OUT -r RUN [-k FOLDS] [-p PREFIX] [-x]
+                                         [--loss {ce,dice_ce}] [--dice_weight W] [--dice_smooth S]
+                                         [--dice_regions {brats,classes}]
 The logits are the `{id}_logits.nii.gz` files `generate_gnn_predictions -f logits` writes.
 
 One deliberate difference: with k > 1 the reference builds every fold's model on the WHOLE dataset, so its
 validation rows score samples the model was trained on.  Here fold f trains on everything outside its held-out
 range, as scripts/train_gnn.py does.
+
+One addition: `--loss dice_ce` trains on the class-weighted cross-entropy plus `--dice_weight` times the soft Dice
+loss over `--dice_regions` (model/losses.py); the default `ce` is the reference's objective.  The progress file's
+loss column is the configured loss.
 """
 import argparse
 import os
@@ -17,6 +23,7 @@ from torch.utils.data import Subset
 
 from data_processing.data_loader import ImageGraphDataset, PredLogitDataset
 from model.cnn_model import RefinementModel
+from model.losses import VOXEL_LOSS_KINDS, make_voxel_loss
 from utils.hyperparam_helpers import generate_random_hyperparameters, populate_hardcoded_hyperparameters
 from utils.training_helpers import (chunk_dataset_into_folds, create_run_progress_file, train_on_fold,
                                     update_progress_file)
@@ -40,9 +47,32 @@ def fold_splits(n_samples, k):
     return folds
 
 
+def add_voxel_loss_arguments(parser):
+    """The flags that choose the voxel objective (shared with scripts/train_joint.py)."""
+    parser.add_argument("--loss", default="ce", choices=VOXEL_LOSS_KINDS,
+                        help="voxel objective: class-weighted cross-entropy, or that plus the soft Dice loss")
+    parser.add_argument("--dice_weight", default=1.0, type=float, help="weight of the Dice term of --loss dice_ce")
+    parser.add_argument("--dice_smooth", default=1.0, type=float,
+                        help="smoothing constant of the soft Dice (added to numerator and denominator)")
+    parser.add_argument("--dice_regions", default="brats", choices=("brats", "classes"),
+                        help="regions the Dice is averaged over: WT / CT / ET, or each tumour class on its own")
+
+
+def voxel_loss_from_args(args, class_weights):
+    """None for the default cross-entropy (the models then build it themselves), else the configured callable."""
+    if args.loss == "ce":
+        return None
+    import torch
+
+    weights = torch.tensor(class_weights, dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+    return make_voxel_loss(args.loss, weights, dice_weight=args.dice_weight, smooth=args.dice_smooth,
+                           regions=args.dice_regions)
+
+
 def train_on_full_dataset(args, hyperparams, progress_file_fd, image_dataset, logit_dataset):
     print("Training on full dataset")
-    model = RefinementModel(hyperparams, image_dataset, logit_dataset)
+    model = RefinementModel(hyperparams, image_dataset, logit_dataset,
+                            voxel_loss=voxel_loss_from_args(args, hyperparams.class_weights))
     train_on_fold(model, args.output_dir + os.sep, hyperparams.n_epochs, args.run_name, 1)
     metrics = model.evaluate(Subset(image_dataset, range(len(image_dataset))))
     document_metrics(progress_file_fd, f"{args.run_name}_full", metrics)
@@ -53,7 +83,8 @@ def run_k_fold_val(args, hyperparams, progress_file_fd, image_dataset, logit_dat
     for fold, (train_idx, val_idx) in enumerate(fold_splits(len(image_dataset), k), start=1):
         training, held_out = Subset(image_dataset, train_idx), Subset(image_dataset, val_idx)
         print(f"Fold contains {len(training)} examples")
-        model = RefinementModel(hyperparams, training, logit_dataset)
+        model = RefinementModel(hyperparams, training, logit_dataset,
+                                voxel_loss=voxel_loss_from_args(args, hyperparams.class_weights))
         train_on_fold(model, args.output_dir + os.sep, hyperparams.n_epochs, args.run_name, fold)
         document_metrics(progress_file_fd, f"{args.run_name}_f{fold}_train", model.evaluate(training))
         document_metrics(progress_file_fd, f"{args.run_name}_f{fold}_val", model.evaluate(held_out))
@@ -78,10 +109,19 @@ def build_parser():
     return parser
 
 
+def build_cli_parser():
+    """The command line `main` takes: the reference's flags plus the choice of the voxel objective."""
+    parser = build_parser()
+    add_voxel_loss_arguments(parser)
+    return parser
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_cli_parser().parse_args(argv)
     if args.num_folds < 1:
         raise ValueError("Number of folds must be a positive integer")
+    if args.dice_weight < 0 or not args.dice_smooth > 0:
+        raise ValueError("--dice_weight must not be negative and --dice_smooth must be positive")
     image_dataset = ImageGraphDataset(os.path.expanduser(args.data_dir), args.data_prefix, read_image=True,
                                       read_graph=False, read_label=True)
     logit_dataset = PredLogitDataset(os.path.expanduser(args.saved_logit_dir))

@@ -469,6 +469,53 @@ int32_t gts_weighted_ce_f32(const float* logits, const int64_t* labels, const fl
                             float* grad_unscaled, float* workspace, int64_t workspace_bytes,
                             float* out3, int64_t n, int64_t n_classes, void* stream);
 
+/* ---- soft Dice over class regions + class-weighted cross-entropy ---------------
+ * The voxel loss of the refinement CNN and of joint training; no counterpart in the reference, whose
+ * loops train on torch.nn.CrossEntropyLoss alone (model/cnn_model.py).  Two passes:
+ *   fwd (D1): one read of logits [n, n_classes] fp32 and labels int64 [n] -> `stats`;
+ *   bwd (D2): a second read, with `stats` -> grad [n, n_classes] = grad_scale * dL/dlogits, written once.
+ * A row is valid when 0 <= label < n_classes; a label of -100 contributes to no sum and gets a zero
+ * gradient; any other label makes the loss NaN.  Over the valid rows, p = softmax(logits):
+ *   q_ir = sum_{c in region r} p_ic    t_ir = [label_i in region r]
+ *   I_r = sum_i q_ir t_ir   S_r = sum_i q_ir   T_r = sum_i t_ir
+ *   dice_r = (2 I_r + smooth) / (S_r + T_r + smooth)     L_dice = 1 - mean_r dice_r
+ *   CE = sum_i w[y_i] nll_i / sum_i w[y_i]               loss = ce_weight CE + dice_weight L_dice
+ * A term whose weight is 0 is skipped (its part reads 0), so ce_weight = 0 gives a finite loss when no
+ * row is valid.  group_masks: HOST pointer to n_groups bitmasks over the classes (bit c = class c),
+ * read during the call.  class_w [n_classes] optional (NULL = ones).  grad_scale: optional DEVICE
+ * scalar (the upstream gradient; NULL = 1).  The same regions, weights and smooth go to both calls.
+ * logits and grad need only float alignment: at n_classes = 4 a 16-byte aligned base takes the form that
+ * moves a row as one 16-byte access, any other base the float-by-float form (same definition).
+ * Deterministic: fixed-association sums through `workspace` (>= gts_dice_ce_workspace bytes), the last
+ * level in float64; no atomics.
+ * Errors, before any launch: NULL pointer -> GTS_ERR_NULL; n <= 0, n_classes outside [1, 32],
+ * n_groups outside [1, 8], short workspace -> GTS_ERR_SHAPE; an empty mask, a mask bit >= n_classes,
+ * a negative or non-finite weight, smooth <= 0 or non-finite -> GTS_ERR_ARGKIND.
+ * stats: GTS_DICE_CE_STATS_FLOATS floats, entries not named below are 0:
+ *   [0] loss  [1] CE  [2] L_dice  [3] CE numerator  [4] CE denominator
+ *   [8 + r] dice_r   [16 + r] I_r   [24 + r] S_r   [32 + r] T_r      (r < n_groups) */
+#define GTS_DICE_CE_MAX_GROUPS 8
+#define GTS_DICE_CE_STATS_FLOATS 40
+#define GTS_DICE_CE_STATS_LOSS 0
+#define GTS_DICE_CE_STATS_CE 1
+#define GTS_DICE_CE_STATS_LDICE 2
+#define GTS_DICE_CE_STATS_CE_NUM 3
+#define GTS_DICE_CE_STATS_CE_DEN 4
+#define GTS_DICE_CE_STATS_DICE 8
+#define GTS_DICE_CE_STATS_I 16
+#define GTS_DICE_CE_STATS_S 24
+#define GTS_DICE_CE_STATS_T 32
+int64_t gts_dice_ce_workspace(int64_t n, int32_t n_groups);
+int32_t gts_dice_ce_fwd_f32(const float* logits, const int64_t* labels, const float* class_w,
+                            const uint32_t* group_masks, int32_t n_groups, double ce_weight,
+                            double dice_weight, double smooth, float* stats, void* workspace,
+                            int64_t workspace_bytes, int64_t n, int64_t n_classes, void* stream);
+int32_t gts_dice_ce_bwd_f32(const float* logits, const int64_t* labels, const float* class_w,
+                            const uint32_t* group_masks, int32_t n_groups, double ce_weight,
+                            double dice_weight, double smooth, const float* stats,
+                            const float* grad_scale, float* grad, int64_t n, int64_t n_classes,
+                            void* stream);
+
 /* ---- tuning knobs -----------------------------------------------------------------------
  * Process-wide tile selection of the K11 kernels (defaults are the tuned values; used by
  * tools/tune_gemm.py).  Returns GTS_ERR_ARGKIND for an unknown option. */
