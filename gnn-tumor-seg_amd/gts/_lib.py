@@ -11,11 +11,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GTS_LIB_PATH: another build of the same library (A/B runs of two builds in one session, tools/); the default is the in-tree build
 LIB_PATH = os.environ.get("GTS_LIB_PATH") or os.path.join(_HERE, "libgts_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "gts_hip.h")
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
 _i64 = ctypes.c_int64
+_u64 = ctypes.c_uint64
 _f32 = ctypes.c_float
 _f64 = ctypes.c_double
 
@@ -86,6 +87,8 @@ SIGNATURES = {
     "gts_dice_ce_workspace": [_i64, _i32],
     "gts_dice_ce_fwd_f32": [_p, _p, _p, _p, _i32, _f64, _f64, _f64, _p, _p, _i64, _i64, _i64, _p],
     "gts_dice_ce_bwd_f32": [_p, _p, _p, _p, _i32, _f64, _f64, _f64, _p, _p, _p, _i64, _i64, _p],
+    "gts_augment_crop_f32": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i32, _u64, _u64, _p],
+    "gts_augment_features_f32": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f64, _u64, _u64, _p],
     "gts_collate_plan": [_p, _i32, _i64, _p, _i32, _p],
     "gts_collate_batch": [_p, _i32, _i64, _p, _i32, _p, _i64, _i32, _p],
     "gts_gg_gaussian_f64": [_p, _p, _p, _p, _i32, _f64, _i64, _i64, _i64, _i64, _p],

@@ -866,6 +866,105 @@ def dice_ce_loss(logits, labels, class_w=None, *, regions="brats", ce_weight=1.0
     return loss, torch.cat([stats[_DICE_CE:_DICE_LDICE + 1], stats[_DICE_DICE:_DICE_DICE + len(masks)]])
 
 
+# ---------------------------------------------------------------- training-time augmentation
+def _crop_augment(x, labels, dims, image_channels, params, flip_mask, seed, step, what):
+    """One A1 launch on x [cx, cy, cz, C] and / or labels [V]; returns fresh tensors (None where the input is)."""
+    cx, cy, cz = (int(d) for d in dims)
+    _f32(x, params)
+    require_device(x, labels, params)
+    channels = 0
+    if x is not None:
+        if x.dim() != 4 or tuple(x.shape[:3]) != (cx, cy, cz):
+            raise _lib.GtsError(f"{what}: expected x [{cx}, {cy}, {cz}, C], got {tuple(x.shape)}")
+        channels = x.shape[3]
+    if labels is not None and (labels.dtype != torch.int64 or labels.numel() != cx * cy * cz):
+        raise _lib.GtsError(f"{what}: labels must be int64 with {cx * cy * cz} entries")
+    x_out = torch.empty_like(x) if x is not None else None
+    labels_out = torch.empty_like(labels) if labels is not None else None
+    if x is None and labels is None:
+        raise _lib.GtsError(f"{what}: nothing to do without x and without labels")
+    if cx * cy * cz:
+        check(_lib.load().gts_augment_crop_f32(ptr(x), ptr(labels), ptr(params), ptr(x_out), ptr(labels_out), cx, cy,
+                                               cz, channels, image_channels, flip_mask, seed, step, current_stream()),
+              "gts_augment_crop_f32")
+    return x_out, labels_out
+
+
+def augment_crop(x, labels, plan):
+    """A1.  (x', labels') of a cropped sample under a gts.augment.AugmentPlan: x [cx, cy, cz, C] fp32 channels-last
+    whose first plan.channels channels are the image modalities (mirrored, x * scale + shift + sigma * noise; the
+    other channels are mirrored only), labels int64 [cx * cy * cz] or [cx, cy, cz] (mirrored).  Either may be None
+    (labels alone must then be 3-D: they carry the extents).  Fresh tensors; not an autograd node."""
+    if x is not None:
+        dims = tuple(x.shape[:3])
+    elif labels is not None and labels.dim() == 3:
+        dims = tuple(labels.shape)
+    else:
+        raise _lib.GtsError("augment_crop: without x the labels must be [cx, cy, cz]")
+    params = None
+    ci = 0
+    if x is not None:
+        import numpy as np
+
+        ci = plan.channels
+        params = torch.from_numpy(np.stack([plan.scale, plan.shift, plan.sigma], axis=1)).to(x.device)
+        x = x.contiguous()
+    if labels is not None:
+        labels = labels.contiguous()
+    return _crop_augment(x, labels, dims, ci, params, plan.flip_mask, plan.seed64, plan.step, "augment_crop")
+
+
+def flip_crop(t, dims, flips):
+    """A1 without image channels: t [V, K] or [cx, cy, cz, K] fp32 over a crop of extents dims, mirrored along the
+    axes whose entry of flips (x, y, z) is true.  An involution and its own adjoint, which is how the joint step
+    carries a gradient back through the mirror.  Returns a fresh tensor of t's shape; not an autograd node."""
+    cx, cy, cz = (int(d) for d in dims)
+    if t.dim() == 2 and t.shape[0] == cx * cy * cz:
+        view = t.contiguous().view(cx, cy, cz, t.shape[1])
+    elif t.dim() == 4 and tuple(t.shape[:3]) == (cx, cy, cz):
+        view = t.contiguous()
+    else:
+        raise _lib.GtsError(f"flip_crop: expected [{cx * cy * cz}, K] or [{cx}, {cy}, {cz}, K], got {tuple(t.shape)}")
+    flips = tuple(bool(f) for f in flips)
+    if len(flips) != 3:
+        raise _lib.GtsError("flip_crop: flips are three booleans (x, y, z)")
+    mask = sum(1 << a for a in range(3) if flips[a])
+    return _crop_augment(view, None, (cx, cy, cz), 0, None, mask, 0, 0, "flip_crop")[0].view(t.shape)
+
+
+def augment_features(feats, batch_num_nodes, plans):
+    """A2.  Node features [N, F] fp32 of a batch of graphs under one gts.augment.AugmentPlan per graph: feature f of a
+    row of graph g becomes f * scale[g][m] + shift[g][m] with m = f // (F // M), M the plans' channel count (the five
+    quantile columns of a modality move with the modality) plus feature_sigma * noise.  batch_num_nodes: the
+    graphs' row counts (graph.batch_num_nodes()).  The noise of the call is keyed by the first plan's seed and step
+    and indexed by the row inside the batch.  Returns a NEW tensor: the dataset cache and resident batches keep the
+    originals.  Not an autograd node."""
+    import numpy as np
+
+    sizes = np.asarray(batch_num_nodes.cpu() if isinstance(batch_num_nodes, torch.Tensor) else batch_num_nodes,
+                       dtype=np.int64).reshape(-1)
+    plans = list(plans)
+    if feats.dim() != 2 or len(plans) != len(sizes) or not plans:
+        raise _lib.GtsError("augment_features takes features [N, F] and one plan per graph")
+    _f32(feats)
+    feats = feats.contiguous()
+    require_device(feats)
+    modalities = plans[0].channels
+    if any(p.channels != modalities or p.feature_sigma != plans[0].feature_sigma for p in plans):
+        raise _lib.GtsError("augment_features: the plans of one batch share the channel count and the feature sigma")
+    row_ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    params = np.stack([np.stack([p.scale, p.shift], axis=1) for p in plans]).astype(np.float32)
+    out = torch.empty_like(feats)
+    n, f = feats.shape
+    row_ptr_dev = torch.from_numpy(row_ptr).to(feats.device)
+    params_dev = torch.from_numpy(params).to(feats.device)
+    check(_lib.load().gts_augment_features_f32(ptr(feats), ptr(row_ptr_dev), row_ptr.ctypes.data, ptr(params_dev),
+                                               ptr(out), n, f, modalities, len(sizes), plans[0].feature_sigma,
+                                               plans[0].seed64, plans[0].step, current_stream()),
+          "gts_augment_features_f32")
+    return out
+
+
 def weighted_ce_numerator_grad(logits, labels, class_w=None):
     """(d numerator / d logits [N, C], [num, den, num/den]) from one launch, outside autograd: what the
     data-parallel step back-propagates with `logits.backward(grad)` — no clone / fill / scale kernels around

@@ -40,9 +40,12 @@ class RefinementModel:
     HD95 is computed, as in the reference, on the [1, cx, cy, cz] arrays of the crop.
     `voxel_loss`: a callable (logits, labels) -> loss from model.losses.make_voxel_loss (soft Dice + cross-entropy);
     None is the reference's class-weighted cross-entropy.  Column 0 of `evaluate` is the configured loss.
+    `augmenter`: a gts.augment.Augmenter; `run_epoch` then draws one plan per sample and mirrors / jitters the
+    uploaded crop on the GPU (gts.ops.augment_crop).  `evaluate` is never augmented.  None: no augmentation.
     """
 
-    def __init__(self, hyperparameters, train_dataset, logit_dataset, prefetch=True, voxel_loss=None):
+    def __init__(self, hyperparameters, train_dataset, logit_dataset, prefetch=True, voxel_loss=None,
+                 augmenter=None):
         if not torch.cuda.is_available():
             raise RuntimeError("RefinementModel trains on an AMD GPU only (no CPU path)")
         self.device = torch.device("cuda", torch.cuda.current_device())
@@ -58,6 +61,7 @@ class RefinementModel:
                                        collate_fn=collate_refinement_net) if train_dataset is not None else None
         self.logit_dataset = logit_dataset
         self.prefetch = prefetch
+        self.augmenter = augmenter
 
     def _cropped(self, mri, img, lab):
         """(input float32 [cx, cy, cz, C], labels int64 [V]) of one sample, or None when its logits are missing."""
@@ -131,6 +135,8 @@ class RefinementModel:
             if sample is None:
                 continue
             x, y = (t.to(self.device, non_blocking=False) for t in sample)
+            if self.augmenter is not None:
+                x, y = ops.augment_crop(x, y, self.augmenter.draw())
             losses.append(self.train_step(x, y))
         self.lr_decay.step()
         if not losses:

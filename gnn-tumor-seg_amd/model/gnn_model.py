@@ -84,14 +84,19 @@ class GNN:
     BATCH_SIZE = 6, model/gnn_model.py:12).  Under torch.distributed with W ranks a step therefore
     trains on a global batch of `batch_size * W` graphs (weak scaling, `global_batch_size`) with the
     learning rate unchanged; pass `keep_global_batch=True` to split the reference's batch over the
-    ranks instead (per-rank batch ceil(batch_size / W), same optimisation problem as one GPU)."""
+    ranks instead (per-rank batch ceil(batch_size / W), same optimisation problem as one GPU).
+    `augmenter`: a gts.augment.Augmenter; `run_epoch` then draws one plan per member graph of every batch and maps
+    the node features of each modality by that plan's scale / shift (gts.ops.augment_features, a new tensor on the
+    main stream); under data parallelism the caller seeds each rank's augmenter with seed + rank.  None: the loop
+    as it was."""
 
     def __init__(self, model_type, hyperparameters, train_dataset, batch_size=BATCH_SIZE, prefetch=True,
-                 keep_global_batch=False, host_collate=True):
+                 keep_global_batch=False, host_collate=True, augmenter=None):
         if not torch.cuda.is_available():
             raise RuntimeError("GNN needs an AMD GPU (MI355X): the HIP kernels have no CPU fallback")
         self.rank, self.world_size = gdist.world()
         self.prefetch = prefetch
+        self.augmenter = augmenter
         # True: the loader's batches are assembled by gts_collate_batch (one host C call, one upload: gts/collate.py);
         # False: by minibatch_graphs + per-array uploads, the Python path whose bytes the C path is tested against
         self.host_collate = host_collate and os.environ.get("GTS_HOST_COLLATE", "1") != "0"
@@ -319,12 +324,21 @@ class GNN:
                 except queue.Empty:
                     worker.join(timeout=0.05)
 
+    def _augmented(self, graph, feats, labels):
+        """The batch with its node features mapped by one freshly drawn plan per member graph."""
+        plans = [self.augmenter.draw() for _ in range(graph.batch_size)]
+        return graph, gops.augment_features(feats, graph.batch_num_nodes(), plans), labels
+
     def run_epoch(self):
         """One pass over the training loader; returns the mean of the per-step losses
         (reference :34-48).  Losses stay on the device until the epoch ends."""
         self.net.train()
-        step_losses = [self.empty_step() if batch is None else self.train_step(*batch)
-                       for batch in self._device_batches()]
+        if self.augmenter is None:
+            step_losses = [self.empty_step() if batch is None else self.train_step(*batch)
+                           for batch in self._device_batches()]
+        else:
+            step_losses = [self.empty_step() if batch is None else self.train_step(*self._augmented(*batch))
+                           for batch in self._device_batches()]
         self.lr_decay.step()
         return np.mean(torch.stack(step_losses).cpu().double().numpy())
 

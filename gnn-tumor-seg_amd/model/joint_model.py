@@ -46,10 +46,14 @@ class JointModel:
     fine-tuning a trained pair: an untrained GNN predicts tumour everywhere, so the crop is the whole
     brain).  `voxel_loss`: a callable (logits, labels) -> loss from model.losses.make_voxel_loss (soft Dice +
     cross-entropy) that replaces the voxel cross-entropy, in training and in column 0 of `evaluate`; None keeps the
-    cross-entropy.  The node loss stays cross-entropy.  Single GPU only."""
+    cross-entropy.  The node loss stays cross-entropy.  `augmenter`: a gts.augment.Augmenter; `run_epoch` then draws
+    one plan per step, whose scale / shift go onto the node features before the graph network (so the crop comes from
+    the augmented features) and onto the image channels of the CNN's input, and whose mirror goes onto that input, the
+    labels and, backwards, the gradient (gts.ops.augment_features, gts.joint).  `evaluate` is never augmented.
+    Single GPU only."""
 
     def __init__(self, gnn_type, gnn_hp, cnn_hp, dataset, gnn_loss_weight=1.0, gnn_weights=None, cnn_weights=None,
-                 voxel_loss=None):
+                 voxel_loss=None, augmenter=None):
         if not torch.cuda.is_available():
             raise RuntimeError("JointModel needs an AMD GPU (MI355X): the HIP kernels have no CPU fallback")
         if gdist.world()[1] > 1:
@@ -76,6 +80,7 @@ class JointModel:
         self.train_loader = DataLoader(dataset, batch_size=1, shuffle=True, num_workers=0, collate_fn=_first) \
             if dataset is not None else None
         self._resident = {}
+        self.augmenter = augmenter
         self.last_box = None              # the CropBox of the last training step
         self.last_node_logits = None      # ... and the node logits it was taken from (detached)
 
@@ -116,17 +121,23 @@ class JointModel:
         xs, ys, zs = (d.long() for d in box.dev)
         return voxel_labels[xs[:, None, None], ys[None, :, None], zs[None, None, :]].reshape(-1)
 
-    def _voxel_logits(self, graph, feats, img, svs, lists):
+    def _voxel_logits(self, graph, feats, img, svs, lists, plan=None):
         node_logits = self.graph_net(graph, feats).float()
         box = self.crop_box(node_logits, svs)
-        return node_logits, box, joint_refinement_logits(node_logits, img, svs, box, self.bg_row, self.conv_net, lists)
+        return node_logits, box, joint_refinement_logits(node_logits, img, svs, box, self.bg_row, self.conv_net,
+                                                         lists, augment=plan)
 
-    def train_step(self, graph, feats, node_labels, img, svs, voxel_labels, lists=None):
+    def train_step(self, graph, feats, node_labels, img, svs, voxel_labels, lists=None, plan=None):
         """One forward / backward / two AdamW updates on one sample already on the device; returns the total loss
-        as a device scalar."""
-        node_logits, box, voxel_logits = self._voxel_logits(graph, feats, img, svs, lists)
+        as a device scalar.  `plan`: the gts.augment.AugmentPlan of this step (None: the sample as it is)."""
+        if plan is not None:
+            feats = ops.augment_features(feats, [feats.shape[0]], [plan])
+        node_logits, box, voxel_logits = self._voxel_logits(graph, feats, img, svs, lists, plan)
         self.last_box, self.last_node_logits = box, node_logits.detach()
-        loss = self.voxel_loss(voxel_logits, self.cropped_labels(voxel_labels, box))
+        labels = self.cropped_labels(voxel_labels, box)
+        if plan is not None and any(plan.flips):
+            labels = ops.augment_crop(None, labels.view(box.shape), plan)[1].reshape(-1)
+        loss = self.voxel_loss(voxel_logits, labels)
         if self.gnn_loss_weight:
             loss = loss + self.gnn_loss_weight * ops.weighted_cross_entropy(node_logits, node_labels,
                                                                             self.gnn_class_weights)
@@ -146,7 +157,11 @@ class JointModel:
         self.graph_net.train()
         self.conv_net.train()
         source = self._source(self.train_loader.dataset)
-        losses = [self.train_step(*self._to_device(source, sample)) for sample in self.train_loader]
+        if self.augmenter is None:
+            losses = [self.train_step(*self._to_device(source, sample)) for sample in self.train_loader]
+        else:
+            losses = [self.train_step(*self._to_device(source, sample), plan=self.augmenter.draw())
+                      for sample in self.train_loader]
         self.gnn_lr_decay.step()
         self.cnn_lr_decay.step()
         if not losses:

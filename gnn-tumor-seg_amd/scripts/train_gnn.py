@@ -2,11 +2,14 @@
 
 Command line, outputs and file names match /root/reference/scripts/train_gnn.py:64-89:
   python -m scripts.train_gnn -d DATA -o LOGDIR -r RUN [-m GSpool|GSmean|GSgcn|GAT] [-k FOLDS]
-                              [-p PREFIX] [-x]
+                              [-p PREFIX] [-x] [--augment] [--aug_scale S] [--aug_shift S] [--aug_seed N]
 Launch under `torchrun --nproc-per-node N` for data-parallel training (one rank per GPU).  By default every
 rank then takes the reference's batch of 6 graphs per step (global batch 6 N at the reference's learning rate:
 weak scaling); `--keep_global_batch` splits the reference's 6 over the ranks instead (ceil(6 / N) each), which is
 the optimisation problem of the single-GPU run.  Evaluation is sharded over the ranks either way.
+`--augment` scales and shifts the node features of every training graph per modality (gts/augment.py: exactly the
+features of the image so mapped); the flip and noise flags the other trainers share are accepted and ignored here.
+Rank r seeds its augmenter with --aug_seed + r.
 """
 import argparse
 import os
@@ -17,6 +20,7 @@ from torch.utils.data import Subset
 import Filepaths
 from data_processing.data_loader import ImageGraphDataset
 from gts import dist as gdist
+from gts.augment import add_augment_arguments, augmenter_from_args
 from model.gnn_model import GNN
 from utils.hyperparam_helpers import generate_random_hyperparameters, populate_hardcoded_hyperparameters
 from utils.training_helpers import (chunk_dataset_into_folds, create_run_progress_file, train_on_fold,
@@ -40,9 +44,14 @@ def document_metrics(fp, description, results):
         update_progress_file(fp, description, metrics[0], metrics[4:7])
 
 
+def _augmenter(args):
+    return augmenter_from_args(args, rank=gdist.world()[0], features_only=True)
+
+
 def train_on_full_dataset(args, hyperparams, progress_file_fd, dataset):
     print("Training on full dataset")
-    model = GNN(args.model_type, hyperparams, dataset, keep_global_batch=args.keep_global_batch)
+    model = GNN(args.model_type, hyperparams, dataset, keep_global_batch=args.keep_global_batch,
+                augmenter=_augmenter(args))
     train_on_fold(model, args.output_dir + os.sep, hyperparams.n_epochs, args.run_name, 1)
     whole = Subset(dataset, range(len(dataset)))
     document_metrics(progress_file_fd, f"{args.run_name}_full", model.evaluate(whole))
@@ -56,7 +65,8 @@ def run_k_fold_val(args, hyperparams, progress_file_fd, dataset, k):
         held_out = Subset(dataset, range(start, end))
         training = Subset(dataset, list(r_[0:start, end:everything]))
         print(f"Fold contains {len(training)} examples")
-        model = GNN(args.model_type, hyperparams, training, keep_global_batch=args.keep_global_batch)
+        model = GNN(args.model_type, hyperparams, training, keep_global_batch=args.keep_global_batch,
+                    augmenter=_augmenter(args))
         train_on_fold(model, args.output_dir + os.sep, hyperparams.n_epochs, args.run_name, fold)
         for split, subset in (("train", training), ("val", held_out)):
             document_metrics(progress_file_fd, f"{args.run_name}_f{fold}_{split}", model.evaluate(subset))
@@ -86,11 +96,20 @@ def build_parser():
     return parser
 
 
+def build_cli_parser():
+    """The command line `main` takes: the flags above plus the augmentation (the flip and noise flags are ignored)."""
+    parser = build_parser()
+    add_augment_arguments(parser, flips=False)
+    return parser
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_cli_parser().parse_args(argv)
     if args.num_folds < 1:
         raise ValueError("Number of folds must be a positive integer")
     rank = gdist.init_from_env()[0]
+    if args.augment and rank == 0:
+        print(_augmenter(args).describe())
     args.output_dir = os.path.expanduser(args.output_dir)
     dataset = ImageGraphDataset(os.path.expanduser(args.data_dir), args.data_prefix, read_image=False,
                                 read_graph=True, read_label=True)

@@ -2,7 +2,9 @@
 
   python -m scripts.train_joint -d DATA -o OUT -r RUN [-k FOLDS] [-p PREFIX] [-m GSpool] [-g GNN.pt] [-c CNN.pt]
                                 [-w GNN_LOSS_WEIGHT] [-x] [--loss {ce,dice_ce}] [--dice_weight W]
-                                [--dice_smooth S] [--dice_regions {brats,classes}]
+                                [--dice_smooth S] [--dice_regions {brats,classes}] [--augment] [--aug_flip_axes xyz]
+                                [--aug_flip_prob P] [--aug_scale S] [--aug_shift S] [--aug_noise SIGMA]
+                                [--aug_noise_prob P] [--aug_seed N]
 
 The reference has no such script (its scripts/train_refinement_cnn.py:21-22 names joint training and declines
 to build it); flags, console report, progress file and folds follow scripts/train_refinement_cnn.py.  DATA is
@@ -12,6 +14,8 @@ predicts tumour everywhere and the crop becomes the whole brain (correct, only s
 comes from the GNN hyper-parameter set.  Checkpoints: `{run}_f{k}_gnn.pt` and `{run}_f{k}_cnn.pt`, which
 generate_joint_predictions and segment_scans load as they load separately trained ones.  `--loss dice_ce` replaces
 the voxel cross-entropy by cross-entropy + soft Dice (model/losses.py); the node loss stays cross-entropy.
+`--augment` draws one plan per step (gts/augment.py): its scale / shift per modality go onto the node features and
+the image alike, its mirror onto the CNN's input, the labels and the gradient; evaluation is never augmented.
 """
 import argparse
 import os
@@ -19,6 +23,7 @@ import os
 from torch.utils.data import Subset
 
 from data_processing.data_loader import ImageGraphDataset
+from gts.augment import add_augment_arguments, augmenter_from_args
 from model.joint_model import JointModel
 from scripts.train_refinement_cnn import (add_voxel_loss_arguments, document_metrics, fold_splits,
                                           voxel_loss_from_args)
@@ -31,7 +36,8 @@ def _model(args, hyperparams, dataset):
     return JointModel(args.gnn_type, gnn_hp, cnn_hp, dataset, gnn_loss_weight=args.gnn_loss_weight,
                       gnn_weights=os.path.expanduser(args.gnn_weights) if args.gnn_weights else None,
                       cnn_weights=os.path.expanduser(args.cnn_weights) if args.cnn_weights else None,
-                      voxel_loss=voxel_loss_from_args(args, cnn_hp.class_weights))
+                      voxel_loss=voxel_loss_from_args(args, cnn_hp.class_weights),
+                      augmenter=augmenter_from_args(args))
 
 
 def train_on_full_dataset(args, hyperparams, progress_file_fd, dataset):
@@ -77,9 +83,10 @@ def build_parser():
 
 
 def build_cli_parser():
-    """The command line `main` takes: the flags above plus the choice of the voxel objective."""
+    """The command line `main` takes: the flags above plus the choice of the voxel objective and the augmentation."""
     parser = build_parser()
     add_voxel_loss_arguments(parser)
+    add_augment_arguments(parser)
     return parser
 
 
@@ -91,6 +98,8 @@ def main(argv=None):
         raise ValueError("The weight of the node-level loss must not be negative")
     if args.dice_weight < 0 or not args.dice_smooth > 0:
         raise ValueError("--dice_weight must not be negative and --dice_smooth must be positive")
+    if args.augment:
+        print(augmenter_from_args(args).describe())
     dataset = ImageGraphDataset(os.path.expanduser(args.data_dir), args.data_prefix, read_image=True,
                                 read_graph=True, read_label=True)
     draw = generate_random_hyperparameters if args.random_hyperparams else populate_hardcoded_hyperparameters

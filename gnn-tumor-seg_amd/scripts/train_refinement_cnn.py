@@ -4,7 +4,9 @@ Command line, console report, progress file and checkpoint names (`{run}_f{k}.pt
 /root/reference/scripts/train_refinement_cnn.py:
   python -m scripts.train_refinement_cnn -d DATA -l LOGITS -o OUT -r RUN [-k FOLDS] [-p PREFIX] [-x]
                                          [--loss {ce,dice_ce}] [--dice_weight W] [--dice_smooth S]
-                                         [--dice_regions {brats,classes}]
+                                         [--dice_regions {brats,classes}] [--augment] [--aug_flip_axes xyz]
+                                         [--aug_flip_prob P] [--aug_scale S] [--aug_shift S] [--aug_noise SIGMA]
+                                         [--aug_noise_prob P] [--aug_seed N]
 The logits are the `{id}_logits.nii.gz` files `generate_gnn_predictions -f logits` writes.
 
 One deliberate difference: with k > 1 the reference builds every fold's model on the WHOLE dataset, so its
@@ -14,6 +16,10 @@ range, as scripts/train_gnn.py does.
 One addition: `--loss dice_ce` trains on the class-weighted cross-entropy plus `--dice_weight` times the soft Dice
 loss over `--dice_regions` (model/losses.py); the default `ce` is the reference's objective.  The progress file's
 loss column is the configured loss.
+
+Another: `--augment` mirrors every training crop along random axes, scales and shifts each image modality and adds
+Gaussian noise to some, on the GPU (gts/augment.py); evaluation is never augmented.  The augmentation has
+its own generator (`--aug_seed`), so the order of the samples does not change with it.
 """
 import argparse
 import os
@@ -22,6 +28,7 @@ from numpy import around, r_
 from torch.utils.data import Subset
 
 from data_processing.data_loader import ImageGraphDataset, PredLogitDataset
+from gts.augment import add_augment_arguments, augmenter_from_args
 from model.cnn_model import RefinementModel
 from model.losses import VOXEL_LOSS_KINDS, make_voxel_loss
 from utils.hyperparam_helpers import generate_random_hyperparameters, populate_hardcoded_hyperparameters
@@ -72,7 +79,8 @@ def voxel_loss_from_args(args, class_weights):
 def train_on_full_dataset(args, hyperparams, progress_file_fd, image_dataset, logit_dataset):
     print("Training on full dataset")
     model = RefinementModel(hyperparams, image_dataset, logit_dataset,
-                            voxel_loss=voxel_loss_from_args(args, hyperparams.class_weights))
+                            voxel_loss=voxel_loss_from_args(args, hyperparams.class_weights),
+                            augmenter=augmenter_from_args(args))
     train_on_fold(model, args.output_dir + os.sep, hyperparams.n_epochs, args.run_name, 1)
     metrics = model.evaluate(Subset(image_dataset, range(len(image_dataset))))
     document_metrics(progress_file_fd, f"{args.run_name}_full", metrics)
@@ -84,7 +92,8 @@ def run_k_fold_val(args, hyperparams, progress_file_fd, image_dataset, logit_dat
         training, held_out = Subset(image_dataset, train_idx), Subset(image_dataset, val_idx)
         print(f"Fold contains {len(training)} examples")
         model = RefinementModel(hyperparams, training, logit_dataset,
-                                voxel_loss=voxel_loss_from_args(args, hyperparams.class_weights))
+                                voxel_loss=voxel_loss_from_args(args, hyperparams.class_weights),
+                                augmenter=augmenter_from_args(args))
         train_on_fold(model, args.output_dir + os.sep, hyperparams.n_epochs, args.run_name, fold)
         document_metrics(progress_file_fd, f"{args.run_name}_f{fold}_train", model.evaluate(training))
         document_metrics(progress_file_fd, f"{args.run_name}_f{fold}_val", model.evaluate(held_out))
@@ -110,9 +119,11 @@ def build_parser():
 
 
 def build_cli_parser():
-    """The command line `main` takes: the reference's flags plus the choice of the voxel objective."""
+    """The command line `main` takes: the reference's flags plus the choice of the voxel objective and the
+    augmentation."""
     parser = build_parser()
     add_voxel_loss_arguments(parser)
+    add_augment_arguments(parser)
     return parser
 
 
@@ -122,6 +133,8 @@ def main(argv=None):
         raise ValueError("Number of folds must be a positive integer")
     if args.dice_weight < 0 or not args.dice_smooth > 0:
         raise ValueError("--dice_weight must not be negative and --dice_smooth must be positive")
+    if args.augment:
+        print(augmenter_from_args(args).describe())
     image_dataset = ImageGraphDataset(os.path.expanduser(args.data_dir), args.data_prefix, read_image=True,
                                       read_graph=False, read_label=True)
     logit_dataset = PredLogitDataset(os.path.expanduser(args.saved_logit_dir))

@@ -516,7 +516,50 @@ int32_t gts_dice_ce_bwd_f32(const float* logits, const int64_t* labels, const fl
                             const float* grad_scale, float* grad, int64_t n, int64_t n_classes,
                             void* stream);
 
-/* ---- tuning knobs -----------------------------------------------------------------------
+/* ---- training-time augmentation -------------------------------------------------
+ * No counterpart in the reference, whose loops show every sample the same way in every epoch.  Both
+ * kernels write fresh outputs (never in place) with plain 16-byte stores; no atomics, no workspace.
+ *
+ * gts_augment_crop_f32 (A1): x [cx, cy, cz, channels] fp32 channels-last and labels int64 [cx*cy*cz],
+ * either of which may be NULL (with its output).  flip_mask bit 0 / 1 / 2 mirrors axis x / y / z:
+ *   x_out[i, j, k, c] = x[i', j', k', c] * a_c + b_c + s_c * n(v, c)   for c < image_channels
+ *                     = x[i', j', k', c]                               for c >= image_channels
+ *   labels_out[v]     = labels[v']
+ * with i' = cx - 1 - i on a mirrored axis and v the C-order index of the OUTPUT voxel.  params: DEVICE
+ * [image_channels][3] = (a_c, b_c, s_c), may be NULL when image_channels == 0 (the plain mirror, which is
+ * its own inverse and its own adjoint).  The affine is a float32 multiply, then a float32 add (no fma).  A
+ * channel with a == 1 and b == 0 is copied, a channel with s == 0 draws nothing: the identity returns its
+ * input bit for bit.  channels % 4 == 0 with 16-byte aligned bases moves 16 bytes per access, anything
+ * else float by float (same values).
+ *
+ * gts_augment_features_f32 (A2): feats [n_rows, n_feats] fp32 node features of a batch of n_graphs graphs;
+ * row_ptr (DEVICE) and row_ptr_host (HOST, read during the call) both hold the n_graphs + 1 row offsets,
+ * ascending from 0 to n_rows (graphs without rows are legal); params: DEVICE [n_graphs][modalities][2] =
+ * (a, b), n_feats % modalities == 0, feature f belongs to modality f / (n_feats / modalities) (the
+ * quantile columns of mri2graph/graphgen.py:23-25, 45-52):
+ *   out[r, f] = feats[r, f] * a_{g(r), m(f)} + b_{g(r), m(f)} + sigma * n(r, f)
+ * Same copy / no-draw rule as A1.  n_rows == 0 returns GTS_OK without touching the device.
+ *
+ * n(idx, c): Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ * (idx & 0xffffffff, idx >> 32 | (c / 4) << 24 | stream << 31, step & 0xffffffff, step >> 32), stream 0
+ * with idx = v for A1 and stream 1 with idx = r for A2.  From the four output words, channel c takes normal
+ * c % 4: normals 0, 1 from words (0, 1), normals 2, 3 from words (2, 3), by Box-Muller in float32 with the
+ * accurate logf / sinf / cosf: u = ((w_even >> 8) + 1) 2^-24, t = 2 pi (w_odd >> 8) 2^-24,
+ * r = sqrt(-2 ln u), normals r cos t and r sin t.  Independent of the launch geometry.
+ * Errors, before any launch: a missing pointer -> GTS_ERR_NULL; a negative extent, channels or n_feats
+ * outside [1, 512], image_channels > channels, n_feats % modalities != 0, 2^56 or more voxels / rows,
+ * row_ptr_host not ascending from 0 to n_rows -> GTS_ERR_SHAPE; flip_mask outside 0..7, a negative or
+ * non-finite sigma -> GTS_ERR_ARGKIND. */
+int32_t gts_augment_crop_f32(const float* x, const int64_t* labels, const float* params, float* x_out,
+                             int64_t* labels_out, int64_t cx, int64_t cy, int64_t cz, int64_t channels,
+                             int64_t image_channels, int32_t flip_mask, uint64_t seed, uint64_t step,
+                             void* stream);
+int32_t gts_augment_features_f32(const float* feats, const int64_t* row_ptr, const int64_t* row_ptr_host,
+                                 const float* params, float* out, int64_t n_rows, int64_t n_feats,
+                                 int64_t modalities, int64_t n_graphs, double sigma, uint64_t seed,
+                                 uint64_t step, void* stream);
+
+/* ---- tuning knobs-----------------------------------------------------------------------
  * Process-wide tile selection of the K11 kernels (defaults are the tuned values; used by
  * tools/tune_gemm.py).  Returns GTS_ERR_ARGKIND for an unknown option. */
 #define GTS_OPT_GEMM_TILE 1  /* forward tile: -1 automatic, -2 automatic among the 32x32x2 tiles only (a row's result then does
