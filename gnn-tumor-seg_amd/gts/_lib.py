@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GTS_LIB_PATH: another build of the same library (A/B runs of two builds in one session, tools/); the default is the in-tree build
 LIB_PATH = os.environ.get("GTS_LIB_PATH") or os.path.join(_HERE, "libgts_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "gts_hip.h")
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -89,6 +89,8 @@ SIGNATURES = {
     "gts_dice_ce_bwd_f32": [_p, _p, _p, _p, _i32, _f64, _f64, _f64, _p, _p, _p, _i64, _i64, _p],
     "gts_augment_crop_f32": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i32, _u64, _u64, _p],
     "gts_augment_features_f32": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f64, _u64, _u64, _p],
+    "gts_augment_spatial_f32": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i32, _u64, _u64, _p],
+    "gts_augment_spatial_bwd_f32": [_p, _p, _p, _i64, _i64, _i64, _i64, _i32, _p],
     "gts_collate_plan": [_p, _i32, _i64, _p, _i32, _p],
     "gts_collate_batch": [_p, _i32, _i64, _p, _i32, _p, _i64, _i32, _p],
     "gts_gg_gaussian_f64": [_p, _p, _p, _p, _i32, _f64, _i64, _i64, _i64, _i64, _p],

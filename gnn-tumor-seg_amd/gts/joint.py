@@ -9,7 +9,8 @@ The image, the box and the background row take no gradient.
 
 With `augment` (a gts.augment.AugmentPlan) the assembled input is mirrored and its image channels jittered (A1,
 gts.ops.augment_crop) before conv1; backward mirrors conv1's data gradient back (a mirror is its own adjoint)
-before J2.  J1 and J2 are the same calls either way.
+before J2; under a spatial plan (a rotation and zoom, A3) it is the adjoint of the resample and the
+mirror (A4, gts.ops.spatial_crop_bwd).  J1 and J2 are the same calls either way.
 """
 import torch
 
@@ -30,6 +31,7 @@ class _JointRefinement(torch.autograd.Function):
         ctx.save_for_backward(x, h1, w1, w2)
         ctx.box, ctx.lists, ctx.ct = box, lists, table.shape[1]
         ctx.flips = augment.flips if augment is not None and any(augment.flips) else None
+        ctx.spatial = augment if augment is not None and augment.spatial else None
         return y
 
     @staticmethod
@@ -45,7 +47,9 @@ class _JointRefinement(torch.autograd.Function):
             # C3 for conv1 on the logit channels only: the image channels' gradient is never formed
             ci = x.shape[3] - ctx.ct
             dx_logits = conv3d_bwd_data(dz1, w1[:, ci:].contiguous(), dims)
-            if ctx.flips is not None:       # the logit channels were mirrored only: the adjoint is the same mirror
+            if ctx.spatial is not None:     # the logit channels were mirrored and resampled: the adjoint of both
+                dx_logits = ops.spatial_crop_bwd(dx_logits, dims, ctx.spatial)
+            elif ctx.flips is not None:     # the logit channels were mirrored only: the adjoint is the same mirror
                 dx_logits = ops.flip_crop(dx_logits, dims, ctx.flips)
             d_nodes = ops.crop_concat_rows_bwd(dx_logits, ctx.lists, ctx.box, 0)
         return d_nodes, dw1, db1, dw2, db2, None, None, None, None, None, None

@@ -866,9 +866,15 @@ def dice_ce_loss(logits, labels, class_w=None, *, regions="brats", ce_weight=1.0
     return loss, torch.cat([stats[_DICE_CE:_DICE_LDICE + 1], stats[_DICE_DICE:_DICE_DICE + len(masks)]])
 
 
-# ---------------------------------------------------------------- training-time augmentation (DESIGN.md 4q)
-def _crop_augment(x, labels, dims, image_channels, params, flip_mask, seed, step, what):
-    """One A1 launch on x [cx, cy, cz, C] and / or labels [V]; returns fresh tensors (None where the input is)."""
+# ---------------------------------------------------------------- training-time augmentation (DESIGN.md 4q, 4r)
+def _matrix_arg(matrix):
+    """The plan's float64 [3, 3] matrix as the 9 host doubles A3 / A4 read during the call."""
+    return (ctypes.c_double * 9)(*(float(m) for m in matrix.reshape(-1)))
+
+
+def _crop_augment(x, labels, dims, image_channels, params, flip_mask, seed, step, what, matrix=None):
+    """One A1 launch (A3 with a matrix) on x [cx, cy, cz, C] and / or labels [V]; returns fresh tensors (None where
+    the input is)."""
     cx, cy, cz = (int(d) for d in dims)
     _f32(x, params)
     require_device(x, labels, params)
@@ -883,18 +889,25 @@ def _crop_augment(x, labels, dims, image_channels, params, flip_mask, seed, step
     labels_out = torch.empty_like(labels) if labels is not None else None
     if x is None and labels is None:
         raise _lib.GtsError(f"{what}: nothing to do without x and without labels")
-    if cx * cy * cz:
+    if cx * cy * cz and matrix is None:
         check(_lib.load().gts_augment_crop_f32(ptr(x), ptr(labels), ptr(params), ptr(x_out), ptr(labels_out), cx, cy,
                                                cz, channels, image_channels, flip_mask, seed, step, current_stream()),
               "gts_augment_crop_f32")
+    elif cx * cy * cz:
+        check(_lib.load().gts_augment_spatial_f32(ptr(x), ptr(labels), ptr(params), _matrix_arg(matrix), ptr(x_out),
+                                                  ptr(labels_out), cx, cy, cz, channels, image_channels, flip_mask,
+                                                  seed, step, current_stream()),
+              "gts_augment_spatial_f32")
     return x_out, labels_out
 
 
 def augment_crop(x, labels, plan):
-    """A1.  (x', labels') of a cropped sample under a gts.augment.AugmentPlan: x [cx, cy, cz, C] fp32 channels-last
-    whose first plan.channels channels are the image modalities (mirrored, x * scale + shift + sigma * noise; the
-    other channels are mirrored only), labels int64 [cx * cy * cz] or [cx, cy, cz] (mirrored).  Either may be None
-    (labels alone must then be 3-D: they carry the extents).  Fresh tensors; not an autograd node."""
+    """A1, or A3 when the plan is spatial.  (x', labels') of a cropped sample under a gts.augment.AugmentPlan: x
+    [cx, cy, cz, C] fp32 channels-last whose first plan.channels channels are the image modalities (mirrored, x *
+    scale + shift + sigma * noise; the other channels are mirrored only), labels int64 [cx * cy * cz] or
+    [cx, cy, cz] (mirrored).  A spatial plan (plan.matrix differs from the identity) also rotates and zooms about the
+    crop's centre: trilinear with a zero border for x, nearest for the labels (include/gts_hip.h).  Either may be
+    None (labels alone must then be 3-D: they carry the extents).  Fresh tensors; not an autograd node."""
     if x is not None:
         dims = tuple(x.shape[:3])
     elif labels is not None and labels.dim() == 3:
@@ -911,7 +924,8 @@ def augment_crop(x, labels, plan):
         x = x.contiguous()
     if labels is not None:
         labels = labels.contiguous()
-    return _crop_augment(x, labels, dims, ci, params, plan.flip_mask, plan.seed64, plan.step, "augment_crop")
+    matrix = plan.matrix if plan.spatial else None
+    return _crop_augment(x, labels, dims, ci, params, plan.flip_mask, plan.seed64, plan.step, "augment_crop", matrix)
 
 
 def flip_crop(t, dims, flips):
@@ -930,6 +944,28 @@ def flip_crop(t, dims, flips):
         raise _lib.GtsError("flip_crop: flips are three booleans (x, y, z)")
     mask = sum(1 << a for a in range(3) if flips[a])
     return _crop_augment(view, None, (cx, cy, cz), 0, None, mask, 0, 0, "flip_crop")[0].view(t.shape)
+
+
+def spatial_crop_bwd(t, dims, plan):
+    """A4.  The adjoint of augment_crop's mirror and resample (not of its affine or noise) on t [V, K] or
+    [cx, cy, cz, K] fp32, a gradient with respect to the augmented crop of extents dims: what the joint step carries
+    back to the node logits.  Deterministic (a gather, float64 sums in a fixed order).  For a plan that is not spatial
+    it is flip_crop.  Returns a fresh tensor of t's shape; not an autograd node."""
+    if not plan.spatial:
+        return flip_crop(t, dims, plan.flips)
+    cx, cy, cz = (int(d) for d in dims)
+    if not ((t.dim() == 2 and t.shape[0] == cx * cy * cz) or (t.dim() == 4 and tuple(t.shape[:3]) == (cx, cy, cz))):
+        raise _lib.GtsError(f"spatial_crop_bwd: expected [{cx * cy * cz}, K] or [{cx}, {cy}, {cz}, K], got "
+                            f"{tuple(t.shape)}")
+    _f32(t)
+    dy = t.contiguous()
+    require_device(dy)
+    dx = torch.empty_like(dy)
+    if dy.numel():
+        check(_lib.load().gts_augment_spatial_bwd_f32(ptr(dy), _matrix_arg(plan.matrix), ptr(dx), cx, cy, cz,
+                                                      dy.shape[-1], plan.flip_mask, current_stream()),
+              "gts_augment_spatial_bwd_f32")
+    return dx
 
 
 def augment_features(feats, batch_num_nodes, plans):

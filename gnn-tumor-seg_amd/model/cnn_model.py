@@ -40,8 +40,8 @@ class RefinementModel:
     HD95 is computed, as in the reference, on the [1, cx, cy, cz] arrays of the crop.
     `voxel_loss`: a callable (logits, labels) -> loss from model.losses.make_voxel_loss (soft Dice + cross-entropy);
     None is the reference's class-weighted cross-entropy.  Column 0 of `evaluate` is the configured loss.
-    `augmenter`: a gts.augment.Augmenter; `run_epoch` then draws one plan per sample and mirrors / jitters the
-    uploaded crop on the GPU (gts.ops.augment_crop).  `evaluate` is never augmented.  None: no augmentation.
+    `augmenter`: a gts.augment.Augmenter; `run_epoch` then draws one plan per sample and mirrors / jitters (and, where
+    the plan is spatial, rotates and zooms) the uploaded crop on the GPU (gts.ops.augment_crop).  `evaluate` is never augmented.  None: no augmentation.
     """
 
     def __init__(self, hyperparameters, train_dataset, logit_dataset, prefetch=True, voxel_loss=None,

@@ -49,7 +49,8 @@ class JointModel:
     cross-entropy.  The node loss stays cross-entropy.  `augmenter`: a gts.augment.Augmenter; `run_epoch` then draws
     one plan per step, whose scale / shift go onto the node features before the graph network (so the crop comes from
     the augmented features) and onto the image channels of the CNN's input, and whose mirror goes onto that input, the
-    labels and, backwards, the gradient (gts.ops.augment_features, gts.joint).  `evaluate` is never augmented.
+    labels and, backwards, the gradient (gts.ops.augment_features, gts.joint); a spatial plan (rotation and zoom) goes
+    the same three ways, backwards as the adjoint of the resample.  `evaluate` is never augmented.
     Single GPU only."""
 
     def __init__(self, gnn_type, gnn_hp, cnn_hp, dataset, gnn_loss_weight=1.0, gnn_weights=None, cnn_weights=None,
@@ -135,7 +136,7 @@ class JointModel:
         node_logits, box, voxel_logits = self._voxel_logits(graph, feats, img, svs, lists, plan)
         self.last_box, self.last_node_logits = box, node_logits.detach()
         labels = self.cropped_labels(voxel_labels, box)
-        if plan is not None and any(plan.flips):
+        if plan is not None and (any(plan.flips) or plan.spatial):
             labels = ops.augment_crop(None, labels.view(box.shape), plan)[1].reshape(-1)
         loss = self.voxel_loss(voxel_logits, labels)
         if self.gnn_loss_weight:

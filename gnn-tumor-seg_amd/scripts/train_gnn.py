@@ -8,7 +8,8 @@ rank then takes the reference's batch of 6 graphs per step (global batch 6 N at 
 weak scaling); `--keep_global_batch` splits the reference's 6 over the ranks instead (ceil(6 / N) each), which is
 the optimisation problem of the single-GPU run.  Evaluation is sharded over the ranks either way.
 `--augment` scales and shifts the node features of every training graph per modality (gts/augment.py: exactly the
-features of the image so mapped); the flip and noise flags the other trainers share are accepted and ignored here.
+features of the image so mapped); the flip, rotation, zoom and noise flags the other trainers share are accepted and
+ignored here (quantiles over a supervoxel do not change when the volume is turned).
 Rank r seeds its augmenter with --aug_seed + r.
 """
 import argparse

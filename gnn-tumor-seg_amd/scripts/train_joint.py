@@ -4,7 +4,8 @@
                                 [-w GNN_LOSS_WEIGHT] [-x] [--loss {ce,dice_ce}] [--dice_weight W]
                                 [--dice_smooth S] [--dice_regions {brats,classes}] [--augment] [--aug_flip_axes xyz]
                                 [--aug_flip_prob P] [--aug_scale S] [--aug_shift S] [--aug_noise SIGMA]
-                                [--aug_noise_prob P] [--aug_seed N]
+                                [--aug_noise_prob P] [--aug_seed N] [--aug_rotate DEGREES] [--aug_zoom Z]
+                                [--aug_spatial_prob P]
 
 The reference has no such script (its scripts/train_refinement_cnn.py:21-22 names joint training and declines
 to build it); flags, console report, progress file and folds follow scripts/train_refinement_cnn.py.  DATA is
@@ -16,6 +17,8 @@ generate_joint_predictions and segment_scans load as they load separately traine
 the voxel cross-entropy by cross-entropy + soft Dice (model/losses.py); the node loss stays cross-entropy.
 `--augment` draws one plan per step (gts/augment.py): its scale / shift per modality go onto the node features and
 the image alike, its mirror onto the CNN's input, the labels and the gradient; evaluation is never augmented.
+`--aug_rotate` / `--aug_zoom` (0 by default: off) add a rotation and zoom of the crop, which go the same three ways:
+the gradient returns to the node logits through the resample's deterministic adjoint.
 """
 import argparse
 import os

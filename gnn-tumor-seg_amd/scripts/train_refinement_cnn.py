@@ -6,7 +6,8 @@ Command line, console report, progress file and checkpoint names (`{run}_f{k}.pt
                                          [--loss {ce,dice_ce}] [--dice_weight W] [--dice_smooth S]
                                          [--dice_regions {brats,classes}] [--augment] [--aug_flip_axes xyz]
                                          [--aug_flip_prob P] [--aug_scale S] [--aug_shift S] [--aug_noise SIGMA]
-                                         [--aug_noise_prob P] [--aug_seed N]
+                                         [--aug_noise_prob P] [--aug_seed N] [--aug_rotate DEGREES] [--aug_zoom Z]
+                                         [--aug_spatial_prob P]
 The logits are the `{id}_logits.nii.gz` files `generate_gnn_predictions -f logits` writes.
 
 One deliberate difference: with k > 1 the reference builds every fold's model on the WHOLE dataset, so its
@@ -19,7 +20,9 @@ loss column is the configured loss.
 
 Another: `--augment` mirrors every training crop along random axes, scales and shifts each image modality and adds
 Gaussian noise to some, on the GPU (gts/augment.py); evaluation is never augmented.  The augmentation has
-its own generator (`--aug_seed`), so the order of the samples does not change with it.
+its own generator (`--aug_seed`), so the order of the samples does not change with it.  `--aug_rotate` / `--aug_zoom`
+(both 0 by default: off) also rotate the crop about each axis and zoom it about its centre with probability
+`--aug_spatial_prob`: trilinear for the channels, nearest for the labels, zero outside the crop.
 """
 import argparse
 import os

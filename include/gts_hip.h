@@ -559,6 +559,41 @@ int32_t gts_augment_features_f32(const float* feats, const int64_t* row_ptr, con
                                  int64_t modalities, int64_t n_graphs, double sigma, uint64_t seed,
                                  uint64_t step, void* stream);
 
+/* ---- rotated and zoomed crops ----------------------------------------------------
+ * No counterpart in the reference either.  gts_augment_spatial_f32 (A3) is A1 with a rotation and an
+ * isotropic zoom between the mirror and the affine; gts_augment_spatial_bwd_f32 (A4) is the adjoint of its
+ * resample and mirror.  Fresh outputs, no atomics, no workspace.  matrix: HOST, 9 doubles M[3][3] row-major,
+ * read during the call.
+ *
+ * Definition.  Crop extents n = (cx, cy, cz), centre c_a = (n_a - 1) / 2.  Output voxel o has mirrored index
+ * o', with o'_a = n_a - 1 - o_a on the axes of flip_mask; d = o' - c is exact.  All coordinate work is float64
+ * with no fma:
+ *   p_a = c_a + ((M[a][0] d_0 + M[a][1] d_1) + M[a][2] d_2)
+ *   f_a = floor(p_a), t_a = p_a - f_a, with p_a clamped into [-2, n_a + 1] before any integer conversion.
+ * Float channels: the eight corners are (f_a | f_a + 1); a corner with any index outside [0, n_a - 1] reads
+ * 0.0 (a zero border, no clamping to the edge); lerp along x, then y, then z, each a + (b - a) t in float64;
+ * round once to float32; then A1's per-modality affine (float32 multiply then add, copied when a == 1 and
+ * b == 0) and A1's noise s_c n(v, c), v the C-order index of the OUTPUT voxel, Philox stream 0, unchanged.
+ * Channels >= image_channels are resampled only.
+ * Labels: m_a = floor(p_a + 0.5); a label outside the crop on any axis becomes 0, else it is labels[m].
+ * Adjoint (A4): the resample and the mirror only, no affine and no noise: dy, dx [cx, cy, cz, channels],
+ *   dx[q, k] = float32( sum_o w(o, q) dy[o, k] ),  w = prod_a w_a,
+ *   w_a = 1 - t_a if f_a == q_a, t_a if f_a + 1 == q_a, else 0,
+ * w computed in float64 from the same p(o), the sum in float64 over the contributing o in ascending C-order
+ * of o'.  Two runs are bit-equal.  The candidates of q are the integer o' of the box
+ * c + M^-1 (q - c) +- h, h_a = sum_b |M^-1[a][b]|, widened by one on each side and clipped to the crop (M^-1
+ * is formed here in float64); every candidate recomputes p(o') with the expression above.
+ * Either of x / labels may be NULL (with its output), as for A1; params as for A1.
+ * Errors, before any launch: a missing pointer -> GTS_ERR_NULL; extents and channels as A1 ->
+ * GTS_ERR_SHAPE; flip_mask outside 0..7, a non-finite matrix entry, a singular matrix (zero or non-finite
+ * determinant or inverse) or any h_a > 8 -> GTS_ERR_ARGKIND.  A crop without voxels returns GTS_OK untouched. */
+int32_t gts_augment_spatial_f32(const float* x, const int64_t* labels, const float* params,
+                                const double* matrix, float* x_out, int64_t* labels_out, int64_t cx,
+                                int64_t cy, int64_t cz, int64_t channels, int64_t image_channels,
+                                int32_t flip_mask, uint64_t seed, uint64_t step, void* stream);
+int32_t gts_augment_spatial_bwd_f32(const float* dy, const double* matrix, float* dx, int64_t cx, int64_t cy,
+                                    int64_t cz, int64_t channels, int32_t flip_mask, void* stream);
+
 /* ---- tuning knobs-----------------------------------------------------------------------
  * Process-wide tile selection of the K11 kernels (defaults are the tuned values; used by
  * tools/tune_gemm.py).  Returns GTS_ERR_ARGKIND for an unknown option. */
