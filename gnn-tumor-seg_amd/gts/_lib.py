@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GTS_LIB_PATH: another build of the same library (A/B runs of two builds in one session, tools/); the default is the in-tree build
 LIB_PATH = os.environ.get("GTS_LIB_PATH") or os.path.join(_HERE, "libgts_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "gts_hip.h")
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -130,6 +130,8 @@ SIGNATURES = {
     "gts_dataset_stats_order_stats": [_p, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _i64, _p],
     "gts_dataset_stats_moments": [_p, _i32, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _p],
     "gts_conform_gather": [_p, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _p, _p, _p, _i32, _p, _p],
+    "gts_softmax_accumulate_f32": [_p, _i64, _p, _i64, _i64, _i32, _p],
+    "gts_argmax_scatter_rows_i16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p],
 }
 _RESTYPE = {"gts_error_string": ctypes.c_char_p, "gts_linear_bwd_weight_workspace": _i64,
             "gts_weighted_ce_workspace": _i64, "gts_gat_reduce_workspace": _i64,

@@ -709,6 +709,61 @@ def argmax_scatter(scores, box, relabel=None):
     return out
 
 
+def argmax_scatter_rows(scores, box, relabel=None):
+    """E2.  K17 for channels-last scores: int16 [X,Y,Z] volume, zero outside the box, first-maximum arg-max over
+    the columns of scores [cx * cy * cz, C] (or [cx, cy, cz, C]) inside."""
+    _f32(scores)
+    cx, cy, cz = box.shape
+    if scores.dim() == 4 and tuple(scores.shape[:3]) == box.shape:
+        scores = scores.reshape(cx * cy * cz, -1)
+    if scores.dim() != 2 or scores.shape[0] != cx * cy * cz or scores.shape[1] < 1:
+        raise _lib.GtsError(f"scores must be [{cx * cy * cz}, C] over the crop box, got {tuple(scores.shape)}")
+    scores = scores.contiguous()
+    require_device(scores, relabel, *box.dev)
+    if relabel is not None and (relabel.dtype != torch.int16 or relabel.numel() < scores.shape[1]):
+        raise _lib.GtsError("relabel must be int16 with one entry per class")
+    out = torch.zeros(box.volume_shape, dtype=torch.int16, device=scores.device)
+    if scores.numel():
+        check(_lib.load().gts_argmax_scatter_rows_i16(ptr(scores), ptr(relabel), ptr(box.dev[0]), ptr(box.dev[1]),
+                                                      ptr(box.dev[2]), ptr(out), cx, cy, cz, box.volume_shape[1],
+                                                      box.volume_shape[2], scores.shape[1], current_stream()),
+              "gts_argmax_scatter_rows_i16")
+    return out
+
+
+SOFTMAX_ACCUMULATE_MAX_CLASSES = 8
+
+
+def softmax_accumulate(logit_sets, acc=None):
+    """E1.  acc [rows, C] fp32 (+)= the sum over the tensors of `logit_sets` (each [rows, C] fp32, 1 <= C <= 8) of
+    their row softmax, added in list order with plain fp32 adds: splitting the list over several calls gives the
+    same bits.  acc None: a fresh tensor that starts from zero; otherwise acc is added onto in place.  Returns acc
+    (the SUM: divide by the number of sets for the mean)."""
+    logit_sets = list(logit_sets)
+    if not logit_sets:
+        raise _lib.GtsError("softmax_accumulate: no logit sets")
+    _f32(acc, *logit_sets)
+    first = logit_sets[0]
+    if first.dim() != 2 or not 1 <= first.shape[1] <= SOFTMAX_ACCUMULATE_MAX_CLASSES:
+        raise _lib.GtsError(f"softmax_accumulate: logits must be [rows, 1..{SOFTMAX_ACCUMULATE_MAX_CLASSES}], "
+                            f"got {tuple(first.shape)}")
+    for t in logit_sets[1:]:
+        _expect(t, first.shape, "softmax_accumulate logits")
+    _expect(acc, first.shape, "softmax_accumulate acc")
+    require_device(acc, *logit_sets)
+    overwrite = acc is None
+    if overwrite:
+        acc = torch.empty_like(first)
+    elif any(t.data_ptr() == acc.data_ptr() for t in logit_sets):
+        raise _lib.GtsError("softmax_accumulate: acc must not be one of the logit sets")
+    if first.numel():
+        pointers = (ctypes.c_void_p * len(logit_sets))(*[t.data_ptr() for t in logit_sets])
+        check(_lib.load().gts_softmax_accumulate_f32(pointers, len(logit_sets), ptr(acc), first.shape[0],
+                                                     first.shape[1], int(overwrite), current_stream()),
+              "gts_softmax_accumulate_f32")
+    return acc
+
+
 def label_confusion(pred, truth):
     """K15.  int64 [5, 5] table on the device: entry [cp, ct] counts the positions where the
     predicted label has class cp and the true label class ct (class = label for 0..3, 4 for

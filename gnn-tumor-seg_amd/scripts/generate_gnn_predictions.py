@@ -3,9 +3,14 @@
 Command line and output files match /root/reference/scripts/generate_gnn_predictions.py:76-100.
 The forward pass, the argmax and the node -> voxel projection all stay on the GPU
 (K12 kernels); only the finished volume crosses PCIe for the NIfTI writer.
+
+--also_gnn_weights P [P ...] (with -f preds) averages the node class probabilities of further weight files, e.g. the
+other folds, with the first one's before the arg-max (gts.ensemble).  Logit files stay per member:
+they feed that member's CNN training.
 """
 import argparse
 import os
+import sys
 
 import numpy as np
 import torch
@@ -18,6 +23,7 @@ from gts import dist as gdist
 from gts import ops
 from model.networks import init_graph_net
 from scripts import cleanup as cleanup_flags
+from scripts import ensemble_flags
 from utils.hyperparam_helpers import DEFAULT_BACKGROUND_NODE_LOGITS, EvalParamSet
 
 output_dir = None
@@ -81,6 +87,21 @@ def save_predictions(net, dataset, save_format="logits", cleanup=None):
             save_voxel_logits(mri_id, dataset, logits)
 
 
+def save_ensemble_predictions(predictor, dataset, cleanup=None):
+    """save_predictions -f preds for a gts.ensemble.EnsemblePredictor (--also_gnn_weights): the arg-max of the
+    members' mean node probabilities, projected to voxels; the ranks of a torchrun share the samples as above."""
+    device = _device()
+    relabel = torch.from_numpy(INTERNAL_TO_BRATS).to(device)
+    for index in gdist.rank_share(len(dataset)):
+        mri_id, graph, feats = dataset[index]
+        svs = dataset.get_supervoxel_partitioning(mri_id)
+        voxels = predictor.predict_gnn(graph, feats, svs, relabel, cleanup=cleanup)
+        nifti_io.save_as_nifti(uncrop_to_brats_size(dataset.get_crop(mri_id), voxels),
+                               f"{output_dir}{os.sep}{mri_id}.nii.gz")
+        if cleanup is not None:
+            print(f"{mri_id}: {cleanup.report()}")
+
+
 _FLAGS = (
     ("-d", "--data_dir", Filepaths.PROCESSED_DATA_DIR, "preprocessed dataset directory"),
     ("-p", "--data_prefix", "", "common prefix of the sample folders, e.g. BraTS2021"),
@@ -94,12 +115,18 @@ def build_parser():
     parser = argparse.ArgumentParser(description="GNN inference + node-to-voxel projection on MI355X")
     for short, long_name, default, text in _FLAGS:
         parser.add_argument(short, long_name, default=default, type=str, help=text)
-    return cleanup_flags.add_flags(parser)
+    return ensemble_flags.add_flags(cleanup_flags.add_flags(parser), cnn=False)
 
 
 def main(argv=None):
     global output_dir
     args = build_parser().parse_args(argv)
+    weight_file = os.path.expanduser(args.weight_file)
+    try:
+        members = ensemble_flags.from_args(args, weight_file, None, args.save_format)
+    except ensemble_flags.FlagError as exc:
+        print(f"generate_gnn_predictions: {exc}", file=sys.stderr)
+        return 2
     rank, world_size, _ = gdist.init_from_env()
     fallback = Filepaths.GNN_LOGIT_DIR if args.save_format == "logits" else Filepaths.PRED_DIR
     output_dir = os.path.expanduser(args.output_dir or fallback)
@@ -108,12 +135,16 @@ def main(argv=None):
         os.makedirs(output_dir, exist_ok=True)
     dataset = data_loader.ImageGraphDataset(os.path.expanduser(args.data_dir), args.data_prefix,
                                             read_image=False, read_graph=True, read_label=False)
-    net = load_net_and_weights(os.path.expanduser(args.weight_file))
-    save_predictions(net, dataset, args.save_format, cleanup_flags.from_args(args))
+    if members is not None:
+        save_ensemble_predictions(members.predictor(), dataset, cleanup_flags.from_args(args))
+    else:
+        net = load_net_and_weights(weight_file)
+        save_predictions(net, dataset, args.save_format, cleanup_flags.from_args(args))
     if world_size > 1:
         torch.distributed.barrier()        # every rank's volumes are on disk before any rank reports completion
     print(f"Finished saving {args.save_format} generated by {args.weight_file} in folder {output_dir}")
+    return 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

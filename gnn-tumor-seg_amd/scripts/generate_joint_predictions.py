@@ -11,9 +11,15 @@ stays on the GPU:
 
 The reference materialises the [X,Y,Z,4] voxel logits, copies them to the host for an argmax
 and a 3-D dilation, and builds the [X,Y,Z,8] concatenation before cropping.
+
+--also_gnn_weights P [P ...] with --also_cnn_weights P [P ...] (further members, e.g. the other folds, paired in
+order) and --tta_mirror AXES (mirrored views of the CNN, a non-empty subset of xyz) average class probabilities over
+all members and views before the arg-max (gts.ensemble, DESIGN.md 4s: the convolutions then run on the HIP kernels).
+Without them the path above runs, unchanged.
 """
 import argparse
 import os
+import sys
 
 import numpy as np
 import torch
@@ -26,6 +32,7 @@ from gts import ops
 from model.cnn_model import combine_node_logits_and_image
 from model.networks import CnnRefinementNet, init_graph_net
 from scripts import cleanup as cleanup_flags
+from scripts import ensemble_flags
 from utils.hyperparam_helpers import DEFAULT_BACKGROUND_NODE_LOGITS, EvalParamSet
 
 output_dir = None
@@ -114,6 +121,22 @@ def save_predictions(graph_net, conv_net, dataset, cleanup=None):
             print(f"{mri}: {cleanup.report()}")
 
 
+def save_ensemble_predictions(predictor, dataset, cleanup=None):
+    """save_predictions for a gts.ensemble.EnsemblePredictor (--also_*_weights, --tta_mirror): same files, the
+    ensemble's labels in them."""
+    relabel = torch.from_numpy(INTERNAL_TO_BRATS).to(_device())
+    for mri, graph, node_feats, img in dataset:
+        try:
+            supervoxel_partitioning = dataset.get_supervoxel_partitioning(mri)
+            raw_data_crop = dataset.get_crop(mri)
+        except FileNotFoundError as e:
+            raise FileNotFoundError(f"Couldnt predict {mri} because couldn't read in a required file: {e}")
+        pred = predictor.predict_joint(graph, node_feats, img, supervoxel_partitioning, relabel, cleanup=cleanup)
+        nifti_io.save_as_nifti(uncrop_to_brats_size(raw_data_crop, pred), f"{output_dir}{os.sep}{mri}.nii.gz")
+        if cleanup is not None:
+            print(f"{mri}: {cleanup.report()}")
+
+
 _ARGUMENTS = [
     ("-d", "--data_dir", Filepaths.PROCESSED_DATA_DIR, "path to the directory where data is stored"),
     ("-p", "--data_prefix", "", "A prefix that all data folders share, i.e. BraTS2021."),
@@ -128,12 +151,18 @@ def build_parser():
     parser = argparse.ArgumentParser()
     for short, long_, default, text in _ARGUMENTS:
         parser.add_argument(short, long_, default=default, help=text, type=str)
-    return cleanup_flags.add_flags(parser)
+    return ensemble_flags.add_flags(cleanup_flags.add_flags(parser))
 
 
 def main(argv=None):
     global output_dir
     args = build_parser().parse_args(argv)
+    gnn_weights, cnn_weights = os.path.expanduser(args.gnn_weights), os.path.expanduser(args.cnn_weights)
+    try:
+        members = ensemble_flags.from_args(args, gnn_weights, cnn_weights)
+    except ensemble_flags.FlagError as exc:
+        print(f"generate_joint_predictions: {exc}", file=sys.stderr)
+        return 2
     # the reference falls back on an attribute its parser never defines (:97); predictions go to PRED_DIR
     output_dir = os.path.expanduser(args.output_dir if args.output_dir else Filepaths.PRED_DIR)
     if not os.path.isdir(output_dir):
@@ -141,12 +170,16 @@ def main(argv=None):
         os.makedirs(output_dir)
     dataset = data_loader.ImageGraphDataset(os.path.expanduser(args.data_dir), args.data_prefix,
                                             read_image=True, read_graph=True, read_label=False)
-    graph_net, conv_net = load_nets(args.gnn_type, os.path.expanduser(args.gnn_weights),
-                                    os.path.expanduser(args.cnn_weights))
+    if members is not None:
+        save_ensemble_predictions(members.predictor(args.gnn_type), dataset, cleanup_flags.from_args(args))
+        print(f"Finished saving predictions generated by an ensemble of {members.describe()} in folder {output_dir}")
+        return 0
+    graph_net, conv_net = load_nets(args.gnn_type, gnn_weights, cnn_weights)
     save_predictions(graph_net, conv_net, dataset, cleanup_flags.from_args(args))
     print(f"Finished saving predictions generated by {args.gnn_weights} and {args.cnn_weights} "
           f"in folder {output_dir}")
+    return 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

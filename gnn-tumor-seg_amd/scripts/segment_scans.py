@@ -16,6 +16,13 @@ A scan that raises is reported and skipped; the exit status is 1 when any scan w
     python -m scripts.segment_scans -d INPUT -o OUT -g GNN.pt [-c CNN.pt] [-m GSpool] [-n 15000 -b 0.5 -k 10]
                                     [--min_component_voxels N --connectivity {6,26} --min_enhancing_voxels T]
                                     [--conform]
+                                    [--also_gnn_weights P [P ...] --also_cnn_weights P [P ...]] [--tta_mirror AXES]
+
+--also_gnn_weights / --also_cnn_weights name further members (the other folds' weight files, paired in order) and
+--tta_mirror AXES (a non-empty subset of xyz) adds the CNN's mirrored views: class probabilities are averaged over
+all members and views before the arg-max (gts.ensemble), and the result equals what
+`generate_joint_predictions` (without -c: `generate_gnn_predictions`) writes with the same flags.  With none of them
+the single-model path runs as before.
 
 --min_component_voxels N drops connected components of the predicted whole tumour with fewer than N voxels,
 --min_enhancing_voxels T relabels the enhancing tumour to necrotic core when fewer than T voxels of it remain
@@ -52,6 +59,7 @@ from data_processing.image_processing import uncrop_to_brats_size, uncrop_to_sha
 from data_processing.labels import INTERNAL_TO_BRATS  # noqa: E402
 from gts import conform, graphgen, intake, ops  # noqa: E402
 from scripts import cleanup as cleanup_flags  # noqa: E402
+from scripts import ensemble_flags  # noqa: E402
 from scripts import preprocess_dataset as prep  # noqa: E402
 
 IO_WORKERS = 3     # threads for NIfTI decode / encode around the GPU work
@@ -81,7 +89,7 @@ def build_parser():
     parser.add_argument("--conform", action="store_true",
                         help="read each scan's orientation and voxel spacing from its headers, segment it in the "
                              "LPS 1 mm frame and write the labels on the scan's own grid with its own affine")
-    return cleanup_flags.add_flags(parser)
+    return ensemble_flags.add_flags(cleanup_flags.add_flags(parser))
 
 
 def find_inputs(data_dir, modality_exts, prefix=""):
@@ -117,7 +125,13 @@ class Segmenter:
         else:
             self.mean, self.std = (np.array(s, dtype=np.float32) for s in prep.STANDARDIZATION_STATS)
         gnn = os.path.expanduser(args.gnn_weights)
-        if args.cnn_weights:
+        members = ensemble_flags.from_args(args, gnn, os.path.expanduser(args.cnn_weights))   # None: one model
+        self.ensemble = None
+        if members is not None:
+            self.ensemble = members.predictor(args.gnn_type)
+            self.graph_net, self.conv_net = None, None
+            self.joint = members.cnn is not None
+        elif args.cnn_weights:
             from scripts.generate_joint_predictions import load_nets
 
             self.graph_net, self.conv_net = load_nets(args.gnn_type, gnn, os.path.expanduser(args.cnn_weights))
@@ -156,7 +170,12 @@ class Segmenter:
         feats = res["feats"].to(torch.float32)
         partition = res["partition"]
         tick("graph")
-        if self.conv_net is not None:
+        if self.ensemble is not None:
+            if self.joint:
+                pred = self.ensemble.predict_joint(graph, feats, image, partition, self.relabel, cleanup=self.cleanup)
+            else:
+                pred = self.ensemble.predict_gnn(graph, feats, partition, self.relabel, cleanup=self.cleanup)
+        elif self.conv_net is not None:
             from scripts.generate_joint_predictions import predict_one_sample
 
             pred = predict_one_sample(self.graph_net, self.conv_net, graph, feats, image, partition, self.relabel,
@@ -217,6 +236,13 @@ class Segmenter:
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    try:        # flags that do not go together: found here, before any scan is read or the GPU touched
+        ensemble_flags.from_args(args, args.gnn_weights, args.cnn_weights)
+    except ensemble_flags.FlagError as exc:
+        print(f"segment_scans: {exc}", file=sys.stderr)
+        return 2
+    if ensemble_flags.mirrors_ignored(args, args.cnn_weights):
+        print(ensemble_flags.MIRRORS_IGNORED)
     scans = find_inputs(args.data_dir, args.modality_extensions, args.data_prefix)
     print(f"{len(scans)} scan(s) found; segmentations go to {args.output_dir}")
     try:

@@ -942,6 +942,25 @@ int32_t gts_conform_gather(const void* src, int32_t dtype, int64_t C, int64_t X,
                            int32_t axis1, int32_t axis2, int64_t OX, int64_t OY, int64_t OZ, const int32_t* idx0,
                            const int32_t* idx1, const double* t, int32_t mode, void* dst, void* stream);
 
+/* ---- E1/E2: ensemble prediction over several weight sets and mirrored views (no counterpart in the reference,
+ * whose scripts/generate_joint_predictions.py:27-110 takes one GNN and one CNN weight file) --------------------
+ * E1 softmax_accumulate: acc[r, :] (+)= sum over s = 0 .. n_sets - 1 of softmax(sets[s][r, :]), every tensor
+ *   [rows, classes] fp32 row-major on the device.  `sets` itself is a HOST array of n_sets device pointers; they
+ *   reach the kernel by value, at most 8 per launch, longer lists are chunked here.  softmax is the stable form
+ *   (row maximum subtracted, denominator summed in class order); the sets are added in ascending s, each one
+ *   plain fp32 add onto the running value, so the result does not depend on how a list of sets is split over
+ *   calls.  overwrite != 0 starts from zero instead of reading acc.  acc must not alias a set.
+ *   classes 1..8, n_sets >= 1, rows >= 0 (0: GTS_OK, nothing launched), else GTS_ERR_SHAPE. */
+int32_t gts_softmax_accumulate_f32(const float* const* sets, int64_t n_sets, float* acc, int64_t rows,
+                                   int64_t classes, int32_t overwrite, void* stream);
+/* E2 argmax_scatter_rows: gts_argmax_scatter_i16 for channels-last scores [cx * cy * cz, n_classes]:
+ *   out[xs[i], ys[j], zs[k]] = relabel[argmax_c scores[(i * cy + j) * cz + k, c]] (first maximum; relabel
+ *   optional); the other voxels of the caller-zeroed int16 volume `out` are left alone.  Box operands and
+ *   limits as gts_argmax_scatter_i16. */
+int32_t gts_argmax_scatter_rows_i16(const float* scores, const int16_t* relabel, const int32_t* xs,
+                                    const int32_t* ys, const int32_t* zs, int16_t* out, int64_t cx, int64_t cy,
+                                    int64_t cz, int64_t dim_y, int64_t dim_z, int64_t n_classes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
