@@ -20,6 +20,10 @@ __device__ __forceinline__ int xcd_contiguous_tile(int b, int nb) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
 }
 
+// ReLU of every fused epilogue, with torch's classes: NaN stays NaN (fmaxf would return 0), -0.0 stays -0.0,
+// -Inf gives 0.  One form everywhere, so tiles, panels and chains stay bit-equal.
+__device__ __forceinline__ float relu_f32(float v) { return v < 0.f ? 0.f : v; }
+
 template <int VEC>
 struct Vec;
 template <>

@@ -167,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void conv_kernel(ConvArgs a) {
         const int z = z0 + 4 * (lane >> 4) + r;
         if (z >= a.oz) continue;
         float v = acc[m][j][r] + bias;
-        if (a.relu) v = fmaxf(v, 0.0f);
+        if (a.relu) v = relu_f32(v);
         a.out[((static_cast<int64_t>(x) * a.oy + y) * a.oz + z) * a.cout + co] = v;
       }
     }
@@ -261,12 +261,14 @@ __global__ __launch_bounds__(kBlock) void wgrad_kernel(WgradArgs a) {
       const int vx = kk / 16, vy = (kk / 4) % 4, vz = 4 * (kk % 4);   // k-step: voxels vz .. vz + 3 of row (vx, vy)
       const int hoff = ((vx * kHY + vy) * kHZ + vz) * VS;
       const int v = (vx * kTY + vy) * kTZ + vz + (lane >> 4);
+      // a k-step voxel past the volume: dy is 0 there, and so must x be (0 * Inf from the clamped halo would be NaN)
+      const bool inside = x0 + vx < a.cx && y0 + vy < a.cy && z0 + vz + (lane >> 4) < a.cz;
       float av[MT];
 #pragma unroll
       for (int m = 0; m < MT; ++m) av[m] = dys[v * DS + m * 16 + (lane & 15)];
 #pragma unroll
       for (int n = 0; n < kWgradTilesPerWave; ++n) {
-        const float bv = halo[bbase[n] + hoff];
+        const float bv = inside ? halo[bbase[n] + hoff] : 0.0f;
 #pragma unroll
         for (int m = 0; m < MT; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m], bv, acc[m][n], 0, 0, 0);
       }

@@ -269,7 +269,7 @@ __device__ __forceinline__ void panel_stage(const PanelStage s, float* lds, int 
         if (row < row_end && col_ok) {
           if (relu) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) val[e] = fmaxf(val[e], 0.f);
+            for (int e = 0; e < 4; ++e) val[e] = relu_f32(val[e]);
           }
           if (float_mask) {
 #pragma unroll
@@ -309,7 +309,7 @@ __device__ __forceinline__ void panel_stage(const PanelStage s, float* lds, int 
           if (row < row_end && c < s.rb) {
             const size_t off = static_cast<size_t>(row) * s.ldc + c;
             float val = acc[tm][tn][r] + bs;
-            if (s.relu) val = fmaxf(val, 0.f);
+            if (s.relu) val = relu_f32(val);
             if (s.mask != nullptr) val = s.mask[off] > 0.f ? val : 0.f;
             s.c[off] = val;
           }

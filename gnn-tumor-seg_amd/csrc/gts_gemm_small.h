@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void tiny_fwd_kernel(const GemmArgs p) {
     v4f o = {acc[n], acc[n + 1], acc[n + 2], acc[n + 3]};
     if (p.relu) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.f);
+      for (int e = 0; e < 4; ++e) o[e] = relu_f32(o[e]);
     }
     *reinterpret_cast<v4f*>(out + n) = o;
   }
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void skinny_fwd_kernel(const GemmArgs p) {
         if (p.bias != nullptr) o += *reinterpret_cast<const v4f*>(p.bias + n);
         if (p.relu) {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.f);
+          for (int e = 0; e < 4; ++e) o[e] = relu_f32(o[e]);
         }
         *reinterpret_cast<v4f*>(p.c + static_cast<size_t>(row0 + r) * p.ldc + n) = o;
       }

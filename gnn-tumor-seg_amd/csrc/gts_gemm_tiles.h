@@ -135,7 +135,7 @@ __device__ __forceinline__ void write_tile(const GemmArgs& p, float* lds, float*
             const size_t off = static_cast<size_t>(row) * p.ldc + col;
             if (p.relu) {
 #pragma unroll
-              for (int e = 0; e < 4; ++e) val[e] = fmaxf(val[e], 0.f);
+              for (int e = 0; e < 4; ++e) val[e] = relu_f32(val[e]);
             }
             if (p.mask != nullptr) {
 #pragma unroll
@@ -160,7 +160,7 @@ __device__ __forceinline__ void write_tile(const GemmArgs& p, float* lds, float*
           if (row < p.ra && col < p.rb) {
             const size_t off = static_cast<size_t>(row) * p.ldc + col;
             float val = acc[tm][tn][r] + bias;
-            if (p.relu) val = fmaxf(val, 0.f);
+            if (p.relu) val = relu_f32(val);
             if (p.mask != nullptr) val = p.mask[off] > 0.f ? val : 0.f;
             c[off] = val;
           }
