@@ -16,136 +16,93 @@ ABI_VERSION = 32
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int32
 _i64 = ctypes.c_int64
-_u64 = ctypes.c_uint64
-_f32 = ctypes.c_float
-_f64 = ctypes.c_double
 
-# name -> argtypes (restype is int32 unless noted)
-SIGNATURES = {
-    "gts_abi_version": [],
-    "gts_error_string": [_i32],
-    "gts_spmm_max_fwd_f32": [_p, _p, _p, _p, _p, _i32, _i32, _i64, _i64, _p],
-    "gts_spmm_max_bwd_f32": [_p, _p, _p, _p, _p, _i32, _p, _p, _i64, _i64, _p],
-    "gts_cluster_record_words": [_i32, _i32, _i32, _i32],
-    "gts_cluster_schedule": [_p, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _i64, _p, _p, _p],
-    "gts_cluster_lds_bytes": [_i32, _i32, _i32, _i32],
-    "gts_cluster_uses_counters": [_i64, _i32, _i32, _i32, _i32],
-    "gts_spmm_max_fwd_cluster_f32": [_p, _i64, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _i64, _i64, _p, _p],
-    "gts_spmm_max_bwd_cluster_f32": [_p, _i64, _i32, _i32, _i32, _p, _p, _i32, _p, _i64, _i64, _p, _p],
-    "gts_spmm_sum_f32": [_p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i64, _p],
-    "gts_gat_fwd_f32": [_p, _p, _p, _p, _p, _f32, _p, _p, _i32, _p, _p, _i64, _i64, _i64, _p],
-    "gts_gat_scores_f32": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
-    "gts_gat_reduce_workspace": [_i64, _i64],
-    "gts_gat_act_bwd_f32": [_p, _p, _i32, _p, _p, _p, _i64, _i64, _i64, _p],
-    "gts_gat_cluster_workspace": [_i64, _i32, _i32, _i64, _i32],
-    "gts_gat_attn_f32": [_p, _p, _p, _p, _f32, _p, _i64, _i64, _i64, _p],
-    "gts_gat_fwd_cluster_f32": [_p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, _f32, _p, _i32, _p, _p, _p, _i64,
-                                _i64, _i64, _i64, _i64, _p],
-    "gts_gat_bwd_edge_cluster_f32": [_p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _f32, _p, _p, _p, _i64,
-                                     _i64, _i64, _i64, _i64, _p],
-    "gts_gat_bwd_src_cluster_f32": [_p, _p, _p, _i64, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i64,
-                                    _i64, _i64, _i64, _i64, _p],
-    "gts_gat_param_grad_f32": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p],
-    "gts_gat_bwd_edge_f32": [_p, _p, _p, _p, _p, _p, _p, _f32, _p, _p, _i64, _i64, _i64, _p],
-    "gts_gat_bwd_src_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p],
-    "gts_project_rows_i16": [_p, _p, _p, _p, _i64, _i64, _i32, _p],
-    "gts_project_argmax_i16": [_p, _p, _p, _p, _i64, _i64, _i64, _p],
-    "gts_project_argmax_occupancy_i16": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p],
-    "gts_crop_concat_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p],
-    "gts_argmax_scatter_i16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p],
-    "gts_crop_concat_rows_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p],
-    "gts_crop_concat_rows_bwd_f32": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
-                                     _p],
-    "gts_adamw_f32": [_p, _p, _p, _p, _i64, _f64, _f64, _f64, _f64, _f64, _i64, _p],
-    "gts_label_confusion_workspace": [_i64],
-    "gts_label_confusion_i16": [_p, _p, _p, _p, _i64, _i64, _p],
-    "gts_linear_fwd_f32": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _p, _p, _p],
-    "gts_relu_bits_bytes": [_i64, _i64],
-    "gts_relu_bits_pay": [_i64, _i64],
-    "gts_linear_bwd_input_f32": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p],
-    "gts_linear_bwd_input_t_f32": [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p],
-    "gts_linear_bwd_input_t_act_workspace": [_i64, _i64],
-    "gts_linear_bwd_input_t_act_f32": [_p, _p, _p, _p, _p, _i32, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p],
-    "gts_transpose_batch_f32": [_p, _p, _i32, _i64, _i64, _p],
-    "gts_packed_weight_floats": [_i64, _i64],
-    "gts_pack_weights_f32": [_p, _p, _p, _i32, _i64, _i64, _i32, _p],
-    "gts_gat_fc_scores_workspace": [_i64, _i64, _i64],
-    "gts_gat_fc_scores_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p],
-    "gts_linear_fwd_chain_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _i64, _i32, _p, _p, _p],
-    "gts_linear_bwd_input_chain_t_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p],
-    "gts_linear_bwd_weight_workspace": [_i64, _i64, _i64, _i32],
-    "gts_linear_bwd_weight_f32": [_p, _p, _p, _p, _i32, _p, _i64, _i64, _i64, _i64, _p],
-    "gts_sage_pool_stack_fwd_arena": [_i64, _p, _i32, _i32, _i32, _i32, _p],
-    "gts_sage_pool_stack_fwd_f32": [_p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _i64, _p, _i32, _i32, _i32, _i32, _p, _i64, _p],
-    "gts_sage_pool_stack_bwd_scratch": [_i64, _p, _i32, _i32],
-    "gts_sage_pool_stack_bwd_f32": [_p, _p, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _i64, _p, _i32, _i32, _i32, _p, _p, _p,
-                                    _p, _i64, _p],
-    "gts_set_option": [_i32, _i32],
-    "gts_get_option": [_i32],
-    "gts_weighted_ce_workspace": [_i64],
-    "gts_weighted_ce_f32": [_p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _p],
-    "gts_dice_ce_workspace": [_i64, _i32],
-    "gts_dice_ce_fwd_f32": [_p, _p, _p, _p, _i32, _f64, _f64, _f64, _p, _p, _i64, _i64, _i64, _p],
-    "gts_dice_ce_bwd_f32": [_p, _p, _p, _p, _i32, _f64, _f64, _f64, _p, _p, _p, _i64, _i64, _p],
-    "gts_augment_crop_f32": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i32, _u64, _u64, _p],
-    "gts_augment_features_f32": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f64, _u64, _u64, _p],
-    "gts_augment_spatial_f32": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i32, _u64, _u64, _p],
-    "gts_augment_spatial_bwd_f32": [_p, _p, _p, _i64, _i64, _i64, _i64, _i32, _p],
-    "gts_collate_plan": [_p, _i32, _i64, _p, _i32, _p],
-    "gts_collate_batch": [_p, _i32, _i64, _p, _i32, _p, _i64, _i32, _p],
-    "gts_gg_gaussian_f64": [_p, _p, _p, _p, _i32, _f64, _i64, _i64, _i64, _i64, _p],
-    "gts_gg_slic_assign_f64": [_p, _p, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _f64, _p, _p, _p, _p],
-    "gts_gg_slic_update_f64": [_p, _p, _p, _i32, _i64, _i64, _i64, _i64, _p, _p],
-    "gts_gg_enforce_connectivity": [_p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p],
-    "gts_gg_sv_stats_workspace": [_i64, _i32],
-    "gts_gg_sv_stats": [_p, _p, _p, _i64, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _p],
-    "gts_gg_discard_f64": [_p, _p, _p, _i32, _i32, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
-    "gts_gg_knn_candidates_f64": [_p, _i32, _i32, _p, _p],
-    "gts_gg_knn_greedy": [_p, _i32, _i32, _p, _p, _p],
-    "gts_gg_touching_workspace": [_i32],
-    "gts_gg_touching_count_i16": [_p, _i64, _i64, _i64, _i32, _p, _p, _p],
-    "gts_gg_touching_emit": [_p, _i32, _p, _p, _p],
-    "gts_conv3d_fwd_workspace": [_i32, _i32],
-    "gts_conv3d_fwd_f32": [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _i32, _p, _i64, _p],
-    "gts_conv3d_bwd_data_workspace": [_i64, _i64, _i64, _i32, _i32],
-    "gts_conv3d_bwd_data_f32": [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _p, _i64, _p],
-    "gts_conv3d_bwd_weight_workspace": [_i64, _i64, _i64, _i32, _i32],
-    "gts_conv3d_bwd_weight_f32": [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _i32, _p, _i64, _p],
-    "gts_hd95_workspace": [_i64, _i64, _i64],
-    "gts_hd95_order_stats_i16": [_p, _p, _i64, _i64, _i64, _i32, _p, _p, _i64, _p],
-    "gts_components_workspace": [_i64, _i64, _i64],
-    "gts_components_roots_i16": [_p, _i64, _i64, _i64, _i32, _p, _p, _i64, _p],
-    "gts_components_filter_i16": [_p, _i64, _i64, _i64, _i32, _i64, _i32, _i64, _i32, _p, _p, _p, _i64, _p],
-    "gts_lesionwise_workspace": [_i64, _i64, _i64],
-    "gts_lesionwise_table_ints": [_i64, _i64, _i64],
-    "gts_lesionwise_dilate_i16": [_p, _i64, _i64, _i64, _i32, _i32, _p, _p, _i64, _p],
-    "gts_lesionwise_tables_i16": [_p, _p, _p, _i64, _i64, _i64, _i32, _p, _i64, _p, _i64, _p],
-    "gts_lesionwise_masks_i16": [_p, _p, _p, _i64, _i64, _i64, _i32, _i32, _p, _i64, _p, _p, _p, _p],
-    "gts_intake_occupancy": [_p, _i32, _i64, _i64, _i64, _p, _p, _p, _p, _p],
-    "gts_intake_select_workspace": [],
-    "gts_intake_order_stats": [_p, _i32, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _i64, _p],
-    "gts_intake_standardize": [_p, _i32, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p],
-    "gts_dataset_stats_workspace": [_i64, _i64, _i64],
-    "gts_dataset_stats_mask": [_p, _i32, _p, _i64, _i64, _i64, _p, _p, _i64, _p],
-    "gts_dataset_stats_order_stats": [_p, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _i64, _p],
-    "gts_dataset_stats_moments": [_p, _i32, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _p],
-    "gts_conform_gather": [_p, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _p, _p, _p, _i32, _p, _p],
-    "gts_softmax_accumulate_f32": [_p, _i64, _p, _i64, _i64, _i32, _p],
-    "gts_argmax_scatter_rows_i16": [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p],
-}
-_RESTYPE = {"gts_error_string": ctypes.c_char_p, "gts_linear_bwd_weight_workspace": _i64,
-            "gts_weighted_ce_workspace": _i64, "gts_gat_reduce_workspace": _i64,
-            "gts_dice_ce_workspace": _i64,
-            "gts_label_confusion_workspace": _i64, "gts_gat_fc_scores_workspace": _i64,
-            "gts_relu_bits_bytes": _i64, "gts_cluster_record_words": _i64, "gts_sage_pool_stack_fwd_arena": _i64, "gts_sage_pool_stack_bwd_scratch": _i64, "gts_cluster_lds_bytes": _i64,
-            "gts_linear_bwd_input_t_act_workspace": _i64, "gts_gat_cluster_workspace": _i64,
-            "gts_packed_weight_floats": _i64, "gts_gg_sv_stats_workspace": _i64, "gts_gg_touching_workspace": _i64,
-            "gts_conv3d_fwd_workspace": _i64, "gts_conv3d_bwd_data_workspace": _i64,
-            "gts_conv3d_bwd_weight_workspace": _i64, "gts_hd95_workspace": _i64,
-            "gts_intake_select_workspace": _i64, "gts_dataset_stats_workspace": _i64,
-            "gts_components_workspace": _i64, "gts_lesionwise_workspace": _i64, "gts_lesionwise_table_ints": _i64}
 
-COLLATE_MAX_SCHEDULES = 6      # GTS_COLLATE_MAX_SCHEDULES
+class GtsError(RuntimeError):
+    pass
+
+
+# ---------------------------------------------------------------- the header is the ABI
+# what an entry point takes by value; everything with a '*' is handed over as an address
+_BY_VALUE = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+             "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double}
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(GTS_\w+)[ \t]+\(?[ \t]*(-?\d+)[ \t]*\)?[ \t]*$", re.M)
+_STRUCT = re.compile(r"\btypedef\s+struct\b[^{;]*\{[^{}]*\}\s*\w+\s*;")
+_PROTOTYPE = re.compile(r"(?P<ret>[\w\s*]+?)\b(?P<name>\w+)\s*\((?P<args>[^()]*)\)")
+
+
+def _ctype(decl, statement, returned=False):
+    """ctypes type of one parameter (or return) declaration of `statement`; refuses what it does not know."""
+    words = decl.replace("*", " * ").split()
+    if "*" in words:
+        return ctypes.c_char_p if returned and words == ["const", "char", "*"] else _p
+    words = [w for w in words if w != "const"]
+    if returned and words == ["void"]:
+        return None
+    if not returned and len(words) > 1:
+        words = words[:-1]                  # the parameter's name
+    if len(words) == 1 and words[0] in _BY_VALUE:
+        return _BY_VALUE[words[0]]
+    raise GtsError(f"gts_hip.h: cannot bind `{decl.strip()}` of `{statement}`: by value only "
+                   f"{', '.join(_BY_VALUE)} are taken (a struct goes by pointer)")
+
+
+def parse_header(text):
+    """(signatures {name: (restype, [argtypes])}, constants {GTS_NAME: int}) of C header text: every prototype
+    and every integer #define.  Strict: a declaration it cannot turn into ctypes raises GtsError."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    constants = {name: int(value) for name, value in _DEFINE.findall(text)}
+    text = re.sub(r"^[ \t]*#[^\n]*$", " ", text, flags=re.M)
+    text = _STRUCT.sub(" ", text)
+    text = re.sub(r'\bextern\s+"C"\s*\{', " ", text)
+    *statements, tail = text.split(";")
+    if tail.strip() not in ("", "}"):       # the brace that closes extern "C"
+        raise GtsError(f"gts_hip.h: cannot parse `{' '.join(tail.split())}`")
+    signatures = {}
+    for statement in statements:
+        statement = " ".join(statement.split())
+        m = _PROTOTYPE.fullmatch(statement)
+        if m is None:
+            raise GtsError(f"gts_hip.h: cannot parse `{statement}`")
+        params = [a.strip() for a in m["args"].split(",")]
+        if params in ([""], ["void"]):
+            params = []
+        if "..." in params or "" in params or "[" in m["args"]:
+            raise GtsError(f"gts_hip.h: cannot bind `{statement}`: variadic, array or empty parameter")
+        signatures[m["name"]] = (_ctype(m["ret"], statement, returned=True), [_ctype(a, statement) for a in params])
+    return signatures, constants
+
+
+_parsed = {}
+
+
+def _header(path):
+    if path not in _parsed:
+        with open(path) as f:
+            _parsed[path] = parse_header(f.read())
+    return _parsed[path]
+
+
+def signatures(header_path=HEADER_PATH):
+    """name -> (restype, argtypes) of every entry point include/gts_hip.h declares: what load() binds."""
+    return _header(header_path)[0]
+
+
+def const(name):
+    """Value of an integer `#define GTS_*` of include/gts_hip.h."""
+    try:
+        return _header(HEADER_PATH)[1][name]
+    except KeyError:
+        raise GtsError(f"gts_hip.h defines no integer constant {name}") from None
+
+
+def declared_symbols(header_path=HEADER_PATH):
+    """Every function name declared in include/gts_hip.h."""
+    return sorted(signatures(header_path))
+
+
+COLLATE_MAX_SCHEDULES = const("GTS_COLLATE_MAX_SCHEDULES")
 
 
 class CollateMember(ctypes.Structure):
@@ -173,17 +130,6 @@ class CollatePlan(ctypes.Structure):
 _lib = None
 
 
-class GtsError(RuntimeError):
-    pass
-
-
-def declared_symbols(header_path=HEADER_PATH):
-    """Every function name declared in include/gts_hip.h."""
-    with open(header_path) as f:
-        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(gts_[a-z0-9_]+)\s*\(", text)))
-
-
 def load():
     """Load the HIP library once; raise loudly when it has not been built."""
     global _lib
@@ -194,10 +140,9 @@ def load():
             f"{LIB_PATH} is missing: build it with `python __graft_entry__.py` (hipcc, gfx950). "
             "The gts operators have no CPU or PyTorch fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
+    for name, (restype, argtypes) in signatures().items():
         fn = getattr(lib, name)  # AttributeError -> the .so is stale; surface it
-        fn.argtypes = argtypes
-        fn.restype = _RESTYPE.get(name, _i32)
+        fn.argtypes, fn.restype = argtypes, restype
     if lib.gts_abi_version() != ABI_VERSION:
         raise GtsError(f"libgts_hip.so ABI {lib.gts_abi_version()} != expected {ABI_VERSION}: rebuild")
     # tuning knobs from the environment, e.g. GTS_OPTIONS="1=5,3=1" (option=value pairs, gts_set_option)

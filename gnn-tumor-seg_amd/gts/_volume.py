@@ -5,6 +5,7 @@ import torch
 
 from . import _lib
 from ._lib import require_device
+from ._operands import scratch
 
 
 def lift_shape(shape, what):
@@ -51,4 +52,4 @@ def workspace(size_fn, x, y, z, device, what):
     size = size_fn(x, y, z)
     if size <= 0:
         raise _lib.GtsError(f"{what}: volume {x}x{y}x{z} is outside the kernels' limits")
-    return torch.empty(size, dtype=torch.uint8, device=device), size
+    return scratch(size, device, torch.uint8), size

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import check, current_stream, ptr, require_device
-from .ops import _expect, _f32
+from ._operands import expect, f32, scratch
 
 MAX_CHANNELS = 32
 
@@ -24,7 +24,7 @@ def _channels_ok(*counts):
 def _operands(x=None, w=None, b=None, dy=None, h=None, dims=None):
     """Host-side checks of every operand before a launch: fp32, contiguous, one device, and shapes that agree
     with the weights and the volume (the kernels index by the sizes they are given)."""
-    _f32(x, w, b, dy, h)
+    f32(x, w, b, dy, h)
     require_device(x, w, b, dy, h)
     if w is not None and (w.dim() != 5 or tuple(w.shape[2:]) != (5, 5, 5)):
         raise _lib.GtsError(f"conv3d: weight must be [Cout, Cin, 5, 5, 5], got {tuple(w.shape)}")
@@ -34,20 +34,16 @@ def _operands(x=None, w=None, b=None, dy=None, h=None, dims=None):
         raise _lib.GtsError(f"conv3d: volume dimensions must be three positive sizes, got {dims}")
 
 
-def _scratch(nbytes, device):
-    return torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=device)
-
-
 def conv3d_fwd(x, w, b, relu):
     """C1 / C2: act(conv(x) + b) for channels-last x [cx, cy, cz, Cin] -> [V, Cout]."""
     _operands(x=x, w=w, b=b)
     cx, cy, cz, cin = x.shape
     cout = w.shape[0]
     _channels_ok(cin, cout)
-    _expect(w, (cout, cin, 5, 5, 5), "conv3d_fwd weight")
-    _expect(b, (cout,), "conv3d_fwd bias")
+    expect(w, (cout, cin, 5, 5, 5), "conv3d_fwd weight")
+    expect(b, (cout,), "conv3d_fwd bias")
     lib = _lib.load()
-    ws = _scratch(lib.gts_conv3d_fwd_workspace(cin, cout), x.device)
+    ws = scratch(lib.gts_conv3d_fwd_workspace(cin, cout), x.device)
     y = torch.empty((cx * cy * cz, cout), dtype=torch.float32, device=x.device)
     check(lib.gts_conv3d_fwd_f32(ptr(x), ptr(w), ptr(b), ptr(y), cx, cy, cz, cin, cout, int(relu), ptr(ws),
                                  ws.numel() * 4, current_stream()), "gts_conv3d_fwd_f32")
@@ -62,10 +58,10 @@ def conv3d_bwd_data(dy, w, dims, h=None):
     _channels_ok(cin, cout)
     cx, cy, cz = dims
     v = cx * cy * cz
-    _expect(dy, (v, cout), "conv3d_bwd_data dy")
-    _expect(h, (v, cin), "conv3d_bwd_data h")
+    expect(dy, (v, cout), "conv3d_bwd_data dy")
+    expect(h, (v, cin), "conv3d_bwd_data h")
     lib = _lib.load()
-    ws = _scratch(lib.gts_conv3d_bwd_data_workspace(cx, cy, cz, cin, cout), dy.device)
+    ws = scratch(lib.gts_conv3d_bwd_data_workspace(cx, cy, cz, cin, cout), dy.device)
     dx = torch.empty((cx * cy * cz, cin), dtype=torch.float32, device=dy.device)
     check(lib.gts_conv3d_bwd_data_f32(ptr(dy), ptr(w), ptr(h), ptr(dx), cx, cy, cz, cin, cout, ptr(ws),
                                       ws.numel() * 4, current_stream()), "gts_conv3d_bwd_data_f32")
@@ -78,9 +74,9 @@ def conv3d_bwd_weight(x, dy, cout, want_bias=True):
     _operands(x=x, dy=dy)
     cx, cy, cz, cin = x.shape
     _channels_ok(cin, cout)
-    _expect(dy, (cx * cy * cz, cout), "conv3d_bwd_weight dy")
+    expect(dy, (cx * cy * cz, cout), "conv3d_bwd_weight dy")
     lib = _lib.load()
-    ws = _scratch(lib.gts_conv3d_bwd_weight_workspace(cx, cy, cz, cin, cout), x.device)
+    ws = scratch(lib.gts_conv3d_bwd_weight_workspace(cx, cy, cz, cin, cout), x.device)
     dw = torch.empty((cout, cin, 5, 5, 5), dtype=torch.float32, device=x.device)
     db = torch.empty(cout, dtype=torch.float32, device=x.device) if want_bias else None
     check(lib.gts_conv3d_bwd_weight_f32(ptr(x), ptr(dy), ptr(dw), ptr(db), cx, cy, cz, cin, cout, ptr(ws),
@@ -117,9 +113,7 @@ def refinement_logits(x, net):
         raise _lib.GtsError(f"refinement_logits takes [cx, cy, cz, C], got {tuple(x.shape)}")
     c1, c2 = net.conv_layers[0], net.conv_layers[1]
     params = (c1.weight, c1.bias, c2.weight, c2.bias)
-    for t in (x, *params):
-        if t.dtype != torch.float32:
-            raise _lib.GtsError(f"gts kernels are fp32: got {t.dtype}")
+    f32(x, *params)
     x = x.contiguous()
     require_device(x, *[p.detach() for p in params])
     if x.shape[3] != c1.in_channels or c2.in_channels != c1.out_channels:

@@ -13,10 +13,12 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check, current_stream, ptr, require_device
+from ._operands import StreamBuffers, f32
 
 # bench.py installs a callable here, timer(kind, flops, launch) with kind in {"fwd", "igrad",
 # "wgrad"}, to bracket every K11 launch with HIP events; None in normal use.
 GEMM_TIMER = None
+_OPT_GEMM_TILE = _lib.const("GTS_OPT_GEMM_TILE")
 
 
 class row_count_invariant:
@@ -33,8 +35,8 @@ class row_count_invariant:
         with row_count_invariant._lock:
             if row_count_invariant._depth == 0:
                 lib = _lib.load()
-                row_count_invariant._saved = int(lib.gts_get_option(1))
-                check(lib.gts_set_option(1, -2), "gts_set_option")
+                row_count_invariant._saved = int(lib.gts_get_option(_OPT_GEMM_TILE))
+                check(lib.gts_set_option(_OPT_GEMM_TILE, -2), "gts_set_option")
             row_count_invariant._depth += 1
         return self
 
@@ -42,25 +44,17 @@ class row_count_invariant:
         with row_count_invariant._lock:
             row_count_invariant._depth -= 1
             if row_count_invariant._depth == 0:
-                check(_lib.load().gts_set_option(1, row_count_invariant._saved), "gts_set_option")
+                check(_lib.load().gts_set_option(_OPT_GEMM_TILE, row_count_invariant._saved), "gts_set_option")
         return False
 
 
 def _timed(kind, flops, launch):
     return GEMM_TIMER(kind, flops, launch) if GEMM_TIMER is not None else launch()
 
-_workspaces = {}
 
-
-def _workspace(device, nbytes):
-    """Caller-owned scratch for the split-reduction weight gradient (grown on demand, reused:
-    kernels on one stream run in order, so one buffer per (device, stream) is enough)."""
-    key = (device, current_stream())
-    buf = _workspaces.get(key)
-    if buf is None or buf.numel() * 4 < nbytes:
-        buf = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
-        _workspaces[key] = buf
-    return buf
+# caller-owned scratch of the split-reduction weight gradient and of the bias gradient in an epilogue: one buffer per
+# (device, stream), grown on demand
+_gemm_ws = StreamBuffers()
 
 
 def _pad4_cols(t):
@@ -85,10 +79,9 @@ def _same(a, b, what):
         raise _lib.GtsError(f"shapes do not match: {what} ({a} vs {b})")
 
 
-def _chk(*tensors):
-    for t in tensors:
-        if t is not None and t.dtype != torch.float32:
-            raise _lib.GtsError(f"gts GEMMs are fp32: got {t.dtype}")
+def _operands(*tensors):
+    """fp32, contiguous and on one device, which is returned."""
+    f32(*tensors)
     return require_device(*tensors)
 
 
@@ -160,7 +153,7 @@ def pack_weights(mats, transposed=False, want_plain=False):
         return ([], []) if want_plain else []
     rows, cols = mats[0].shape
     mats = [m.contiguous() for m in mats]
-    dev = _chk(*mats)
+    dev = _operands(*mats)
     for m in mats:
         _same(tuple(m.shape), (rows, cols), "matrices of one pack batch")
     lib = _lib.load()
@@ -192,7 +185,7 @@ def linear_fwd(a0, w0, a1=None, w1=None, bias=None, relu=False, relu_bits=None, 
     a0, w0 = _pad4_cols(a0), _pad4_cols(w0)
     if a1 is not None:
         a1, w1 = _pad4_cols(a1), _pad4_cols(w1)
-    dev = _chk(a0, w0, a1, w1, bias)
+    dev = _operands(a0, w0, a1, w1, bias)
     m, n = a0.shape[0], w0.shape[0]
     _chk_bits(relu_bits, m, n, "relu_bits")
     out = torch.empty((m, n), dtype=torch.float32, device=dev)
@@ -232,7 +225,7 @@ def linear_fwd_chain(a0, w0, a1, w1, bias, relu, w2, bias2, relu2, relu_bits=Non
     if n % 4 or k0 % 4 or k1 % 4:
         raise _lib.GtsError("linear_fwd_chain needs widths that are multiples of 4")
     a0, w0, a1, w1, bias, w2, bias2 = _dense(a0, w0, a1, w1, bias, w2, bias2)
-    dev = _chk(a0, w0, a1, w1, bias, w2, bias2)
+    dev = _operands(a0, w0, a1, w1, bias, w2, bias2)
     _chk_bits(relu_bits, m, n, "relu_bits")
     out = torch.empty((m, n), dtype=torch.float32, device=dev)
     out2 = torch.empty((m, n2), dtype=torch.float32, device=dev)
@@ -264,7 +257,7 @@ def linear_bwd_input_chain_t(g0, w0t, g1, w1t, relu_mask, w2t, relu_bits=None, p
     if k % 4 or n0 % 4 or n1 % 4:
         raise _lib.GtsError("linear_bwd_input_chain_t needs widths that are multiples of 4")
     g0, w0t, g1, w1t, relu_mask, w2t = _dense(g0, w0t, g1, w1t, relu_mask, w2t)
-    dev = _chk(g0, w0t, g1, w1t, relu_mask, w2t)
+    dev = _operands(g0, w0t, g1, w1t, relu_mask, w2t)
     _chk_bits(relu_bits if relu_mask is not None else None, m, k, "relu_bits")
     relu_bits = relu_bits if relu_mask is not None else None
     gin = torch.empty((m, k), dtype=torch.float32, device=dev)
@@ -296,7 +289,7 @@ def linear_bwd_input(g0, w0, g1=None, w1=None, relu_mask=None):
         g1, w1 = _pad4_cols(g1), _pad4_cols(_pad4_rows(w1))
     if relu_mask is not None:
         relu_mask = _pad4_cols(relu_mask)
-    dev = _chk(g0, w0, g1, w1, relu_mask)
+    dev = _operands(g0, w0, g1, w1, relu_mask)
     m = g0.shape[0]
     gin = torch.empty((m, kp), dtype=torch.float32, device=dev)
     n0, n1 = g0.shape[1], g1.shape[1] if g1 is not None else 0
@@ -314,7 +307,7 @@ def transpose_batch(mats):
         return []
     rows, cols = mats[0].shape
     mats = [m.contiguous() for m in mats]
-    dev = _chk(*mats)
+    dev = _operands(*mats)
     for m in mats:
         _same(tuple(m.shape), (rows, cols), "matrices of one transpose batch")
     out = torch.empty((len(mats), cols, rows), dtype=torch.float32, device=dev)
@@ -342,7 +335,7 @@ def linear_bwd_input_t(g0, w0t, g1=None, w1t=None, relu_mask=None, relu_bits=Non
     if k % 4 or n0 % 4 or n1 % 4:
         raise _lib.GtsError("linear_bwd_input_t needs widths that are multiples of 4 (use linear_bwd_input)")
     g0, w0t, g1, w1t, relu_mask = _dense(g0, w0t, g1, w1t, relu_mask)
-    dev = _chk(g0, w0t, g1, w1t, relu_mask)
+    dev = _operands(g0, w0t, g1, w1t, relu_mask)
     relu_bits = relu_bits if relu_mask is not None else None
     _chk_bits(relu_bits, m, k, "relu_bits")
     gin = torch.empty((m, k), dtype=torch.float32, device=dev)
@@ -371,12 +364,12 @@ def linear_bwd_input_t_act(g0, w0t, act_out, activation, g1=None, w1t=None, want
     if k % 4 or n0 % 4 or n1 % 4:
         raise _lib.GtsError("linear_bwd_input_t_act needs widths that are multiples of 4")
     g0, w0t, g1, w1t, act_out = _dense(g0, w0t, g1, w1t, act_out)
-    dev = _chk(g0, w0t, g1, w1t, act_out)
+    dev = _operands(g0, w0t, g1, w1t, act_out)
     lib = _lib.load()
     gin = torch.empty((m, k), dtype=torch.float32, device=dev)
     g_bias = torch.empty(k, dtype=torch.float32, device=dev) if want_bias_grad else None
     nbytes = lib.gts_linear_bwd_input_t_act_workspace(m, k) if want_bias_grad else 0
-    ws = _workspace(dev, nbytes) if want_bias_grad else None
+    ws = _gemm_ws.get(dev, nbytes) if want_bias_grad else None
     table = _packed_array(packed, (w0t, w1t))
     _timed("igrad", 2.0 * m * k * (n0 + n1), lambda: check(
         lib.gts_linear_bwd_input_t_act_f32(ptr(g0), ptr(w0t), ptr(g1), ptr(w1t), ptr(act_out), activation, ptr(gin),
@@ -401,7 +394,7 @@ def linear_bwd_weight_multi(problems):
     n, k = problems[0][0].shape[1], problems[0][1].shape[1]
     gs = [_pad4_cols(g) for g, _, _ in problems]
     acts = [_pad4_cols(a) for _, a, _ in problems]
-    dev = _chk(*gs, *acts)
+    dev = _operands(*gs, *acts)
     m, n_p, k_p = gs[0].shape[0], gs[0].shape[1], acts[0].shape[1]
     for g, a in zip(gs, acts):
         if g.shape != (m, n_p) or a.shape != (m, k_p):
@@ -415,7 +408,7 @@ def linear_bwd_weight_multi(problems):
     else:
         lib = _lib.load()
         nbytes = lib.gts_linear_bwd_weight_workspace(m, n_p, k_p, q)
-        ws = _workspace(dev, nbytes)
+        ws = _gemm_ws.get(dev, nbytes)
         arr = ctypes.c_void_p * q
         _timed("wgrad", 2.0 * m * n_p * k_p * q, lambda: check(
             lib.gts_linear_bwd_weight_f32(arr(*[ptr(t) for t in gs]), arr(*[ptr(t) for t in acts]),

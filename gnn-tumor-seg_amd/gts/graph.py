@@ -175,6 +175,17 @@ class _DeviceSchedule:
         self.host, self.packed = sched, records
         return self
 
+    @staticmethod
+    def launch_args(ds, with_tag=False):
+        """The arguments that lead every clustered launch (include/gts_hip.h: rec, n_clusters, max_rows, max_srcs,
+        loc_words; with_tag: also `tagged`, which the GAT kernels take).  ds None: the all-zero form by which the stack
+        entry points are told that there is no schedule."""
+        if ds is None:
+            return (None, 0, 0, 0, 0, 0) if with_tag else (None, 0, 0, 0, 0)
+        h = ds.host
+        lead = (ds.packed.data_ptr(), h.n_clusters, h.limits[0], h.limits[1], h.loc_words)
+        return lead + (1 if h.tagged else 0,) if with_tag else lead
+
 
 class Graph:
     def __init__(self, src, dst, num_nodes, batch_num_nodes=None, _prebuilt=None, _members=None):

@@ -14,10 +14,12 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import check, current_stream
+from ._operands import scratch
 
-MAX_SV = 32767   # GTS_GG_MAX_SV: the partition is int16, as in the reference
-MAX_K = 32       # GTS_GG_MAX_K
-MAX_RADIUS = 16  # GTS_GG_MAX_RADIUS
+MAX_SV = _lib.const("GTS_GG_MAX_SV")   # the partition is int16, as in the reference
+MAX_K = _lib.const("GTS_GG_MAX_K")
+MAX_RADIUS = _lib.const("GTS_GG_MAX_RADIUS")
 QUANTILES = (0.1, 0.25, 0.5, 0.75, 0.9)
 
 
@@ -37,14 +39,6 @@ def _tensor(x, dtype, dev=None):
 
 def _out(t, as_numpy):
     return t.cpu().numpy() if as_numpy else t
-
-
-def _stream():
-    return _lib.current_stream()
-
-
-def _check(code, what):
-    _lib.check(code, what)
 
 
 def _volume(image):
@@ -123,9 +117,9 @@ def gaussian(image, sigma=1.0, scale=1.0):
     wt = torch.from_numpy(weights).to(img.device)
     out = torch.empty_like(img)
     tmp = torch.empty_like(img)
-    _check(_lib.load().gts_gg_gaussian_f64(img.data_ptr(), out.data_ptr(), tmp.data_ptr(), wt.data_ptr(),
-                                           len(weights) - 1, float(scale), d, h, w, c, _stream()),
-           "gts_gg_gaussian_f64")
+    check(_lib.load().gts_gg_gaussian_f64(img.data_ptr(), out.data_ptr(), tmp.data_ptr(), wt.data_ptr(),
+                                          len(weights) - 1, float(scale), d, h, w, c, current_stream()),
+          "gts_gg_gaussian_f64")
     return _out(out.reshape(image.shape), as_numpy)
 
 
@@ -153,13 +147,13 @@ def slic_rounds(scaled, n_segments, max_iter=10, on_round=None):
     sw = 1.0 / (step ** 2)
     for i in range(max_iter):
         if i > 0:
-            _check(lib.gts_gg_slic_update_f64(img.data_ptr(), labels.data_ptr(), centres.data_ptr(), k, d, h, w, c,
-                                              bbox.data_ptr(), _stream()), "gts_gg_slic_update_f64")
+            check(lib.gts_gg_slic_update_f64(img.data_ptr(), labels.data_ptr(), centres.data_ptr(), k, d, h, w, c,
+                                             bbox.data_ptr(), current_stream()), "gts_gg_slic_update_f64")
             if on_round:
                 on_round(i, "update")
-        _check(lib.gts_gg_slic_assign_f64(img.data_ptr(), centres.data_ptr(), k, d, h, w, c, *window, sw,
-                                          labels.data_ptr(), best.data_ptr(), winner.data_ptr(), _stream()),
-               "gts_gg_slic_assign_f64")
+        check(lib.gts_gg_slic_assign_f64(img.data_ptr(), centres.data_ptr(), k, d, h, w, c, *window, sw,
+                                         labels.data_ptr(), best.data_ptr(), winner.data_ptr(), current_stream()),
+              "gts_gg_slic_assign_f64")
         if on_round:
             on_round(i, "assign")
         if i == 0 and int(labels.min()) < 0:
@@ -183,9 +177,9 @@ def _enforce_connectivity(labels, min_size, max_size):
     out = np.empty_like(lab)
     queue = np.empty(max(int(max_size), 1), dtype=np.int64)
     n = ctypes.c_int32()
-    _check(_lib.load().gts_gg_enforce_connectivity(lab.ctypes.data, out.ctypes.data, *lab.shape, int(min_size),
-                                                   int(max_size), queue.ctypes.data, ctypes.byref(n)),
-           "gts_gg_enforce_connectivity")
+    check(_lib.load().gts_gg_enforce_connectivity(lab.ctypes.data, out.ctypes.data, *lab.shape, int(min_size),
+                                                  int(max_size), queue.ctypes.data, ctypes.byref(n)),
+          "gts_gg_enforce_connectivity")
     return out, n.value
 
 
@@ -226,10 +220,10 @@ def supervoxel_statistics(partition, intensities, voxel_labels, n_sv):
     feats = torch.empty((n_sv, 5 * c), dtype=torch.float64, device=dev)
     cents = torch.empty((n_sv, 3), dtype=torch.float64, device=dev)
     svl = torch.empty(n_sv, dtype=torch.int32, device=dev)
-    scratch = torch.empty(int(lib.gts_gg_sv_stats_workspace(d * h * w, n_sv)), dtype=torch.uint8, device=dev)
-    _check(lib.gts_gg_sv_stats(part.data_ptr(), img.data_ptr(), None if lab is None else lab.data_ptr(), d, h, w, c,
-                               n_sv, feats.data_ptr(), cents.data_ptr(), svl.data_ptr(), scratch.data_ptr(),
-                               _stream()), "gts_gg_sv_stats")
+    ws = scratch(lib.gts_gg_sv_stats_workspace(d * h * w, n_sv), dev, torch.uint8)
+    check(lib.gts_gg_sv_stats(part.data_ptr(), img.data_ptr(), None if lab is None else lab.data_ptr(), d, h, w, c,
+                              n_sv, feats.data_ptr(), cents.data_ptr(), svl.data_ptr(), ws.data_ptr(),
+                              current_stream()), "gts_gg_sv_stats")
     return _out(feats, as_numpy), _out(cents, as_numpy), _out(svl, as_numpy)
 
 
@@ -251,10 +245,10 @@ def discard_empty_svs(partition, feats, centroids, sv_labels):
     nl = torch.empty_like(svl)
     new_part = torch.empty(part.shape, dtype=torch.int16, device=dev)
     n_nodes = torch.zeros(1, dtype=torch.int32, device=dev)
-    _check(_lib.load().gts_gg_discard_f64(f.data_ptr(), cen.data_ptr(), svl.data_ptr(), n_sv, n_feat, part.data_ptr(),
-                                          part.numel(), remap.data_ptr(), keep.data_ptr(), nf.data_ptr(), nc.data_ptr(),
-                                          nl.data_ptr(), new_part.data_ptr(), n_nodes.data_ptr(), _stream()),
-           "gts_gg_discard_f64")
+    check(_lib.load().gts_gg_discard_f64(f.data_ptr(), cen.data_ptr(), svl.data_ptr(), n_sv, n_feat, part.data_ptr(),
+                                         part.numel(), remap.data_ptr(), keep.data_ptr(), nf.data_ptr(), nc.data_ptr(),
+                                         nl.data_ptr(), new_part.data_ptr(), n_nodes.data_ptr(), current_stream()),
+          "gts_gg_discard_f64")
     n = int(n_nodes.item())
     return _out(new_part, as_numpy), _out(nf[:n], as_numpy), _out(nc[:n], as_numpy), _out(nl[:n], as_numpy)
 
@@ -269,8 +263,8 @@ def knn_candidates(positions, k):
         raise ValueError(f"kNN needs 0 < n <= {MAX_SV} and 0 < k <= {MAX_K}")
     pos = _tensor(positions, torch.float64)
     cand = torch.empty((n, k), dtype=torch.int32, device=pos.device)
-    _check(_lib.load().gts_gg_knn_candidates_f64(pos.data_ptr(), n, k, cand.data_ptr(), _stream()),
-           "gts_gg_knn_candidates_f64")
+    check(_lib.load().gts_gg_knn_candidates_f64(pos.data_ptr(), n, k, cand.data_ptr(), current_stream()),
+          "gts_gg_knn_candidates_f64")
     return _out(cand, as_numpy)
 
 
@@ -282,9 +276,9 @@ def knn_greedy(cand, k):
     picks = np.empty_like(c)
     got = np.empty(n, dtype=np.int32)
     n_edges = ctypes.c_int64()
-    _check(_lib.load().gts_gg_knn_greedy(c.ctypes.data, n, int(k), picks.ctypes.data, got.ctypes.data,
-                                         ctypes.byref(n_edges)),
-           "gts_gg_knn_greedy")
+    check(_lib.load().gts_gg_knn_greedy(c.ctypes.data, n, int(k), picks.ctypes.data, got.ctypes.data,
+                                        ctypes.byref(n_edges)),
+          "gts_gg_knn_greedy")
     return picks
 
 
@@ -308,14 +302,14 @@ def touching_edges(partition, n_nodes):
         raise ValueError("face adjacency needs a 3-D partition")
     dev = part.device
     lib = _lib.load()
-    scratch = torch.empty(int(lib.gts_gg_touching_workspace(n_nodes)), dtype=torch.uint8, device=dev)
+    ws = scratch(lib.gts_gg_touching_workspace(n_nodes), dev, torch.uint8)
     indptr = torch.empty(n_nodes + 1, dtype=torch.int32, device=dev)
-    _check(lib.gts_gg_touching_count_i16(part.data_ptr(), *part.shape, n_nodes, scratch.data_ptr(), indptr.data_ptr(),
-                                         _stream()), "gts_gg_touching_count_i16")
+    check(lib.gts_gg_touching_count_i16(part.data_ptr(), *part.shape, n_nodes, ws.data_ptr(), indptr.data_ptr(),
+                                        current_stream()), "gts_gg_touching_count_i16")
     n_e = int(indptr[n_nodes].item())
     cols = torch.empty(max(n_e, 1), dtype=torch.int32, device=dev)
-    _check(lib.gts_gg_touching_emit(scratch.data_ptr(), n_nodes, indptr.data_ptr(), cols.data_ptr(), _stream()),
-           "gts_gg_touching_emit")
+    check(lib.gts_gg_touching_emit(ws.data_ptr(), n_nodes, indptr.data_ptr(), cols.data_ptr(), current_stream()),
+          "gts_gg_touching_emit")
     ip = indptr.cpu().numpy().astype(np.int64)
     rows = np.repeat(np.arange(n_nodes, dtype=np.int64), np.diff(ip))
     return rows, cols[:n_e].cpu().numpy().astype(np.int64)

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._operands import scratch
 
 CHANNELS = 4
 QUANTILE = 0.995
@@ -110,7 +111,7 @@ def order_stats(src, shape, lists, sizes, ranks):
     X, Y, Z = shape
     lib = _lib.load()
     dev = src.device
-    ws = torch.empty(int(lib.gts_intake_select_workspace()), dtype=torch.uint8, device=dev)
+    ws = scratch(lib.gts_intake_select_workspace(), dev, torch.uint8)
     out = torch.empty((CHANNELS, 2), dtype=torch.float32, device=dev)
     xs, ys, zs = lists
     _lib.check(lib.gts_intake_order_stats(src.data_ptr(), DTYPE_CODES[_np_dtype(src)], X, Y, Z, xs.data_ptr(),

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import require_device
+from ._operands import f32
 from .conv3d import conv3d_bwd_data, conv3d_bwd_weight, conv3d_fwd
 
 
@@ -67,9 +68,7 @@ def joint_refinement_logits(node_logits, img, svs, box, bg_row, net, lists=None,
     params = (c1.weight, c1.bias, c2.weight, c2.bias)
     if node_logits.dim() != 2 or img.dim() != 4:
         raise _lib.GtsError("joint_refinement_logits takes node logits [N, C] and an image [X, Y, Z, C]")
-    for t in (node_logits, img, bg_row, *params):
-        if t.dtype != torch.float32:
-            raise _lib.GtsError(f"gts kernels are fp32: got {t.dtype}")
+    f32(node_logits, img, bg_row, *params)
     img, svs, bg_row = img.contiguous(), svs.contiguous(), bg_row.contiguous()
     require_device(node_logits.detach().contiguous(), img, svs, bg_row, *[p.detach() for p in params])
     if img.shape[3] + node_logits.shape[1] != c1.in_channels or c2.in_channels != c1.out_channels:

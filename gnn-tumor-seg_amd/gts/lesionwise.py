@@ -39,10 +39,6 @@ def _dilation(dilation, what):
     return int(dilation)
 
 
-def _workspace(lib, labels, what):
-    return _volume.workspace(lib.gts_lesionwise_workspace, *labels.shape, labels.device, what)
-
-
 def _dilate(lib, labels, region, dilation, workspace, size):
     x, y, z = labels.shape
     out = torch.empty_like(labels)
@@ -58,7 +54,7 @@ def dilate_region(labels, region, dilation=3):
     labels = _volume.label_volume(labels, "dilate_region", three_d=True)
     region, dilation = _region_index(region), _dilation(dilation, "dilate_region")
     lib = _lib.load()
-    workspace, size = _workspace(lib, labels, "dilate_region")
+    workspace, size = _volume.workspace(lib.gts_lesionwise_workspace, *labels.shape, labels.device, "dilate_region")
     return _dilate(lib, labels, region, dilation, workspace, size)
 
 
@@ -74,7 +70,7 @@ class _RegionState:
         what = "lesion_tables"
         self.lib, self.truth, self.region, self.shape = lib, truth, region, tuple(truth.shape)
         x, y, z = self.shape
-        workspace, size = _workspace(lib, truth, what)
+        workspace, size = _volume.workspace(lib.gts_lesionwise_workspace, x, y, z, truth.device, what)
         mask_p, mask_d = (_dilate(lib, v, region, n, workspace, size) for v, n in ((pred, 0), (truth, dilation)))
         self.roots_p = components.roots_unchecked(mask_p, self.shape, 26, what)
         self.roots_d = components.roots_unchecked(mask_d, self.shape, 26, what)

@@ -17,6 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import dense, ops
+from .graph import _DeviceSchedule
 
 
 class GraphError(RuntimeError):
@@ -370,11 +371,9 @@ class _SagePoolStackCall(torch.autograd.Function):
             raise _lib.GtsError("gts_sage_pool_stack_fwd_arena rejected the stack's shape")
         arena = torch.empty(max(int(total), 16), dtype=torch.uint8, device=x.device)
         ds = ops._cluster_schedule(g, "in", n, 256, ab if need_bwd else 0) if 256 in widths[:-1] else None
-        h = ds.host if ds is not None else None
         check(lib.gts_sage_pool_stack_fwd_f32(
-            ptr(d.indptr), ptr(d.indices), ptr(ds.packed) if ds else None, h.n_clusters if h else 0,
-            h.limits[0] if h else 0, h.limits[1] if h else 0, h.loc_words if h else 0, ptr(x), table, n, c_widths,
-            n_layers, 1 if need_bwd else 0, ab, relu_bits, arena.data_ptr(), int(total), current_stream()),
+            ptr(d.indptr), ptr(d.indices), *_DeviceSchedule.launch_args(ds), ptr(x), table, n, c_widths, n_layers,
+            1 if need_bwd else 0, ab, relu_bits, arena.data_ptr(), int(total), current_stream()),
             "gts_sage_pool_stack_fwd_f32")
         at = int(offsets[4 * (n_layers - 1) + 2])
         out = arena[at:at + 4 * n * widths[-1]].view(torch.float32).view(n, widths[-1])
@@ -419,10 +418,8 @@ class _SagePoolStackCall(torch.autograd.Function):
         scratch = torch.empty(max(int(need), 16), dtype=torch.uint8, device=x.device)
         gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
         ds = ops._cluster_schedule(g, "out", n, 256, ab) if 256 in widths[:-1] else None
-        h = ds.host if ds is not None else None
         check(lib.gts_sage_pool_stack_bwd_f32(
-            ptr(d.t_indptr), ptr(d.t_indices), ptr(d.t_slot), ptr(ds.packed) if ds else None, h.n_clusters if h else 0,
-            h.limits[0] if h else 0, h.limits[1] if h else 0, h.loc_words if h else 0, ptr(gout), ptr(x), table, n,
+            ptr(d.t_indptr), ptr(d.t_indices), ptr(d.t_slot), *_DeviceSchedule.launch_args(ds), ptr(gout), ptr(x), table, n,
             c_widths, n_layers, ab, relu_bits, arena.data_ptr(), grads, ptr(gx), scratch.data_ptr(), int(need),
             current_stream()), "gts_sage_pool_stack_bwd_f32")
         if sink is not None:

@@ -9,6 +9,8 @@ import torch
 
 from . import _lib
 from ._lib import check, current_stream, ptr, require_device
+from ._operands import StreamBuffers, expect, f32, scratch
+from .graph import _DeviceSchedule
 
 _ARG_DTYPE = {0: torch.uint8, 1: torch.uint8, 4: torch.int32}
 
@@ -28,30 +30,14 @@ def _timed(name, launch):
     return timer(launch) if timer is not None else launch()
 
 
-def _expect(tensor, shape, name):
-    """Operand shapes are checked on the host: the kernels index by the sizes they are given."""
-    if tensor is not None and tuple(tensor.shape) != tuple(shape):
-        raise _lib.GtsError(f"{name}: expected shape {tuple(shape)}, got {tuple(tensor.shape)}")
-
-
-def _f32(*tensors):
-    for t in tensors:
-        if t is not None and t.dtype != torch.float32:
-            raise _lib.GtsError(f"gts kernels are fp32: got {t.dtype}")
-
-
-_cluster_counters = {}
+_counters = StreamBuffers(torch.int32, zeroed=True)
+_COUNTER_BYTES = 4 * _lib.const("GTS_CLUSTER_COUNTER_WORDS")
 
 
 def cluster_counters(device):
     """The unit counters of the clustered K1 / K2 kernels (include/gts_hip.h: GTS_CLUSTER_COUNTER_WORDS zero words that every launch
     leaves zero): one buffer per (device, stream), zeroed once."""
-    key = (device, current_stream())
-    buf = _cluster_counters.get(key)
-    if buf is None:
-        buf = torch.zeros(256, dtype=torch.int32, device=device)
-        _cluster_counters[key] = buf
-    return buf
+    return _counters.get(device, _COUNTER_BYTES)
 
 
 # ---------------------------------------------------------------- raw kernel calls
@@ -60,7 +46,7 @@ def spmm_max_fwd(g, x, want_arg=True, relu_input=False):
     maxima that are not positive get no winner, so spmm_max_bwd on this arg yields the gradient
     w.r.t. the pre-activation directly (no relu_src needed)."""
     x = x.contiguous()
-    _f32(x)
+    f32(x)
     require_device(x)
     d = g.dev()
     if x.dim() != 2 or x.shape[0] != g.n:
@@ -72,12 +58,10 @@ def spmm_max_fwd(g, x, want_arg=True, relu_input=False):
     lib = _lib.load()
     ds = _cluster_schedule(g, "in", n, f, ab)
     if ds is not None:      # LDS-staged neighbour tiles over the graph's cluster row schedule: same result, bit for bit
-        h = ds.host
-
         def launch():
-            return lib.gts_spmm_max_fwd_cluster_f32(ptr(ds.packed), h.n_clusters, h.limits[0], h.limits[1], h.loc_words,
-                                                    ptr(x), ptr(out), ptr(arg), ab, 1 if relu_input else 0, n, f,
-                                                    ptr(cluster_counters(x.device)), current_stream())
+            return lib.gts_spmm_max_fwd_cluster_f32(*_DeviceSchedule.launch_args(ds), ptr(x), ptr(out), ptr(arg), ab,
+                                                    1 if relu_input else 0, n, f, ptr(cluster_counters(x.device)),
+                                                    current_stream())
     else:
         def launch():
             return lib.gts_spmm_max_fwd_f32(ptr(d.indptr), ptr(d.indices), ptr(x), ptr(out), ptr(arg),
@@ -103,26 +87,23 @@ def _cluster_schedule(g, which, n, f, arg_bytes):
 def spmm_max_bwd(g, gout, arg, relu_src=None):
     """K2.  gout [N,F], arg from spmm_max_fwd -> gx [N,F]; optional fused ReLU mask."""
     gout = gout.contiguous()
-    _f32(gout, relu_src)
+    f32(gout, relu_src)
     require_device(gout, arg, relu_src)
     d = g.dev()
     if gout.dim() != 2 or gout.shape[0] != g.n:
         raise _lib.GtsError(f"gradient must be [graph nodes = {g.n}, F], got {tuple(gout.shape)}")
     n, f = g.n, gout.shape[1]
-    _expect(arg, (n, f), "arg")
-    _expect(relu_src, (n, f), "relu_src")
+    expect(arg, (n, f), "arg")
+    expect(relu_src, (n, f), "relu_src")
     if arg.dtype != _ARG_DTYPE[g.arg_bytes]:
         raise _lib.GtsError(f"arg dtype {arg.dtype} does not belong to this graph ({_ARG_DTYPE[g.arg_bytes]})")
     gx = torch.empty((n, f), dtype=torch.float32, device=gout.device)
     lib = _lib.load()
     ds = _cluster_schedule(g, "out", n, f, arg.element_size()) if relu_src is None else None
     if ds is not None:
-        h = ds.host
-
         def launch():
-            return lib.gts_spmm_max_bwd_cluster_f32(ptr(ds.packed), h.n_clusters, h.limits[0], h.limits[1], h.loc_words,
-                                                    ptr(gout), ptr(arg), 1, ptr(gx), n, f, ptr(cluster_counters(gout.device)),
-                                                    current_stream())
+            return lib.gts_spmm_max_bwd_cluster_f32(*_DeviceSchedule.launch_args(ds), ptr(gout), ptr(arg), 1, ptr(gx), n, f,
+                                                    ptr(cluster_counters(gout.device)), current_stream())
     else:
         def launch():
             return lib.gts_spmm_max_bwd_f32(ptr(d.t_indptr), ptr(d.t_indices), ptr(d.t_slot), ptr(gout),
@@ -137,7 +118,7 @@ def spmm_sum_raw(g, x, transposed=False, div_in=None, div_out=None, add_self=Fal
     """K3/K4.  Generic sum reducer over the in-CSR (or the out-CSR when transposed); `accum` [N,F] is added
     to the result (a gradient that reached the rows by another path)."""
     x = x.contiguous()
-    _f32(x, div_in, div_out, accum)
+    f32(x, div_in, div_out, accum)
     require_device(x, div_in, div_out, accum)
     d = g.dev()
     indptr, indices = (d.t_indptr, d.t_indices) if transposed else (d.indptr, d.indices)
@@ -145,9 +126,9 @@ def spmm_sum_raw(g, x, transposed=False, div_in=None, div_out=None, add_self=Fal
     if x.dim() != 2 or x.shape[0] != n:
         raise _lib.GtsError(f"features must be [graph nodes = {n}, F], got {tuple(x.shape)}")
     f = x.shape[1]
-    _expect(div_in, (n,), "div_in")
-    _expect(div_out, (n,), "div_out")
-    _expect(accum, (n, f), "accum")
+    expect(div_in, (n,), "div_in")
+    expect(div_out, (n,), "div_out")
+    expect(accum, (n, f), "accum")
     out = torch.empty_like(x)
     check(_lib.load().gts_spmm_sum_f32(ptr(indptr), ptr(indices), ptr(x), ptr(out), ptr(div_in), ptr(div_out),
                                        ptr(accum), 1 if add_self else 0, n, f, current_stream()), "gts_spmm_sum_f32")
@@ -212,14 +193,14 @@ def _gat_fwd(g, ft, el, er, slope, bias=None, residual=None, activation=0):
     if ft.dim() != 3 or ft.shape[0] != g.n:
         raise _lib.GtsError(f"ft must be [graph nodes = {g.n}, H, D], got {tuple(ft.shape)}")
     n, h, dim = ft.shape
-    _expect(el, (n, h), "el")
-    _expect(er, (n, h), "er")
-    _expect(bias, (h * dim,), "bias")
+    expect(el, (n, h), "el")
+    expect(er, (n, h), "er")
+    expect(bias, (h * dim,), "bias")
     if residual is not None and (residual.shape[0] != n or residual.numel() != n * h * dim):
         raise _lib.GtsError(f"residual must hold [{n}, {h}*{dim}] values, got {tuple(residual.shape)}")
     if activation not in (0, 1):
         raise _lib.GtsError(f"_gat_fwd: activation must be 0 (none) or 1 (ELU), got {activation!r}")
-    _f32(ft, el, er, bias, residual)
+    f32(ft, el, er, bias, residual)
     ft, el, er = ft.contiguous(), el.contiguous(), er.contiguous()
     bias = bias.contiguous() if bias is not None else None
     residual = residual.contiguous() if residual is not None else None
@@ -234,9 +215,9 @@ def _gat_fwd(g, ft, el, er, slope, bias=None, residual=None, activation=0):
         nbytes = lib.gts_gat_cluster_workspace(hs.n_clusters, hs.limits[0], hs.loc_words, h, 0)
         ws = _gat_ws(ft.device, nbytes)
         launch = lambda: lib.gts_gat_fwd_cluster_f32(      # noqa: E731
-            ptr(d.indptr), ptr(d.indices), ptr(ds.packed), hs.n_clusters, hs.limits[0], hs.limits[1], hs.loc_words,
-            1 if hs.tagged else 0, ptr(ft), ptr(el), ptr(er), float(slope), ptr(bias), activation, ptr(out), ptr(attn),
-            ptr(ws), nbytes, n, h, dim, g.max_in_degree, current_stream())
+            ptr(d.indptr), ptr(d.indices), *_DeviceSchedule.launch_args(ds, with_tag=True), ptr(ft), ptr(el), ptr(er),
+            float(slope), ptr(bias), activation, ptr(out), ptr(attn), ptr(ws), nbytes, n, h, dim, g.max_in_degree,
+            current_stream())
     else:
         launch = lambda: lib.gts_gat_fwd_f32(      # noqa: E731
             ptr(d.indptr), ptr(d.indices), ptr(ft), ptr(el), ptr(er), float(slope), ptr(bias), ptr(residual),
@@ -245,17 +226,9 @@ def _gat_fwd(g, ft, el, er, slope, bias=None, residual=None, activation=0):
     return out, attn
 
 
-_gat_workspaces = {}
-
-
-def _gat_ws(device, nbytes):
-    """Scratch of the clustered GAT kernels (their weight blocks), grown on demand and reused: one per (device, stream)."""
-    key = (device, current_stream())
-    buf = _gat_workspaces.get(key)
-    if buf is None or buf.numel() * 4 < nbytes:
-        buf = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
-        _gat_workspaces[key] = buf
-    return buf
+# _gat_ws(device, nbytes): scratch of the clustered GAT kernels (their weight blocks), grown on demand and reused: one per
+# (device, stream); _gat_ws(device, 0) is the buffer the last launch used
+_gat_ws = StreamBuffers().get
 
 
 def _gat_cluster_schedule(g, which, n, heads, dim):
@@ -276,15 +249,15 @@ def _gat_bwd(g, ft, el, er, attn, gout, slope, attn_l=None, attn_r=None):
     if ft.dim() != 3 or ft.shape[0] != g.n:
         raise _lib.GtsError(f"ft must be [graph nodes = {g.n}, H, D], got {tuple(ft.shape)}")
     n, h, dim = ft.shape
-    _expect(el, (n, h), "el")
-    _expect(er, (n, h), "er")
-    _expect(attn, (g.number_of_edges(), h), "attn")
-    _expect(gout, (n, h, dim), "gout")
-    _expect(attn_l, (h, dim), "attn_l")
-    _expect(attn_r, (h, dim), "attn_r")
+    expect(el, (n, h), "el")
+    expect(er, (n, h), "er")
+    expect(attn, (g.number_of_edges(), h), "attn")
+    expect(gout, (n, h, dim), "gout")
+    expect(attn_l, (h, dim), "attn_l")
+    expect(attn_r, (h, dim), "attn_r")
     if (attn_l is None) != (attn_r is None):
         raise _lib.GtsError("_gat_bwd: attn_l and attn_r come together or not at all")
-    _f32(ft, el, er, attn, gout, attn_l, attn_r)
+    f32(ft, el, er, attn, gout, attn_l, attn_r)
     ft, el, er, attn, gout = ft.contiguous(), el.contiguous(), er.contiguous(), attn.contiguous(), gout.contiguous()
     attn_l = attn_l.contiguous() if attn_l is not None else None
     attn_r = attn_r.contiguous() if attn_r is not None else None
@@ -300,9 +273,9 @@ def _gat_bwd(g, ft, el, er, attn, gout, slope, attn_l=None, attn_r=None):
         nbytes = 2 * lib.gts_gat_cluster_workspace(hs.n_clusters, hs.limits[0], hs.loc_words, h, 0)
         ws_e = _gat_ws(ft.device, nbytes)
         edge = lambda: lib.gts_gat_bwd_edge_cluster_f32(      # noqa: E731
-            ptr(d.indptr), ptr(d.indices), ptr(es.packed), hs.n_clusters, hs.limits[0], hs.limits[1], hs.loc_words,
-            1 if hs.tagged else 0, ptr(ft), ptr(el), ptr(er), ptr(attn), ptr(gout), float(slope), ptr(ge), ptr(ger),
-            ptr(ws_e), nbytes, n, h, dim, g.max_in_degree, current_stream())
+            ptr(d.indptr), ptr(d.indices), *_DeviceSchedule.launch_args(es, with_tag=True), ptr(ft), ptr(el), ptr(er),
+            ptr(attn), ptr(gout), float(slope), ptr(ge), ptr(ger), ptr(ws_e), nbytes, n, h, dim, g.max_in_degree,
+            current_stream())
     else:
         edge = lambda: lib.gts_gat_bwd_edge_f32(ptr(d.indptr), ptr(d.indices), ptr(ft), ptr(el), ptr(er), ptr(attn),   # noqa: E731
                                                 ptr(gout), float(slope), ptr(ge), ptr(ger), n, h, dim, current_stream())
@@ -316,9 +289,9 @@ def _gat_bwd(g, ft, el, er, attn, gout, slope, attn_l=None, attn_r=None):
         ws = _gat_ws(ft.device, nbytes)
         attn_lr = torch.stack([attn_l.reshape(-1), attn_r.reshape(-1)]) if attn_l is not None else None
         src = lambda: lib.gts_gat_bwd_src_cluster_f32(      # noqa: E731
-            ptr(d.t_indptr), ptr(d.t_pos), ptr(ds.packed), hs.n_clusters, hs.limits[0], hs.limits[1], hs.loc_words,
-            1 if hs.tagged else 0, ptr(attn), ptr(ge), ptr(gout), ptr(attn_lr), ptr(ger) if attn_l is not None else None,
-            ptr(gft), ptr(gel), ptr(ws), nbytes, n, h, dim, g.max_out_degree, current_stream())
+            ptr(d.t_indptr), ptr(d.t_pos), *_DeviceSchedule.launch_args(ds, with_tag=True), ptr(attn), ptr(ge), ptr(gout),
+            ptr(attn_lr), ptr(ger) if attn_l is not None else None, ptr(gft), ptr(gel), ptr(ws), nbytes, n, h, dim,
+            g.max_out_degree, current_stream())
     else:
         src = lambda: lib.gts_gat_bwd_src_f32(ptr(d.t_indptr), ptr(d.t_indices), ptr(d.t_pos), ptr(attn), ptr(ge),     # noqa: E731
                                               ptr(gout), ptr(attn_l), ptr(attn_r),
@@ -334,7 +307,7 @@ class _GATAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, g, ft, el, er, negative_slope):
         ft, el, er = ft.contiguous(), el.contiguous(), er.contiguous()
-        _f32(ft, el, er)
+        f32(ft, el, er)
         require_device(ft, el, er)
         out, attn = _gat_fwd(g, ft, el, er, negative_slope)
         ctx.g, ctx.slope = g, float(negative_slope)
@@ -355,14 +328,14 @@ def gat_aggregate(g, ft, el, er, negative_slope):
 def gat_scores(ft, attn_l, attn_r):
     """(el, er) [N,H]: <ft[n,h,:], attn_l[h,:]>, <ft[n,h,:], attn_r[h,:]> in one pass over ft."""
     ft, attn_l, attn_r = ft.contiguous(), attn_l.contiguous(), attn_r.contiguous()
-    _f32(ft, attn_l, attn_r)
+    f32(ft, attn_l, attn_r)
     require_device(ft, attn_l, attn_r)
     if ft.dim() != 3:
         raise _lib.GtsError(f"ft must be [N, H, D], got {tuple(ft.shape)}")
     n, h, dim = ft.shape
     attn_l, attn_r = attn_l.reshape(-1, dim), attn_r.reshape(-1, dim)
-    _expect(attn_l, (h, dim), "attn_l")
-    _expect(attn_r, (h, dim), "attn_r")
+    expect(attn_l, (h, dim), "attn_l")
+    expect(attn_r, (h, dim), "attn_r")
     el = torch.empty((n, h), dtype=torch.float32, device=ft.device)
     er = torch.empty_like(el)
     check(_lib.load().gts_gat_scores_f32(ptr(ft), ptr(attn_l), ptr(attn_r), ptr(el), ptr(er), n, h, dim,
@@ -376,7 +349,7 @@ def gat_fc_scores(h, w_fc, attn_l, attn_r, heads, dim, packed=None):
     packed: dense.pack_weights copy of w_fc (fragment order; read by the panel kernels, same values)."""
     h, w_fc = h.contiguous(), w_fc.contiguous()
     attn_l, attn_r = attn_l.reshape(heads, dim).contiguous(), attn_r.reshape(heads, dim).contiguous()
-    _f32(h, w_fc, attn_l, attn_r)
+    f32(h, w_fc, attn_l, attn_r)
     require_device(h, w_fc, attn_l, attn_r)
     n, k = h.shape
     if w_fc.dim() != 2 or w_fc.shape[1] != k:
@@ -390,7 +363,7 @@ def gat_fc_scores(h, w_fc, attn_l, attn_r, heads, dim, packed=None):
     el = torch.empty((n, heads), dtype=torch.float32, device=h.device)
     er = torch.empty_like(el)
     nbytes = lib.gts_gat_fc_scores_workspace(n, heads, dim)
-    ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=h.device)
+    ws = scratch(nbytes, h.device)
     from . import dense
     if packed is not None:
         dense._packed_array((packed,), (w_fc,))      # size check only
@@ -398,11 +371,6 @@ def gat_fc_scores(h, w_fc, attn_l, attn_r, heads, dim, packed=None):
         ptr(h), ptr(w_fc), ptr(attn_l), ptr(attn_r), ptr(ft), ptr(el), ptr(er), ptr(ws), ws.numel() * 4, n, heads, dim, k,
         ptr(packed), current_stream()), "gts_gat_fc_scores_f32"))
     return ft, el, er
-
-
-def _reduce_ws(n, cols, device):
-    nbytes = _lib.load().gts_gat_reduce_workspace(n, cols)
-    return torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=device)
 
 
 def gat_act_bwd(gout, out, activation, want_bias_grad):
@@ -420,15 +388,16 @@ def gat_act_bwd(gout, out, activation, want_bias_grad):
     n, cols = gout.shape[0], gout[0].numel()
     if cols == 0 or cols % 4:
         raise _lib.GtsError(f"gat_act_bwd needs a row width that is a multiple of 4, got {cols}")
-    _expect(out, gout.shape, "out")
-    _f32(gout, out)
+    expect(out, gout.shape, "out")
+    f32(gout, out)
     gout = gout.contiguous()
     out = out.contiguous() if out is not None else None
     require_device(gout, out)
     g_pre = torch.empty_like(gout) if activation else gout
     g_bias = torch.empty(cols, dtype=torch.float32, device=gout.device) if want_bias_grad else None
-    ws = _reduce_ws(n, cols, gout.device) if want_bias_grad else None
-    check(_lib.load().gts_gat_act_bwd_f32(ptr(gout), ptr(out), activation, ptr(g_pre) if activation else None,
+    lib = _lib.load()
+    ws = scratch(lib.gts_gat_reduce_workspace(n, cols), gout.device) if want_bias_grad else None
+    check(lib.gts_gat_act_bwd_f32(ptr(gout), ptr(out), activation, ptr(g_pre) if activation else None,
                                           ptr(g_bias), ptr(ws), ws.numel() * 4 if ws is not None else 0,
                                           n, cols, current_stream()), "gts_gat_act_bwd_f32")
     return g_pre, g_bias
@@ -440,18 +409,19 @@ def gat_param_grad(ft, gel, ger):
     if ft.dim() != 3:
         raise _lib.GtsError(f"ft must be [N, H, D], got {tuple(ft.shape)}")
     n, h, dim = ft.shape
-    _expect(gel, (n, h), "gel")
-    _expect(ger, (n, h), "ger")
+    expect(gel, (n, h), "gel")
+    expect(ger, (n, h), "ger")
     if n == 0 or h == 0 or dim == 0 or dim % 4:
         raise _lib.GtsError(f"gat_param_grad needs N > 0, H > 0 and a head width that is a multiple of 4, "
                             f"got {tuple(ft.shape)}")
-    _f32(ft, gel, ger)
+    f32(ft, gel, ger)
     ft, gel, ger = ft.contiguous(), gel.contiguous(), ger.contiguous()
     require_device(ft, gel, ger)
     gl = torch.empty((h, dim), dtype=torch.float32, device=ft.device)
     gr = torch.empty_like(gl)
-    ws = _reduce_ws(n, h * dim, ft.device)
-    check(_lib.load().gts_gat_param_grad_f32(ptr(ft), ptr(gel), ptr(ger), ptr(gl), ptr(gr), ptr(ws),
+    lib = _lib.load()
+    ws = scratch(lib.gts_gat_reduce_workspace(n, h * dim), ft.device)
+    check(lib.gts_gat_param_grad_f32(ptr(ft), ptr(gel), ptr(ger), ptr(gl), ptr(gr), ptr(ws),
                                              ws.numel() * 4, n, h, dim, current_stream()),
           "gts_gat_param_grad_f32")
     return gl, gr
@@ -480,15 +450,19 @@ def project_rows(svs, table, bg_row):
     return out
 
 
+def _check_relabel(relabel, n_classes):
+    if relabel is not None and (relabel.dtype != torch.int16 or relabel.numel() < n_classes):
+        raise _lib.GtsError("relabel must be int16 with one entry per class")
+
+
 def project_argmax(svs, logits, relabel=None):
     """K12 fused: argmax over classes of the voxel's node, 0 for background; int16 out."""
-    _f32(logits)
+    f32(logits)
     if svs.dtype != torch.int16:
         raise _lib.GtsError("supervoxel partitioning must be int16")
     svs, logits = svs.contiguous(), logits.contiguous()
     require_device(svs, logits, relabel)
-    if relabel is not None and (relabel.dtype != torch.int16 or relabel.numel() < logits.shape[1]):
-        raise _lib.GtsError("relabel must be int16 with one entry per class")
+    _check_relabel(relabel, logits.shape[1])
     out = torch.empty(svs.shape, dtype=torch.int16, device=svs.device)
     if svs.numel() == 0:
         return out
@@ -501,7 +475,7 @@ def project_argmax(svs, logits, relabel=None):
 def project_argmax_occupancy(svs, logits):
     """K12 arg-max projection of a 3-D partitioning plus the tumour-plane flags of the result:
     (int16 labels [X,Y,Z], (any over (y,z) [X], any over (x,z) [Y], any over (x,y) [Z]) as uint8)."""
-    _f32(logits)
+    f32(logits)
     if svs.dtype != torch.int16 or svs.dim() != 3:
         raise _lib.GtsError("supervoxel partitioning must be a 3-D int16 volume")
     svs, logits = svs.contiguous(), logits.contiguous()
@@ -599,9 +573,9 @@ class SupervoxelLists:
 
 
 def _crop_operands(img, svs, table, bg_row, box, what):
-    """The operand checks of crop_concat (K16 keeps its own copy: it is left as it was), for J1; returns
-    (img, svs, table, bg_row, ci, ct), contiguous."""
-    _f32(img, table, bg_row)
+    """The operand checks of crop_concat (K16) and crop_concat_rows (J1); returns (img, svs, table, bg_row, ci, ct),
+    contiguous."""
+    f32(img, table, bg_row)
     if svs.dtype != torch.int16 or tuple(svs.shape) != box.volume_shape:
         raise _lib.GtsError("partitioning must be int16 with the crop box's volume shape")
     ci = 0
@@ -611,11 +585,11 @@ def _crop_operands(img, svs, table, bg_row, box, what):
         img, ci = img.contiguous(), img.shape[3]
     if table.dim() != 2:
         raise _lib.GtsError(f"{what}: table must be [N, C], got {tuple(table.shape)}")
-    svs, table, bg_row = svs.contiguous(), table.contiguous(), bg_row.contiguous()
-    require_device(svs, table, bg_row, img, *box.dev)
     ct = table.shape[1]
     if bg_row.numel() != ct:
         raise _lib.GtsError("background row does not match table rows")
+    svs, table, bg_row = svs.contiguous(), table.contiguous(), bg_row.contiguous()
+    require_device(svs, table, bg_row, img, *box.dev)
     return img, svs, table, bg_row, ci, ct
 
 
@@ -633,17 +607,27 @@ def crop_concat_rows(img, svs, table, bg_row, box):
     return out
 
 
+def _rows_over_box(t, dims, what, min_cols=0):
+    """t fp32 [V, K] or [cx, cy, cz, K] over a crop of extents dims (V = cx cy cz), K >= min_cols: its [V, K] view."""
+    f32(t)
+    cx, cy, cz = (int(d) for d in dims)
+    v = cx * cy * cz
+    if t.dim() == 4 and tuple(t.shape[:3]) == (cx, cy, cz):
+        t = t.reshape(v, t.shape[3])
+    if t.dim() != 2 or t.shape[0] != v or t.shape[1] < min_cols:
+        raise _lib.GtsError(f"{what}: expected [{v}, K] or [{cx}, {cy}, {cz}, K] over the crop box with K >= {min_cols}, "
+                            f"got {tuple(t.shape)}")
+    return t
+
+
 def crop_concat_rows_bwd(dx, lists, box, img_channels=0):
     """J2, the adjoint of crop_concat_rows with respect to `table`: d_table [N, Ct] from dx [V, Ci + Ct] (or
     [cx, cy, cz, Ci + Ct]) over the crop, Ci = img_channels (0 when dx holds the table's columns only).
     `lists`: the SupervoxelLists of the partitioning for N rows.  Deterministic (fixed-order sums)."""
-    _f32(dx)
+    if img_channels < 0:
+        raise _lib.GtsError(f"crop_concat_rows_bwd: {img_channels} image channels")
+    dx = _rows_over_box(dx, box.shape, "crop_concat_rows_bwd", img_channels + 1)
     cx, cy, cz = box.shape
-    v = cx * cy * cz
-    if dx.dim() == 4 and tuple(dx.shape[:3]) == box.shape:
-        dx = dx.reshape(v, -1)
-    if dx.dim() != 2 or dx.shape[0] != v or dx.shape[1] <= img_channels or img_channels < 0:
-        raise _lib.GtsError(f"crop_concat_rows_bwd: expected dx [{v}, > {img_channels}], got {tuple(dx.shape)}")
     if not isinstance(lists, SupervoxelLists) or lists.volume_shape != box.volume_shape:
         raise _lib.GtsError("crop_concat_rows_bwd: the voxel lists belong to another volume")
     dx = dx.contiguous()
@@ -664,19 +648,7 @@ def crop_concat(img, svs, table, bg_row, box):
     """K16.  [1, Ci + Ct, cx, cy, cz] fp32 = cat([img, table_plus_bg[svs]], -1)[box] moved to
     channels-first, without materialising the voxel-logit volume.  img [X,Y,Z,Ci] fp32 (or None),
     svs [X,Y,Z] int16, table [N,Ct] fp32, bg_row [Ct]."""
-    _f32(img, table, bg_row)
-    if svs.dtype != torch.int16 or tuple(svs.shape) != box.volume_shape:
-        raise _lib.GtsError("partitioning must be int16 with the crop box's volume shape")
-    ci = 0
-    if img is not None:
-        if img.dim() != 4 or tuple(img.shape[:3]) != box.volume_shape:
-            raise _lib.GtsError("image must be [X, Y, Z, C] over the same volume")
-        img, ci = img.contiguous(), img.shape[3]
-    svs, table, bg_row = svs.contiguous(), table.contiguous(), bg_row.contiguous()
-    require_device(svs, table, bg_row, img, *box.dev)
-    ct = table.shape[1]
-    if bg_row.numel() != ct:
-        raise _lib.GtsError("background row does not match table rows")
+    img, svs, table, bg_row, ci, ct = _crop_operands(img, svs, table, bg_row, box, "crop_concat")
     cx, cy, cz = box.shape
     out = torch.empty((1, ci + ct, cx, cy, cz), dtype=torch.float32, device=svs.device)
     if out.numel():
@@ -690,15 +662,14 @@ def crop_concat(img, svs, table, bg_row, box):
 def argmax_scatter(scores, box, relabel=None):
     """K17.  int16 [X,Y,Z] volume, zero outside the box, arg-max over channels of
     scores [C, cx, cy, cz] (or [1, C, ...]) inside."""
-    _f32(scores)
+    f32(scores)
     if scores.dim() == 5 and scores.shape[0] == 1:
         scores = scores[0]
     if scores.dim() != 4 or tuple(scores.shape[1:]) != box.shape:
         raise _lib.GtsError("scores must be [C, cx, cy, cz] over the crop box")
     scores = scores.contiguous()
     require_device(scores, relabel, *box.dev)
-    if relabel is not None and (relabel.dtype != torch.int16 or relabel.numel() < scores.shape[0]):
-        raise _lib.GtsError("relabel must be int16 with one entry per class")
+    _check_relabel(relabel, scores.shape[0])
     out = torch.zeros(box.volume_shape, dtype=torch.int16, device=scores.device)
     cx, cy, cz = box.shape
     if scores.numel():
@@ -712,16 +683,10 @@ def argmax_scatter(scores, box, relabel=None):
 def argmax_scatter_rows(scores, box, relabel=None):
     """E2.  K17 for channels-last scores: int16 [X,Y,Z] volume, zero outside the box, first-maximum arg-max over
     the columns of scores [cx * cy * cz, C] (or [cx, cy, cz, C]) inside."""
-    _f32(scores)
     cx, cy, cz = box.shape
-    if scores.dim() == 4 and tuple(scores.shape[:3]) == box.shape:
-        scores = scores.reshape(cx * cy * cz, -1)
-    if scores.dim() != 2 or scores.shape[0] != cx * cy * cz or scores.shape[1] < 1:
-        raise _lib.GtsError(f"scores must be [{cx * cy * cz}, C] over the crop box, got {tuple(scores.shape)}")
-    scores = scores.contiguous()
+    scores = _rows_over_box(scores, box.shape, "argmax_scatter_rows", 1).contiguous()
     require_device(scores, relabel, *box.dev)
-    if relabel is not None and (relabel.dtype != torch.int16 or relabel.numel() < scores.shape[1]):
-        raise _lib.GtsError("relabel must be int16 with one entry per class")
+    _check_relabel(relabel, scores.shape[1])
     out = torch.zeros(box.volume_shape, dtype=torch.int16, device=scores.device)
     if scores.numel():
         check(_lib.load().gts_argmax_scatter_rows_i16(ptr(scores), ptr(relabel), ptr(box.dev[0]), ptr(box.dev[1]),
@@ -742,14 +707,14 @@ def softmax_accumulate(logit_sets, acc=None):
     logit_sets = list(logit_sets)
     if not logit_sets:
         raise _lib.GtsError("softmax_accumulate: no logit sets")
-    _f32(acc, *logit_sets)
+    f32(acc, *logit_sets)
     first = logit_sets[0]
     if first.dim() != 2 or not 1 <= first.shape[1] <= SOFTMAX_ACCUMULATE_MAX_CLASSES:
         raise _lib.GtsError(f"softmax_accumulate: logits must be [rows, 1..{SOFTMAX_ACCUMULATE_MAX_CLASSES}], "
                             f"got {tuple(first.shape)}")
     for t in logit_sets[1:]:
-        _expect(t, first.shape, "softmax_accumulate logits")
-    _expect(acc, first.shape, "softmax_accumulate acc")
+        expect(t, first.shape, "softmax_accumulate logits")
+    expect(acc, first.shape, "softmax_accumulate acc")
     require_device(acc, *logit_sets)
     overwrite = acc is None
     if overwrite:
@@ -777,32 +742,37 @@ def label_confusion(pred, truth):
     counts = torch.zeros((5, 5), dtype=torch.int64, device=pred.device)
     if pred.numel():
         lib = _lib.load()
-        scratch = torch.empty(lib.gts_label_confusion_workspace(pred.numel()), dtype=torch.uint8,
-                              device=pred.device)
-        check(lib.gts_label_confusion_i16(ptr(pred), ptr(truth), ptr(counts), ptr(scratch), scratch.numel(),
+        ws = scratch(lib.gts_label_confusion_workspace(pred.numel()), pred.device, torch.uint8)
+        check(lib.gts_label_confusion_i16(ptr(pred), ptr(truth), ptr(counts), ptr(ws), ws.numel(),
                                           pred.numel(), current_stream()), "gts_label_confusion_i16")
     return counts
 
 
 # ---------------------------------------------------------------- class-weighted cross-entropy
+def _weighted_ce_launch(logits, labels, class_w, want_grad):
+    """The one gts_weighted_ce_f32 launch: (grad_unscaled [N, C] or None, stats = [num, den, num/den])."""
+    logits, labels = logits.contiguous(), labels.contiguous()
+    f32(logits, class_w)
+    require_device(logits, labels, class_w)
+    if logits.dim() != 2 or labels.dtype != torch.int64 or labels.shape != logits.shape[:1]:
+        raise _lib.GtsError("weighted CE takes logits [N, C] and int64 labels [N]")
+    n, c = logits.shape
+    expect(class_w, (c,), "class_w")
+    lib = _lib.load()
+    ws = scratch(lib.gts_weighted_ce_workspace(n), logits.device)
+    grad = torch.empty_like(logits) if want_grad else None
+    stats = torch.empty(3, dtype=torch.float32, device=logits.device)
+    check(lib.gts_weighted_ce_f32(ptr(logits), ptr(labels), ptr(class_w), ptr(grad), ptr(ws), ws.numel() * 4,
+                                  ptr(stats), n, c, current_stream()), "gts_weighted_ce_f32")
+    return grad, stats
+
+
 class _WeightedCE(torch.autograd.Function):
     """(logits [N,C], labels int64 [N], class_w [C] or None) -> stats = [num, den, num/den]."""
 
     @staticmethod
     def forward(ctx, logits, labels, class_w):
-        logits, labels = logits.contiguous(), labels.contiguous()
-        _f32(logits, class_w)
-        require_device(logits, labels, class_w)
-        if logits.dim() != 2 or labels.dtype != torch.int64 or labels.shape != logits.shape[:1]:
-            raise _lib.GtsError("weighted CE takes logits [N, C] and int64 labels [N]")
-        n, c = logits.shape
-        _expect(class_w, (c,), "class_w")
-        lib = _lib.load()
-        ws = torch.empty(max(1, lib.gts_weighted_ce_workspace(n) // 4), dtype=torch.float32, device=logits.device)
-        grad = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
-        stats = torch.empty(3, dtype=torch.float32, device=logits.device)
-        check(lib.gts_weighted_ce_f32(ptr(logits), ptr(labels), ptr(class_w), ptr(grad), ptr(ws), ws.numel() * 4,
-                                      ptr(stats), n, c, current_stream()), "gts_weighted_ce_f32")
+        grad, stats = _weighted_ce_launch(logits, labels, class_w, ctx.needs_input_grad[0])
         ctx.save_for_backward(grad, stats)
         ctx.mark_non_differentiable(stats)
         ctx.set_materialize_grads(False)                 # an unused output arrives as None, not as a zero tensor
@@ -835,9 +805,10 @@ def weighted_cross_entropy(logits, labels, class_w=None, reduction="mean"):
 
 
 # ---------------------------------------------------------------- soft Dice + class-weighted cross-entropy
-DICE_MAX_GROUPS = 8            # GTS_DICE_CE_MAX_GROUPS
-DICE_STATS_FLOATS = 40         # GTS_DICE_CE_STATS_FLOATS; offsets below as in include/gts_hip.h
-_DICE_LOSS, _DICE_CE, _DICE_LDICE, _DICE_DICE = 0, 1, 2, 8
+DICE_MAX_GROUPS = _lib.const("GTS_DICE_CE_MAX_GROUPS")
+DICE_STATS_FLOATS = _lib.const("GTS_DICE_CE_STATS_FLOATS")
+_DICE_LOSS, _DICE_CE, _DICE_LDICE, _DICE_DICE = (_lib.const("GTS_DICE_CE_STATS_" + part)
+                                                 for part in ("LOSS", "CE", "LDICE", "DICE"))
 
 
 def dice_region_masks(regions, n_classes):
@@ -872,16 +843,15 @@ class _DiceCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, class_w, masks, ce_weight, dice_weight, smooth):
         logits, labels = logits.contiguous(), labels.contiguous()
-        _f32(logits, class_w)
+        f32(logits, class_w)
         require_device(logits, labels, class_w)
         if logits.dim() != 2 or labels.dtype != torch.int64 or labels.shape != logits.shape[:1]:
             raise _lib.GtsError("Dice + CE takes logits [N, C] and int64 labels [N]")
         n, c = logits.shape
-        _expect(class_w, (c,), "class_w")
+        expect(class_w, (c,), "class_w")
         lib = _lib.load()
         host_masks = (ctypes.c_uint32 * len(masks))(*masks)
-        ws = torch.empty(max(1, lib.gts_dice_ce_workspace(n, len(masks)) // 4), dtype=torch.float32,
-                         device=logits.device)
+        ws = scratch(lib.gts_dice_ce_workspace(n, len(masks)), logits.device)
         stats = torch.empty(DICE_STATS_FLOATS, dtype=torch.float32, device=logits.device)
         check(lib.gts_dice_ce_fwd_f32(ptr(logits), ptr(labels), ptr(class_w), host_masks, len(masks), ce_weight,
                                       dice_weight, smooth, ptr(stats), ptr(ws), ws.numel() * 4, n, c,
@@ -931,7 +901,7 @@ def _crop_augment(x, labels, dims, image_channels, params, flip_mask, seed, step
     """One A1 launch (A3 with a matrix) on x [cx, cy, cz, C] and / or labels [V]; returns fresh tensors (None where
     the input is)."""
     cx, cy, cz = (int(d) for d in dims)
-    _f32(x, params)
+    f32(x, params)
     require_device(x, labels, params)
     channels = 0
     if x is not None:
@@ -988,12 +958,8 @@ def flip_crop(t, dims, flips):
     axes whose entry of flips (x, y, z) is true.  An involution and its own adjoint, which is how the joint step
     carries a gradient back through the mirror.  Returns a fresh tensor of t's shape; not an autograd node."""
     cx, cy, cz = (int(d) for d in dims)
-    if t.dim() == 2 and t.shape[0] == cx * cy * cz:
-        view = t.contiguous().view(cx, cy, cz, t.shape[1])
-    elif t.dim() == 4 and tuple(t.shape[:3]) == (cx, cy, cz):
-        view = t.contiguous()
-    else:
-        raise _lib.GtsError(f"flip_crop: expected [{cx * cy * cz}, K] or [{cx}, {cy}, {cz}, K], got {tuple(t.shape)}")
+    rows = _rows_over_box(t, dims, "flip_crop")
+    view = rows.contiguous().view(cx, cy, cz, rows.shape[1])
     flips = tuple(bool(f) for f in flips)
     if len(flips) != 3:
         raise _lib.GtsError("flip_crop: flips are three booleans (x, y, z)")
@@ -1009,18 +975,14 @@ def spatial_crop_bwd(t, dims, plan):
     if not plan.spatial:
         return flip_crop(t, dims, plan.flips)
     cx, cy, cz = (int(d) for d in dims)
-    if not ((t.dim() == 2 and t.shape[0] == cx * cy * cz) or (t.dim() == 4 and tuple(t.shape[:3]) == (cx, cy, cz))):
-        raise _lib.GtsError(f"spatial_crop_bwd: expected [{cx * cy * cz}, K] or [{cx}, {cy}, {cz}, K], got "
-                            f"{tuple(t.shape)}")
-    _f32(t)
-    dy = t.contiguous()
+    dy = _rows_over_box(t, dims, "spatial_crop_bwd").contiguous()
     require_device(dy)
     dx = torch.empty_like(dy)
     if dy.numel():
         check(_lib.load().gts_augment_spatial_bwd_f32(ptr(dy), _matrix_arg(plan.matrix), ptr(dx), cx, cy, cz,
-                                                      dy.shape[-1], plan.flip_mask, current_stream()),
+                                                      dy.shape[1], plan.flip_mask, current_stream()),
               "gts_augment_spatial_bwd_f32")
-    return dx
+    return dx.view(t.shape)
 
 
 def augment_features(feats, batch_num_nodes, plans):
@@ -1037,7 +999,7 @@ def augment_features(feats, batch_num_nodes, plans):
     plans = list(plans)
     if feats.dim() != 2 or len(plans) != len(sizes) or not plans:
         raise _lib.GtsError("augment_features takes features [N, F] and one plan per graph")
-    _f32(feats)
+    f32(feats)
     feats = feats.contiguous()
     require_device(feats)
     modalities = plans[0].channels
@@ -1060,20 +1022,7 @@ def weighted_ce_numerator_grad(logits, labels, class_w=None):
     """(d numerator / d logits [N, C], [num, den, num/den]) from one launch, outside autograd: what the
     data-parallel step back-propagates with `logits.backward(grad)` — no clone / fill / scale kernels around
     the loss (the normalisation by the GLOBAL denominator happens after the all-reduce)."""
-    logits_c, labels = logits.detach().contiguous(), labels.contiguous()
-    _f32(logits_c, class_w)
-    require_device(logits_c, labels, class_w)
-    if logits_c.dim() != 2 or labels.dtype != torch.int64 or labels.shape != logits_c.shape[:1]:
-        raise _lib.GtsError("weighted CE takes logits [N, C] and int64 labels [N]")
-    n, c = logits_c.shape
-    _expect(class_w, (c,), "class_w")
-    lib = _lib.load()
-    ws = torch.empty(max(1, lib.gts_weighted_ce_workspace(n) // 4), dtype=torch.float32, device=logits_c.device)
-    grad = torch.empty_like(logits_c)
-    stats = torch.empty(3, dtype=torch.float32, device=logits_c.device)
-    check(lib.gts_weighted_ce_f32(ptr(logits_c), ptr(labels), ptr(class_w), ptr(grad), ptr(ws), ws.numel() * 4,
-                                  ptr(stats), n, c, current_stream()), "gts_weighted_ce_f32")
-    return grad, stats
+    return _weighted_ce_launch(logits.detach(), labels, class_w, True)
 
 
 def weighted_cross_entropy_stats(logits, labels, class_w=None):

@@ -153,7 +153,7 @@ class ClusterSchedule:
             code = lib.gts_cluster_schedule(*map(_i32p, arrs), _i32p(tag), n, int(lim[0]), int(lim[1]), int(lim[2]),
                                             _i32p(rec), capacity, ctypes.byref(n_cl), ctypes.byref(staged),
                                             ctypes.byref(e_max))
-            if code == -2:      # GTS_ERR_SHAPE: a row's degree (or a tag) is beyond what a cluster can hold
+            if code == _lib.const("GTS_ERR_SHAPE"):      # a row's degree (or a tag) is beyond what a cluster can hold
                 return None
             _lib.check(code, "gts_cluster_schedule")
             if n_cl.value <= capacity:

@@ -9,12 +9,115 @@ from gts import _lib, build
 
 def test_library_builds_and_exports_declared_symbols(hip_lib):
     declared = _lib.declared_symbols()
-    assert len(declared) >= 10
-    assert set(declared) == set(_lib.SIGNATURES), "header and ctypes table disagree"
+    assert len(declared) >= 105
+    table = _lib.signatures()
+    assert all(name in table for name in declared), "a declared symbol has no derived signature"
     raw = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(raw, name), f"{name} declared in gts_hip.h but not exported"
     assert hip_lib.gts_abi_version() == _lib.ABI_VERSION
+
+
+_P, _I32, _I64, _U64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
+_F32, _F64 = ctypes.c_float, ctypes.c_double
+# one entry point of every kind of declaration, as the hand-written table held them before the header was parsed
+PINNED = {
+    "gts_abi_version": (_I32, []),                                                       # (void)
+    "gts_error_string": (ctypes.c_char_p, [_I32]),                                       # const char* return
+    "gts_gat_reduce_workspace": (_I64, [_I64, _I64]),                                    # int64_t return
+    "gts_gat_fwd_f32": (_I32, [_P, _P, _P, _P, _P, _F32, _P, _P, _I32, _P, _P, _I64, _I64, _I64, _P]),     # float by value
+    "gts_augment_features_f32": (_I32, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _F64, _U64, _U64, _P]),  # double, uint64_t
+    "gts_spmm_max_fwd_cluster_f32": (_I32, [_P, _I64, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _I64, _I64, _P, _P]),  # uint32_t*
+    "gts_pack_weights_f32": (_I32, [_P, _P, _P, _I32, _I64, _I64, _I32, _P]),            # const float* const*
+    "gts_collate_plan": (_I32, [_P, _I32, _I64, _P, _I32, _P]),                          # struct pointers
+}
+
+
+def test_signatures_are_derived_from_the_header():
+    table = _lib.signatures()
+    assert table is _lib.signatures(), "the header is parsed once per process"
+    for name, want in PINNED.items():
+        assert table[name] == want, name
+    for name, (restype, argtypes) in table.items():
+        assert restype in (_I32, _I64, ctypes.c_char_p), name
+        assert all(a in (_P, _I32, _I64, ctypes.c_uint32, _U64, _F32, _F64) for a in argtypes), name
+
+
+def test_header_parser_refuses_what_it_cannot_bind():
+    import pytest
+
+    sigs, consts = _lib.parse_header("""
+        /* int32_t gts_in_a_block_comment(int32_t a);  prose (with parentheses) */
+        // int32_t gts_in_a_line_comment(int32_t a);
+        #define GTS_THREE 3
+        #define GTS_MINUS (-7)   /* why */
+        #define GTS_NOT_A_NUMBER "x"
+        typedef struct { int64_t n; void* p; } gts_pair_t;
+        int32_t gts_one(const gts_pair_t* pair, uint32_t* words, const float* const* tables, double x, void* stream);
+        int64_t gts_none(void);
+        const char* gts_name(int32_t code);
+        void gts_quiet(float a,
+                       uint64_t b);
+    """)
+    assert sigs == {"gts_one": (_I32, [_P, _P, _P, _F64, _P]), "gts_none": (_I64, []),
+                    "gts_name": (ctypes.c_char_p, [_I32]), "gts_quiet": (None, [_F32, _U64])}
+    assert consts == {"GTS_THREE": 3, "GTS_MINUS": -7}
+    for bad in ("int32_t gts_bad(int16_t small);",                 # a scalar outside the six
+                "int32_t gts_bad(unsigned int n);",
+                "int32_t gts_bad(gts_pair_t by_value);",           # a struct by value
+                "gts_pair_t gts_bad(int32_t n);",
+                "int32_t gts_bad(const char* fmt, ...);",          # variadic
+                "int32_t gts_bad(int32_t box[6]);",
+                "int32_t gts_bad(int32_t (*callback)(int32_t));",  # cannot be split
+                "int32_t gts_bad(int32_t n) { return n; }"):
+        with pytest.raises(_lib.GtsError, match="gts_bad"):
+            _lib.parse_header(bad)
+
+
+def test_constants_are_read_from_the_header():
+    import pytest
+
+    from gts import dense, graphgen, ops
+
+    assert (ops.DICE_MAX_GROUPS, ops.DICE_STATS_FLOATS) == (8, 40)
+    assert (ops._DICE_LOSS, ops._DICE_CE, ops._DICE_LDICE, ops._DICE_DICE) == (0, 1, 2, 8)
+    assert _lib.COLLATE_MAX_SCHEDULES == 6
+    assert (graphgen.MAX_SV, graphgen.MAX_K, graphgen.MAX_RADIUS) == (32767, 32, 16)
+    assert _lib.const("GTS_CLUSTER_COUNTER_WORDS") == 256 and ops._COUNTER_BYTES == 4 * 256
+    assert _lib.const("GTS_OPT_GEMM_TILE") == 1 and dense._OPT_GEMM_TILE == 1
+    assert _lib.const("GTS_ERR_SHAPE") == -2
+    assert _lib.const("GTS_DICE_CE_STATS_FLOATS") == 40
+    with pytest.raises(_lib.GtsError, match="GTS_NO_SUCH"):
+        _lib.const("GTS_NO_SUCH")
+
+
+def test_crop_concat_and_crop_concat_rows_refuse_the_same_operands():
+    """K16 and J1 share their operand checks: the same GtsError for the same bad operand, on the host, before any launch."""
+    import numpy as np
+    import pytest
+    import torch
+
+    from gts import ops
+
+    shape = (3, 2, 4)
+    box = ops.CropBox([0, 2], [1], [0, 1, 3], shape, "cpu")
+    good = dict(img=torch.zeros(shape + (2,)), svs=torch.zeros(shape, dtype=torch.int16), table=torch.zeros(5, 4),
+                bg_row=torch.zeros(4))
+    bad = {"partitioning dtype": dict(svs=torch.zeros(shape, dtype=torch.int32)),
+           "image over another volume": dict(img=torch.zeros((3, 2, 5, 2))),
+           "background row width": dict(bg_row=torch.zeros(3)),
+           "1-D table": dict(table=torch.zeros(20)),
+           "3-D table": dict(table=torch.zeros(5, 2, 2))}
+    for what, change in bad.items():
+        texts = []
+        for fn in (ops.crop_concat, ops.crop_concat_rows):
+            a = dict(good, **change)
+            with pytest.raises(ops._lib.GtsError) as err:
+                fn(a["img"], a["svs"], a["table"], a["bg_row"], box)
+            texts.append(str(err.value).replace(fn.__name__, "<fn>"))
+        assert texts[0] == texts[1], what
+        assert "MI355X only" not in texts[0], f"{what}: refused for its shape or dtype, not for lying on the CPU"
+    assert np.prod(box.shape) == 6
 
 
 def test_library_is_gfx950_code(hip_lib):
