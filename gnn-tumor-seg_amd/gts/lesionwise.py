@@ -6,7 +6,9 @@ are the lesions and those of the predicted mask P the predicted components (C1-C
 lesion's volume, true positives and box, each component's size and box, and the (component, lesion) pairs that
 touch.  The tables come to the host in one copy; per scored lesion the masks M_k and G_k are written over the
 lesion's box (L3) and go through the HD95 kernels (H1-H5).  The float arithmetic is one division per lesion,
-gts.metrics.percentile95_from_order_stats, and sequential float64 sums in lesion order.
+gts.metrics.percentile95_from_order_stats, and sequential float64 sums in lesion order.  With a voxel spacing the
+per-lesion pair goes through the weighted kernels instead (H3w-H5w): HD95 in millimetres and, with
+tolerances, the normalised surface Dice per lesion from the same call.
 
 Labels are internal: 0 healthy, 1 edema, 2 NET, 3 ET.  Everything runs on the current stream.
 """
@@ -107,9 +109,9 @@ class _RegionState:
                     matched_components=matched, comp_roots=self.comps[:, 0].tolist(), comp_sizes=sizes.tolist(),
                     n_fp=int((~hit).sum()))
 
-    def lesion_hd95(self, k, matched):
-        """hd95(M_k, G_k) over the union box of both, grown by one voxel and clamped: a mask voxel then lies on
-        a face of the crop only where that is a face of the volume, so the crop's borders are the volume's."""
+    def lesion_masks(self, k, matched):
+        """(M_k, G_k) over the union box of both, grown by one voxel and clamped: a mask voxel then lies on a
+        face of the crop only where that is a face of the volume, so the crop's borders are the volume's."""
         lib = self.lib
         boxes = [_box(self.lesions[k], self.shape)] + [_box(self.comps[c], self.shape) for c in matched]
         crop = []
@@ -130,10 +132,22 @@ class _RegionState:
                                            root, self.matched_dev.data_ptr() + 4 * first, count,
                                            (ctypes.c_int64 * 6)(*crop), ptr(mask_m), ptr(mask_g), current_stream()),
               "gts_lesionwise_masks_i16")
-        n, d2_lo, d2_hi, present = metrics.hd95_order_stats(mask_m, mask_g)[2].cpu().tolist()
+        return mask_m, mask_g
+
+    def lesion_hd95(self, k, matched):
+        """hd95(M_k, G_k) in voxels."""
+        n, d2_lo, d2_hi, present = metrics.hd95_order_stats(*self.lesion_masks(k, matched))[2].cpu().tolist()
         if present != 3:
-            raise _lib.GtsError(f"lesionwise: lesion {k} lost a mask over its box {crop}")
+            raise _lib.GtsError(f"lesionwise: lesion {k} lost a mask")
         return metrics.percentile95_from_order_stats(n, d2_lo, d2_hi)
+
+    def lesion_surface(self, k, matched, spacing_mm, tolerances_mm):
+        """(hd95 in mm, [NSD per tolerance]) of M_k against G_k, from one weighted call."""
+        row = metrics.surface_stats(*self.lesion_masks(k, matched), spacing_mm, tolerances_mm)[2].cpu().tolist()
+        if row[3] != 3:
+            raise _lib.GtsError(f"lesionwise: lesion {k} lost a mask")
+        return (metrics.hd95_mm_from_row(row, metrics.spacing_units(spacing_mm)[1]),
+                metrics.surface_dices_from_row(row, len(tolerances_mm)))
 
 
 def lesion_tables(pred, truth, region, dilation=3):
@@ -145,52 +159,84 @@ def lesion_tables(pred, truth, region, dilation=3):
     return _RegionState(_lib.load(), pred, truth, region, dilation).tables()
 
 
-def _region_scores(state, min_lesion_voxels):
+def _region_scores(state, min_lesion_voxels, spacing_mm=None, nsd_tolerances_mm=()):
     t = state.tables()
-    lesions, dice_sum, hd_sum, n_scored, n_fn = [], 0.0, 0.0, 0, 0
+    n_tol = len(nsd_tolerances_mm)
+    lesions, dice_sum, hd_sum, nsd_sum, n_scored, n_fn = [], 0.0, 0.0, [0.0] * n_tol, 0, 0
     for k, (vol, tp, m, matched) in enumerate(zip(t["vol"], t["tp"], t["matched_voxels"], t["matched_components"])):
         scored = vol > min_lesion_voxels
-        dice = hd = None
+        dice = hd = nsd = None
         if scored:
             if m == 0:
-                dice, hd = 0.0, PENALTY_HD95
+                dice, hd, nsd = 0.0, PENALTY_HD95, [0.0] * n_tol
                 n_fn += 1
             else:
                 dice = (2 * tp) / (m + vol)
-                hd = state.lesion_hd95(k, matched)
+                if spacing_mm is None:
+                    hd = state.lesion_hd95(k, matched)
+                else:
+                    hd, nsd = state.lesion_surface(k, matched, spacing_mm, nsd_tolerances_mm)
             dice_sum += dice
             hd_sum += hd
+            nsd_sum = [a + b for a, b in zip(nsd_sum, nsd or ())]
             n_scored += 1
-        lesions.append(dict(vol=vol, tp=tp, matched_voxels=m, scored=scored, dice=dice, hd95=hd))
+        lesion = dict(vol=vol, tp=tp, matched_voxels=m, scored=scored, dice=dice, hd95=hd)
+        if n_tol:
+            lesion["nsd"] = nsd
+        lesions.append(lesion)
     n_fp = t["n_fp"]
     if n_scored + n_fp == 0:
-        lw_dice, lw_hd95 = 1.0, 0.0
+        lw_dice, lw_hd95, lw_nsd = 1.0, 0.0, [1.0] * n_tol
     else:
         lw_dice = dice_sum / (n_scored + n_fp)
         lw_hd95 = (hd_sum + PENALTY_HD95 * n_fp) / (n_scored + n_fp)
-    return dict(lw_dice=lw_dice, lw_hd95=lw_hd95, n_lesions=len(lesions), n_scored=n_scored, n_fp=n_fp, n_fn=n_fn,
-                lesions=lesions, lesion_roots=t["lesion_roots"])
+        lw_nsd = [a / (n_scored + n_fp) for a in nsd_sum]
+    record = dict(lw_dice=lw_dice, lw_hd95=lw_hd95, n_lesions=len(lesions), n_scored=n_scored, n_fp=n_fp, n_fn=n_fn,
+                  lesions=lesions, lesion_roots=t["lesion_roots"])
+    if n_tol:
+        record["lw_nsd"] = lw_nsd
+    return record
 
 
-def lesionwise_scores(pred, truth, dilation=3, min_lesion_voxels=50):
+def lesionwise_scores(pred, truth, dilation=3, min_lesion_voxels=50, spacing_mm=None, nsd_tolerances_mm=()):
     """{"WT" | "CT" | "ET": record} for two int16 CUDA volumes [X, Y, Z] of internal labels.  A record holds
     the legacy whole-region dice (from the confusion counts) and hd95 (gts.metrics.hd95s), lw_dice, lw_hd95,
     n_lesions, n_scored, n_fp, n_fn and `lesions`: one dict per lesion in lesion order with vol, tp,
     matched_voxels, scored, dice and hd95 (None for a lesion of at most min_lesion_voxels voxels, which is
     not scored).  A scored lesion without a matched component has dice 0 and hd95 374, and so does every
-    predicted component matched to no lesion."""
+    predicted component matched to no lesion.
+
+    spacing_mm (x, y, z): the whole-region hd95 and every lesion's are in millimetres (gts.metrics.hd95s_mm);
+    the penalty stays 374 and the dilation stays in voxels.  nsd_tolerances_mm (at most 4, needs a spacing):
+    each record gains `nsd`, the whole-region surface Dice per tolerance (gts.metrics.surface_dices), and
+    `lw_nsd`, its lesion-wise mean over lw_dice's divisor; each lesion gains `nsd` (None when not scored).  A
+    missed lesion and a false-positive component count 0.  Without either the result is what it was."""
     from model import evaluation
 
     from . import ops
 
     pred, truth = _volume.label_pair(pred, truth, "lesionwise_scores", three_d=True)
     dilation = _dilation(dilation, "lesionwise_scores")
+    nsd_tolerances_mm = tuple(nsd_tolerances_mm)
+    if nsd_tolerances_mm and spacing_mm is None:
+        raise _lib.GtsError("lesionwise_scores: nsd_tolerances_mm needs spacing_mm")
     lib = _lib.load()
     dices = evaluation.dices_from_confusion(ops.label_confusion(pred, truth).cpu().numpy())
-    hd95s = metrics.hd95s(pred, truth)
+    nsds = None
+    if spacing_mm is None:
+        hd95s = metrics.hd95s(pred, truth)
+    else:
+        spacing_mm = tuple(spacing_mm)
+        scale = metrics.spacing_units(spacing_mm)[1]
+        rows = metrics.surface_stats(pred, truth, spacing_mm, nsd_tolerances_mm).cpu().tolist()
+        hd95s = [metrics.hd95_mm_from_row(row, scale) for row in rows]
+        nsds = [metrics.surface_dices_from_row(row, len(nsd_tolerances_mm)) for row in rows]
     out = {}
     for r, name in enumerate(REGIONS):
-        record = _region_scores(_RegionState(lib, pred, truth, r, dilation), min_lesion_voxels)
+        record = _region_scores(_RegionState(lib, pred, truth, r, dilation), min_lesion_voxels, spacing_mm,
+                                nsd_tolerances_mm)
         record["dice"], record["hd95"] = float(dices[r]), float(hd95s[r])
+        if nsd_tolerances_mm:
+            record["nsd"] = nsds[r]
         out[name] = record
     return out

@@ -13,6 +13,15 @@ at a time while a small thread pool decodes the next ones.  A scan whose predict
 differs from its truth or that raises is reported and left out; the exit status is 1 when any scan was left out.
 
     python -m scripts.score_predictions -d DATA_DIR -l _seg.nii.gz -s PRED_DIR -o scores.csv
+
+--mm scores distances in millimetres: the voxel spacing is read from the ground-truth file's affine (its column
+norms) and the whole-region and per-lesion HD95 come from gts.metrics' spacing-aware route; a scan
+whose prediction has another spacing, in any step of 1e-4 mm, is left out.  --nsd_tolerance MM [MM ...] (at most
+4, implies --mm) appends the normalised surface Dice at each tolerance, whole-region and lesion-wise, as
+{region}_nsd@{tol} and {region}_lw_nsd@{tol} columns after the existing ones.  Without either flag the CSV is
+what it always was.
+
+    python -m scripts.score_predictions -d DATA_DIR -s PRED_DIR -o scores_mm.csv --mm --nsd_tolerance 1 2
 """
 import argparse
 import os
@@ -36,6 +45,13 @@ REGIONS = ("WT", "CT", "ET")
 FIELDS = ("dice", "hd95", "lw_dice", "lw_hd95", "n_scored", "n_fp", "n_fn")
 COUNTS = ("n_scored", "n_fp", "n_fn")
 HEADER = ["id"] + [f"{region}_{field}" for region in REGIONS for field in FIELDS]
+MAX_TOLERANCES = 4
+
+
+def header_for(tolerances=()):
+    """HEADER, then per tolerance {region}_nsd@{tol} and {region}_lw_nsd@{tol} for the three regions."""
+    return HEADER + [f"{region}_{field}@{tol:g}" for tol in tolerances for region in REGIONS
+                     for field in ("nsd", "lw_nsd")]
 
 
 def build_parser():
@@ -50,7 +66,28 @@ def build_parser():
                         help="dilation steps that merge ground-truth components into lesions")
     parser.add_argument("--min_lesion_voxels", type=int, default=50,
                         help="a ground-truth lesion is scored when it has more voxels than this")
+    parser.add_argument("--mm", action="store_true",
+                        help="HD95 in millimetres, with the voxel spacing of the ground-truth file's affine")
+    parser.add_argument("--nsd_tolerance", type=float, nargs="+", default=[], metavar="MM",
+                        help=f"surface Dice tolerances in mm (at most {MAX_TOLERANCES}; implies --mm): appends "
+                             "{region}_nsd@MM and {region}_lw_nsd@MM columns")
     return parser
+
+
+def spacing_of(path):
+    """The voxel spacing (x, y, z) in mm of a NIfTI file: the column norms of its affine."""
+    affine, _ = nifti_io.read_affine(path)
+    return tuple(float(v) for v in np.sqrt((affine[:3, :3] ** 2).sum(axis=0)))
+
+
+def load_spacing(folder, scan_id, label_extension, pred_dir):
+    """Host stage of --mm: the truth file's voxel spacing, which the prediction's must equal in every step of
+    1e-4 mm (the unit gts.metrics.spacing_units works in)."""
+    truth_path = sorted(os.path.join(folder, f) for f in os.listdir(folder) if f.endswith(label_extension))[0]
+    spacing, pred_spacing = spacing_of(truth_path), spacing_of(os.path.join(pred_dir, scan_id + ".nii.gz"))
+    if [round(v * 10000) for v in spacing] != [round(v * 10000) for v in pred_spacing]:
+        raise ValueError(f"prediction spacing {pred_spacing} mm and ground-truth spacing {spacing} mm differ")
+    return spacing
 
 
 def load_pair(folder, scan_id, label_extension, pred_dir):
@@ -67,36 +104,38 @@ def load_pair(folder, scan_id, label_extension, pred_dir):
     return np.ascontiguousarray(pred), np.ascontiguousarray(truth)
 
 
-def row_of(scores):
-    """The CSV fields of one scan's lesionwise_scores record, in HEADER's order (without the id)."""
-    return [scores[region][field] for region in REGIONS for field in FIELDS]
+def row_of(scores, n_tolerances=0):
+    """The CSV fields of one scan's lesionwise_scores record, in header_for's order (without the id)."""
+    return [scores[region][field] for region in REGIONS for field in FIELDS] + \
+        [scores[region][field][k] for k in range(n_tolerances) for region in REGIONS for field in ("nsd", "lw_nsd")]
 
 
 def mean_row(rows):
     """Column means over the scans' rows (plain float64 means; counts become averages per scan)."""
-    return [float(np.mean([row[c] for row in rows])) for c in range(len(HEADER) - 1)]
+    return [float(np.mean([row[c] for row in rows])) for c in range(len(rows[0]))]
 
 
 def format_value(field, value):
     return str(int(value)) if field.split("_", 1)[1] in COUNTS and float(value).is_integer() else repr(float(value))
 
 
-def format_row(name, values):
-    return ",".join([name] + [format_value(field, value) for field, value in zip(HEADER[1:], values)])
+def format_row(name, values, header=HEADER):
+    return ",".join([name] + [format_value(field, value) for field, value in zip(header[1:], values)])
 
 
-def write_csv(path, rows):
+def write_csv(path, rows, tolerances=()):
     """rows: {id: values}; the ids in sorted order, then the mean row (when any scan was scored)."""
+    header = header_for(tolerances)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
-        f.write(",".join(HEADER) + "\n")
+        f.write(",".join(header) + "\n")
         for scan_id in sorted(rows):
-            f.write(format_row(scan_id, rows[scan_id]) + "\n")
+            f.write(format_row(scan_id, rows[scan_id], header) + "\n")
         if rows:
-            f.write(format_row("mean", mean_row([rows[s] for s in sorted(rows)])) + "\n")
+            f.write(format_row("mean", mean_row([rows[s] for s in sorted(rows)]), header) + "\n")
 
 
-def score(scans, label_extension, pred_dir, dilation=3, min_lesion_voxels=50):
+def score(scans, label_extension, pred_dir, dilation=3, min_lesion_voxels=50, mm=False, tolerances=()):
     """({id: CSV values}, ids left out) of {id: folder}."""
     import torch
 
@@ -105,18 +144,23 @@ def score(scans, label_extension, pred_dir, dilation=3, min_lesion_voxels=50):
     ids = sorted(scans)
     rows, failed = {}, []
     with ThreadPoolExecutor(max_workers=IO_WORKERS) as pool:
+        def load(i):
+            pair = load_pair(scans[ids[i]], ids[i], label_extension, pred_dir)
+            return pair + ((load_spacing(scans[ids[i]], ids[i], label_extension, pred_dir),) if mm else ())
+
         def submit(i):
-            return pool.submit(load_pair, scans[ids[i]], ids[i], label_extension, pred_dir)
+            return pool.submit(load, i)
 
         pending = {i: submit(i) for i in range(min(READ_AHEAD, len(ids)))}
         for i, scan_id in enumerate(ids):
             if i + READ_AHEAD < len(ids):
                 pending[i + READ_AHEAD] = submit(i + READ_AHEAD)
             try:
-                pred, truth = pending.pop(i).result()
+                pred, truth, *spacing = pending.pop(i).result()
+                extra = dict(spacing_mm=spacing[0], nsd_tolerances_mm=tuple(tolerances)) if mm else {}
                 rows[scan_id] = row_of(lesionwise.lesionwise_scores(torch.from_numpy(pred).cuda(),
                                                                     torch.from_numpy(truth).cuda(), dilation,
-                                                                    min_lesion_voxels))
+                                                                    min_lesion_voxels, **extra), len(tolerances))
             except Exception as exc:
                 print(f"{scan_id}: left out ({exc!r})")
                 failed.append(scan_id)
@@ -124,12 +168,16 @@ def score(scans, label_extension, pred_dir, dilation=3, min_lesion_voxels=50):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if len(args.nsd_tolerance) > MAX_TOLERANCES:
+        parser.error(f"--nsd_tolerance takes at most {MAX_TOLERANCES} values")
+    mm = args.mm or bool(args.nsd_tolerance)
     scans = prep.find_scans(args.data_dir or Filepaths.INPUT_MRI_DIR, args.data_prefix)
     print(f"{len(scans)} scan folders found; scores go to {args.output}")
     rows, failed = score(scans, args.label_extension, os.path.expanduser(args.pred_dir), args.dilation,
-                         args.min_lesion_voxels)
-    write_csv(os.path.expanduser(args.output), rows)
+                         args.min_lesion_voxels, mm, args.nsd_tolerance)
+    write_csv(os.path.expanduser(args.output), rows, args.nsd_tolerance)
     if rows:
         means = mean_row([rows[s] for s in sorted(rows)])
         for r, region in enumerate(REGIONS):
@@ -137,6 +185,9 @@ def main(argv=None):
             print(f"{region}: Dice {part['dice']:.4f}, HD95 {part['hd95']:.3f}, lesion-wise Dice {part['lw_dice']:.4f}, "
                   f"lesion-wise HD95 {part['lw_hd95']:.3f} (per scan: {part['n_scored']:.2f} scored lesions, "
                   f"{part['n_fp']:.2f} false positives, {part['n_fn']:.2f} missed)")
+            for k, tol in enumerate(args.nsd_tolerance):
+                at = len(HEADER) - 1 + 2 * (len(REGIONS) * k + r)
+                print(f"{region}: surface Dice at {tol:g} mm {means[at]:.4f}, lesion-wise {means[at + 1]:.4f}")
     print(f"{len(rows)} scan(s) scored, {len(failed)} left out")
     return 1 if failed else 0
 

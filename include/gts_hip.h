@@ -801,6 +801,30 @@ int32_t gts_hd95_order_stats_i16(const int16_t* pred, const int16_t* truth, int6
                                  int32_t all_border, int64_t* out, void* workspace, int64_t workspace_bytes,
                                  void* stream);
 
+/* ---- H3w-H5w: surface distances under a voxel spacing (HD95 in millimetres, surface Dice) -------------
+ * What medpy's hd95(voxelspacing=...) and the surface-Dice scripts of the BraTS tasks compute on the host with
+ * distance_transform_edt(sampling=...), for the borders H1 defines (model/evaluation.py:112-189 with a spacing).
+ * units (HOST int64 [3], read at launch): the voxel spacing along X, Y, Z as positive integers u_a <= 10^6 with
+ * no common factor needed (gts.metrics.spacing_units: 1e-4 mm steps divided by a common divisor).  The device quantity
+ * is D2(p) = min over border voxels q of the other side of sum_a u_a^2 (p_a - q_a)^2, an exact int64; a distance
+ * is sqrt(double(D2)) times the caller's scale.  thresholds (HOST int64 [n_thresholds], 0 <= n_thresholds <= 4;
+ * may be NULL when n_thresholds is 0): squared tolerances T_k >= 0 in the same integer units.
+ * out (device int64 [3][12], one row per region): n, D2 at ranks lo and hi, presence bits, all four as in
+ * gts_hd95_order_stats_i16 (with units {1, 1, 1} the same integers), then within[side][k] for side pred, truth
+ * and k < 4: the number of border voxels of that side with D2 <= T_k (0 for k >= n_thresholds, and for a region
+ * absent from either side).
+ * Arithmetic is int64; with B = sum_a u_a^2 (N_a - 1)^2 a volume is accepted when every extent is in [1, 4097],
+ * X * Y * Z < 2^31 and B * max(N_a) < 2^62 (the envelope's cross-multiplied comparison then cannot overflow),
+ * else GTS_ERR_SHAPE; 240 x 240 x 155 passes at any spacing up to 10 mm.  A unit outside [1, 10^6], a negative
+ * threshold, n_thresholds outside 0..4 or all_border outside {0, 1}: GTS_ERR_ARGKIND.  Every argument is checked
+ * before anything is launched.  workspace: gts_surface_workspace(X, Y, Z, units) bytes (0 for a rejected shape
+ * or unit).  Integer arithmetic and integer atomics throughout: identical results on every run. */
+int64_t gts_surface_workspace(int64_t X, int64_t Y, int64_t Z, const int64_t* units);
+int32_t gts_surface_stats_i16(const int16_t* pred, const int16_t* truth, int64_t X, int64_t Y, int64_t Z,
+                              int32_t all_border, const int64_t* units, const int64_t* thresholds,
+                              int32_t n_thresholds, int64_t* out, void* workspace, int64_t workspace_bytes,
+                              void* stream);
+
 /* ---- C1-C5: 3-D connected components and the small-island clean-up of a prediction ------------------
  * The post-processing step a user otherwise runs on the host with scipy.ndimage.label + np.bincount.
  * labels: int16 volume [X, Y, Z], Z contiguous; foreground is labels != 0, whatever the values.  connectivity
