@@ -4,7 +4,10 @@ Bars: bit-exact for max aggregation (+ its argmax), for the sum/mean/gcn reducer
 kernels accumulate in the oracle's slot order and divide like it) and for the voxel
 projection; rtol/atol 1e-5 against the fp32 oracle for the GAT attention path on benign random
 graphs here (device expf is not bit-identical to the host's) — the float64 bounds of that path, at
-its degree, geometry and score edges, are in tests/test_gpu_gat_edges.py."""
+its degree, geometry and score edges, are in tests/test_gpu_gat_edges.py.  The reducers run here on benign
+random graphs (mean degree about 7, one hub, one empty row) and partly through the routing of gts.ops; their
+degree, width, grid, option, flag and value-class edges, on the plain kernels alone, are in
+tests/test_gpu_spmm_edges.py."""
 import os
 
 import numpy as np
