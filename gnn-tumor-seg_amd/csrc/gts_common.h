@@ -24,6 +24,13 @@ __device__ __forceinline__ int xcd_contiguous_tile(int b, int nb) {
 // -Inf gives 0.  One form everywhere, so tiles, panels and chains stay bit-equal.
 __device__ __forceinline__ float relu_f32(float v) { return v < 0.f ? 0.f : v; }
 
+// Row index inside [table rows..., background] of a supervoxel id: numpy semantics of table_plus_bg[id]
+// for id in [-(n_rows+1), n_rows]; anything outside selects the background row (index n_rows).
+__device__ __forceinline__ int resolve_row(int id, int n_rows) {
+  const int r = id < 0 ? id + n_rows + 1 : id;
+  return (r < 0 || r > n_rows) ? n_rows : r;
+}
+
 template <int VEC>
 struct Vec;
 template <>

@@ -33,13 +33,6 @@ constexpr int kVoxPerLane = 8;                     // one 16-byte load of int16 
 constexpr int kVoxPerWave = kWave * kVoxPerLane;   // 512
 constexpr int kVoxPerBlock = kVoxPerWave * kWavesPerBlock;
 
-// Row index inside [table rows..., background]: numpy semantics of table_plus_bg[id]
-// for id in [-(n_rows+1), n_rows]; anything outside selects the background row.
-__device__ __forceinline__ int resolve_row(int id, int n_rows) {
-  const int r = id < 0 ? id + n_rows + 1 : id;
-  return (r < 0 || r > n_rows) ? n_rows : r;
-}
-
 // ids of this wave's tile -> per-lane registers, lane l gets voxels j*64 + l.
 __device__ __forceinline__ void load_tile_ids(const int16_t* __restrict__ svs, int64_t tile_base,
                                               int64_t n_vox, int16_t* lds_wave,
@@ -191,7 +184,7 @@ inline void launch_project_argmax(const int16_t* svs, const float* logits, const
 }  // namespace
 }  // namespace gts
 
-extern "C" int32_t gts_abi_version(void) { return 33; }
+extern "C" int32_t gts_abi_version(void) { return 34; }
 
 extern "C" const char* gts_error_string(int32_t code) {
   switch (code) {

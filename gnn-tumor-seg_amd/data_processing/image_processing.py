@@ -14,6 +14,18 @@ def uncrop_to_brats_size(crop, voxel_preds):
     return full
 
 
+def uncrop_maps_to_brats_size(crop, maps):
+    """uncrop_to_brats_size for a stack of uint8 maps [K, x, y, z] (the uncertainty maps of gts.uncertainty):
+    uint8 [K, *BRATS_SHAPE], zero (certain) outside the crop."""
+    maps = np.asarray(maps)
+    if maps.dtype != np.uint8 or maps.ndim != 4:
+        raise ValueError(f"maps must be uint8 [K, x, y, z], got {maps.dtype} {maps.shape}")
+    full = np.zeros((maps.shape[0],) + tuple(BRATS_SHAPE), dtype=np.uint8)
+    for k in range(maps.shape[0]):
+        full[k][crop] = maps[k]
+    return full
+
+
 def uncrop_to_shape(crop, voxel_preds, shape):
     """uncrop_to_brats_size for a volume of any shape: the cropped predictions pasted into a zero (healthy)
     int16 volume of `shape` (a scan conformed from another geometry has its own extents)."""

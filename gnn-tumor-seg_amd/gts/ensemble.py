@@ -131,9 +131,11 @@ class EnsemblePredictor:
             _, total = self._node_logits(graph.to(device), self._on_device(feats, device, torch.float32))
             return total.div_(len(self.graph_nets))
 
-    def predict_gnn(self, graph, feats, svs, relabel=None, cleanup=None):
+    def predict_gnn(self, graph, feats, svs, relabel=None, cleanup=None, return_uncertainty=False):
         """GNN-only prediction: int16 label volume of the partitioning's shape (numpy), project_argmax of the mean
-        node probabilities, then the optional `cleanup` (which expects BraTS coding: relabel = INTERNAL_TO_BRATS)."""
+        node probabilities, then the optional `cleanup` (which expects BraTS coding: relabel = INTERNAL_TO_BRATS).
+        With return_uncertainty: (labels, uint8 [3, X, Y, Z] numpy), the region maps of DESIGN.md 4u over the
+        members' node probabilities (U1n); `cleanup` changes labels only, never the maps."""
         device = self._device()
         with torch.no_grad():
             svs = self._on_device(svs, device)
@@ -141,12 +143,18 @@ class EnsemblePredictor:
             pred = ops.project_argmax(svs, total, relabel)
             if cleanup is not None:
                 pred = cleanup(pred)
-            return pred.cpu().numpy()
+            labels = pred.cpu().numpy()
+            if return_uncertainty:
+                return labels, ops.region_uncertainty_nodes(svs, total, len(self.graph_nets)).cpu().numpy()
+            return labels
 
-    def predict_joint(self, graph, feats, img, svs, relabel=None, cleanup=None, return_probabilities=False):
+    def predict_joint(self, graph, feats, img, svs, relabel=None, cleanup=None, return_probabilities=False,
+                      return_uncertainty=False):
         """Steps 1-5: int16 label volume of the partitioning's shape (numpy), the ensemble's CNN prediction inside
         the one crop box all members share, healthy outside.  Operands as predict_one_sample.  With
-        return_probabilities: (labels, mean probabilities fp32 [cx, cy, cz, C] on the device, the CropBox)."""
+        return_probabilities: (labels, mean probabilities fp32 [cx, cy, cz, C] on the device, the CropBox).  With
+        return_uncertainty a uint8 [3, X, Y, Z] numpy array follows the labels: the region maps of DESIGN.md 4u,
+        from the class sums before the division (U1), 0 outside the box; `cleanup` never changes them."""
         from scripts.generate_joint_predictions import gnn_crop_box
         from utils.hyperparam_helpers import DEFAULT_BACKGROUND_NODE_LOGITS
 
@@ -179,6 +187,9 @@ class EnsemblePredictor:
             if cleanup is not None:
                 pred = cleanup(pred)
             labels = pred.cpu().numpy()
+            first = (labels,)
+            if return_uncertainty:
+                first += (ops.region_uncertainty_rows(total, self.terms, box).cpu().numpy(),)                # U1
             if return_probabilities:
-                return labels, total.div_(self.terms).view(*box.shape, -1), box
-            return labels
+                return first + (total.div_(self.terms).view(*box.shape, -1), box)
+            return first if return_uncertainty else labels

@@ -729,6 +729,83 @@ def softmax_accumulate(logit_sets, acc=None):
     return acc
 
 
+UNCERTAINTY_BINS = _lib.const("GTS_UNCERTAINTY_BINS")
+UNCERTAINTY_CLASSES = 4     # the internal labels 0 healthy, 1 edema, 2 NET, 3 ET: the regions are sets of them
+
+
+def _uncertainty_sums(total, terms, what):
+    f32(total)
+    if total.dim() < 1 or total.shape[-1] != UNCERTAINTY_CLASSES:
+        raise _lib.GtsError(f"{what}: the class sums must have {UNCERTAINTY_CLASSES} columns, got "
+                            f"{tuple(total.shape)}")
+    if int(terms) != terms or not 1 <= terms <= 2 ** 31:
+        raise _lib.GtsError(f"{what}: terms must be a whole number in 1..2^31, got {terms!r}")
+    return int(terms)
+
+
+def region_uncertainty_rows(total, terms, box):
+    """U1.  uint8 [3, X, Y, Z] (WT, CT, ET), zero outside the box: the QU-BraTS style uncertainty 0..100 of the
+    class sums `total` [cx * cy * cz, 4] (or [cx, cy, cz, 4]) that softmax_accumulate left over `terms` softmaxes
+    (the SUM, before any division).  DESIGN.md 4u has the formula; it equals the numpy expression bit for bit."""
+    terms = _uncertainty_sums(total, terms, "region_uncertainty_rows")
+    total = _rows_over_box(total, box.shape, "region_uncertainty_rows", UNCERTAINTY_CLASSES).contiguous()
+    require_device(total, *box.dev)
+    out = torch.zeros((3,) + tuple(box.volume_shape), dtype=torch.uint8, device=total.device)
+    cx, cy, cz = box.shape
+    if total.numel():
+        check(_lib.load().gts_region_uncertainty_rows_u8(ptr(total), ptr(box.dev[0]), ptr(box.dev[1]),
+                                                         ptr(box.dev[2]), ptr(out), cx, cy, cz, *box.volume_shape,
+                                                         total.shape[1], terms, current_stream()),
+              "gts_region_uncertainty_rows_u8")
+    return out
+
+
+def region_uncertainty_nodes(svs, total, terms):
+    """U1n.  uint8 [3, *svs.shape]: the uncertainty of the node class sums `total` [N, 4] (over `terms` members)
+    at every voxel's node, ids resolved as project_argmax resolves them; background voxels get 0."""
+    terms = _uncertainty_sums(total, terms, "region_uncertainty_nodes")
+    if svs.dtype != torch.int16:
+        raise _lib.GtsError("supervoxel partitioning must be int16")
+    if total.dim() != 2:
+        raise _lib.GtsError(f"region_uncertainty_nodes: the class sums must be [N, 4], got {tuple(total.shape)}")
+    svs, total = svs.contiguous(), total.contiguous()
+    require_device(svs, total)
+    out = torch.empty((3,) + tuple(svs.shape), dtype=torch.uint8, device=svs.device)
+    if svs.numel():
+        check(_lib.load().gts_region_uncertainty_nodes_u8(ptr(svs), ptr(total), ptr(out), svs.numel(),
+                                                          total.shape[0], total.shape[1], terms, current_stream()),
+              "gts_region_uncertainty_nodes_u8")
+    return out
+
+
+def uncertainty_histogram(pred, truth, unc):
+    """U2.  int64 [3, 4, 102] on the device: per region (WT, CT, ET) and outcome (TP, FP, FN, TN of the region
+    masks of pred / truth, int16 internal labels 0..3) the number of voxels at each value 0..100 of the region's
+    map unc[r] (uint8 [3, ...] over the same voxels); the last bin stays 0.  A map value above 100 or a label
+    outside 0..3 raises GtsError (after the one pass that finds it)."""
+    if pred.dtype != torch.int16 or truth.dtype != torch.int16:
+        raise _lib.GtsError("uncertainty_histogram takes int16 labels")
+    if unc.dtype != torch.uint8:
+        raise _lib.GtsError(f"uncertainty_histogram takes uint8 maps, got {unc.dtype}")
+    n = pred.numel()
+    if truth.numel() != n:
+        raise _lib.GtsError(f"uncertainty_histogram: {n} predictions vs {truth.numel()} labels")
+    if unc.dim() < 1 or unc.shape[0] != 3 or unc.numel() != 3 * n:
+        raise _lib.GtsError(f"uncertainty_histogram: the maps must be [3, {n} voxels], got {tuple(unc.shape)}")
+    pred, truth, unc = pred.contiguous(), truth.contiguous(), unc.contiguous()
+    require_device(pred, truth, unc)
+    hist = torch.zeros((4, 4, UNCERTAINTY_BINS), dtype=torch.int64, device=pred.device)
+    if n:
+        check(_lib.load().gts_uncertainty_histogram(ptr(pred), ptr(truth), ptr(unc), ptr(hist), n, current_stream()),
+              "gts_uncertainty_histogram")
+    host = hist.cpu()
+    if int(host[3, 0, 0]):
+        raise _lib.GtsError(f"uncertainty_histogram: {int(host[3, 0, 0])} voxel(s) carry a label outside 0..3")
+    if int(host[:3, :, UNCERTAINTY_BINS - 1].sum()):
+        raise _lib.GtsError("uncertainty_histogram: the maps hold values above 100")
+    return hist[:3]
+
+
 def label_confusion(pred, truth):
     """K15.  int64 [5, 5] table on the device: entry [cp, ct] counts the positions where the
     predicted label has class cp and the true label class ct (class = label for 0..3, 4 for

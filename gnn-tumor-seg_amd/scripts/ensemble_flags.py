@@ -1,6 +1,12 @@
 """The ensemble flags of the prediction CLIs (segment_scans, generate_gnn_predictions, generate_joint_predictions),
 defined once.  With none of them given `from_args` returns None and gts.ensemble is never imported: the CLIs then
-run the single-model path and write what they always wrote."""
+run the single-model path and write what they always wrote.
+
+--uncertainty_dir DIR also writes the three region uncertainty maps of every scan as
+DIR/{id}_unc_whole.nii.gz, _unc_core and _unc_enhance: uint8, 0..100, on the label file's grid.  The maps come from
+the ensemble's probabilities, so the flag alone (one weight set, no mirrors) routes the scan through
+gts.ensemble.EnsemblePredictor with one term; with -c the labels then come from the HIP convolutions and not from
+the single-model path's torch convolutions, and may differ from it where two classes are within rounding."""
 import os
 
 MIRROR_AXES = "xyz"
@@ -34,7 +40,27 @@ def add_flags(parser, cnn=True):
         parser.add_argument("--tta_mirror", type=mirror_axes, default=None, metavar="AXES",
                             help="also average the CNN's probabilities over the mirrored views along these axes, a "
                                  "non-empty subset of xyz (xyz: 8 views)")
+    parser.add_argument("--uncertainty_dir", default=None, metavar="DIR",
+                        help="also write {id}_unc_whole / _unc_core / _unc_enhance.nii.gz there: uint8 maps 0..100 of "
+                             "how unsure the averaged probabilities are about each region (alone it runs a "
+                             "one-member ensemble)")
     return parser
+
+
+def uncertainty_dir(args):
+    """The expanded --uncertainty_dir of parsed arguments, or None."""
+    folder = getattr(args, "uncertainty_dir", None)
+    return os.path.expanduser(folder) if folder else None
+
+
+def save_uncertainty_maps(folder, scan_id, maps, affine=None):
+    """Write uint8 maps [3, X, Y, Z] (WT, CT, ET) as the scan's three map files in `folder`."""
+    from data_processing import nifti_io
+    from gts.uncertainty import map_file_names
+
+    os.makedirs(folder, exist_ok=True)
+    for name, volume in zip(map_file_names(scan_id), maps):
+        nifti_io.save_as_nifti(volume, os.path.join(folder, name), nifti_io.BRATS_AFFINE if affine is None else affine)
 
 
 class Members:
@@ -75,16 +101,19 @@ def from_args(args, gnn_weights, cnn_weights, save_format="preds"):
     also_gnn = getattr(args, "also_gnn_weights", None)
     also_cnn = getattr(args, "also_cnn_weights", None)
     axes = getattr(args, "tta_mirror", None)
+    maps = bool(getattr(args, "uncertainty_dir", None))
+    if maps and getattr(args, "conform", False):
+        raise FlagError("--uncertainty_dir does not go with --conform: the maps are written on the BraTS grid only")
     if not cnn_weights:         # mirrors are then ignored (mirrors_ignored)
         if also_cnn:
             raise FlagError("--also_cnn_weights needs the first member's convolutional net (-c)")
-        if not also_gnn:
+        if not also_gnn and not maps:
             return None
         if save_format != "preds":
-            raise FlagError("--also_gnn_weights goes with -f preds: logit files are written per member, because "
-                            "they feed that member's CNN training")
-        return Members([gnn_weights, *map(os.path.expanduser, also_gnn)], None, "")
-    if not also_gnn and not also_cnn and not axes:
+            raise FlagError("--also_gnn_weights and --uncertainty_dir go with -f preds: logit files are written per "
+                            "member, because they feed that member's CNN training")
+        return Members([gnn_weights, *map(os.path.expanduser, also_gnn or ())], None, "")
+    if not also_gnn and not also_cnn and not axes and not maps:
         return None
     if bool(also_gnn) != bool(also_cnn):
         raise FlagError("joint prediction pairs the members' nets: give both --also_gnn_weights and "

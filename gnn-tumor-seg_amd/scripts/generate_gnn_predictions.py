@@ -7,6 +7,9 @@ The forward pass, the argmax and the node -> voxel projection all stay on the GP
 --also_gnn_weights P [P ...] (with -f preds) averages the node class probabilities of further weight files, e.g. the
 other folds, with the first one's before the arg-max (gts.ensemble).  Logit files stay per member:
 they feed that member's CNN training.
+
+--uncertainty_dir DIR (with -f preds) also writes the three region uncertainty maps of the members' mean node
+probabilities per scan (gts.uncertainty); alone it runs a one-member ensemble.
 """
 import argparse
 import os
@@ -17,7 +20,7 @@ import torch
 
 import Filepaths
 from data_processing import data_loader, graph_io, nifti_io
-from data_processing.image_processing import uncrop_to_brats_size
+from data_processing.image_processing import uncrop_maps_to_brats_size, uncrop_to_brats_size
 from data_processing.labels import INTERNAL_TO_BRATS
 from gts import dist as gdist
 from gts import ops
@@ -87,15 +90,21 @@ def save_predictions(net, dataset, save_format="logits", cleanup=None):
             save_voxel_logits(mri_id, dataset, logits)
 
 
-def save_ensemble_predictions(predictor, dataset, cleanup=None):
+def save_ensemble_predictions(predictor, dataset, cleanup=None, uncertainty_dir=None):
     """save_predictions -f preds for a gts.ensemble.EnsemblePredictor (--also_gnn_weights): the arg-max of the
-    members' mean node probabilities, projected to voxels; the ranks of a torchrun share the samples as above."""
+    members' mean node probabilities, projected to voxels; the ranks of a torchrun share the samples as above.
+    uncertainty_dir: the scan's three region maps go there as well."""
     device = _device()
     relabel = torch.from_numpy(INTERNAL_TO_BRATS).to(device)
     for index in gdist.rank_share(len(dataset)):
         mri_id, graph, feats = dataset[index]
         svs = dataset.get_supervoxel_partitioning(mri_id)
-        voxels = predictor.predict_gnn(graph, feats, svs, relabel, cleanup=cleanup)
+        voxels = predictor.predict_gnn(graph, feats, svs, relabel, cleanup=cleanup,
+                                       return_uncertainty=bool(uncertainty_dir))
+        if uncertainty_dir:
+            voxels, unc = voxels
+            ensemble_flags.save_uncertainty_maps(uncertainty_dir, mri_id,
+                                                 uncrop_maps_to_brats_size(dataset.get_crop(mri_id), unc))
         nifti_io.save_as_nifti(uncrop_to_brats_size(dataset.get_crop(mri_id), voxels),
                                f"{output_dir}{os.sep}{mri_id}.nii.gz")
         if cleanup is not None:
@@ -136,7 +145,8 @@ def main(argv=None):
     dataset = data_loader.ImageGraphDataset(os.path.expanduser(args.data_dir), args.data_prefix,
                                             read_image=False, read_graph=True, read_label=False)
     if members is not None:
-        save_ensemble_predictions(members.predictor(), dataset, cleanup_flags.from_args(args))
+        save_ensemble_predictions(members.predictor(), dataset, cleanup_flags.from_args(args),
+                                  ensemble_flags.uncertainty_dir(args))
     else:
         net = load_net_and_weights(weight_file)
         save_predictions(net, dataset, args.save_format, cleanup_flags.from_args(args))

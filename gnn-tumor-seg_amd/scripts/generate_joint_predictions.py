@@ -26,7 +26,8 @@ import torch
 
 import Filepaths
 from data_processing import data_loader, nifti_io
-from data_processing.image_processing import tumor_crop_from_plane_flags, uncrop_to_brats_size
+from data_processing.image_processing import (tumor_crop_from_plane_flags, uncrop_maps_to_brats_size,
+                                              uncrop_to_brats_size)
 from data_processing.labels import INTERNAL_TO_BRATS
 from gts import ops
 from model.cnn_model import combine_node_logits_and_image
@@ -121,9 +122,9 @@ def save_predictions(graph_net, conv_net, dataset, cleanup=None):
             print(f"{mri}: {cleanup.report()}")
 
 
-def save_ensemble_predictions(predictor, dataset, cleanup=None):
+def save_ensemble_predictions(predictor, dataset, cleanup=None, uncertainty_dir=None):
     """save_predictions for a gts.ensemble.EnsemblePredictor (--also_*_weights, --tta_mirror): same files, the
-    ensemble's labels in them."""
+    ensemble's labels in them.  uncertainty_dir: the scan's three region maps go there as well."""
     relabel = torch.from_numpy(INTERNAL_TO_BRATS).to(_device())
     for mri, graph, node_feats, img in dataset:
         try:
@@ -131,7 +132,11 @@ def save_ensemble_predictions(predictor, dataset, cleanup=None):
             raw_data_crop = dataset.get_crop(mri)
         except FileNotFoundError as e:
             raise FileNotFoundError(f"Couldnt predict {mri} because couldn't read in a required file: {e}")
-        pred = predictor.predict_joint(graph, node_feats, img, supervoxel_partitioning, relabel, cleanup=cleanup)
+        pred = predictor.predict_joint(graph, node_feats, img, supervoxel_partitioning, relabel, cleanup=cleanup,
+                                       return_uncertainty=bool(uncertainty_dir))
+        if uncertainty_dir:
+            pred, unc = pred
+            ensemble_flags.save_uncertainty_maps(uncertainty_dir, mri, uncrop_maps_to_brats_size(raw_data_crop, unc))
         nifti_io.save_as_nifti(uncrop_to_brats_size(raw_data_crop, pred), f"{output_dir}{os.sep}{mri}.nii.gz")
         if cleanup is not None:
             print(f"{mri}: {cleanup.report()}")
@@ -171,7 +176,8 @@ def main(argv=None):
     dataset = data_loader.ImageGraphDataset(os.path.expanduser(args.data_dir), args.data_prefix,
                                             read_image=True, read_graph=True, read_label=False)
     if members is not None:
-        save_ensemble_predictions(members.predictor(args.gnn_type), dataset, cleanup_flags.from_args(args))
+        save_ensemble_predictions(members.predictor(args.gnn_type), dataset, cleanup_flags.from_args(args),
+                                  ensemble_flags.uncertainty_dir(args))
         print(f"Finished saving predictions generated by an ensemble of {members.describe()} in folder {output_dir}")
         return 0
     graph_net, conv_net = load_nets(args.gnn_type, gnn_weights, cnn_weights)

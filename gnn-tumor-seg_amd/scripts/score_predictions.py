@@ -22,6 +22,15 @@ whose prediction has another spacing, in any step of 1e-4 mm, is left out.  --ns
 what it always was.
 
     python -m scripts.score_predictions -d DATA_DIR -s PRED_DIR -o scores_mm.csv --mm --nsd_tolerance 1 2
+
+--uncertainty_dir DIR scores the uncertainty maps the prediction scripts write there with the same flag
+({id}_unc_whole / _unc_core / _unc_enhance.nii.gz, values 0..100) QU-BraTS style (gts.uncertainty):
+after all other columns come, per region, {region}_qu, {region}_qu_dice_auc, {region}_qu_ftp_auc and
+{region}_qu_ftn_auc.  --qu_thresholds T [T ...] sets the filtering thresholds (default 25 50 75 100; at most 8
+strictly ascending integers in 0..100).  A scan with a missing or wrongly shaped map, or one holding a value above
+100, is left out.  Without the flag the CSV is what it always was.
+
+    python -m scripts.score_predictions -d DATA_DIR -s PRED_DIR -o scores_qu.csv --uncertainty_dir UNC_DIR
 """
 import argparse
 import os
@@ -46,12 +55,15 @@ FIELDS = ("dice", "hd95", "lw_dice", "lw_hd95", "n_scored", "n_fp", "n_fn")
 COUNTS = ("n_scored", "n_fp", "n_fn")
 HEADER = ["id"] + [f"{region}_{field}" for region in REGIONS for field in FIELDS]
 MAX_TOLERANCES = 4
+QU_FIELDS = ("qu", "dice_auc", "ftp_auc", "ftn_auc")      # gts.uncertainty.FIELDS; columns {region}_qu, {region}_qu_*
+QU_COLUMNS = [f"{region}_qu" + ("" if field == "qu" else f"_{field}") for region in REGIONS for field in QU_FIELDS]
 
 
-def header_for(tolerances=()):
-    """HEADER, then per tolerance {region}_nsd@{tol} and {region}_lw_nsd@{tol} for the three regions."""
+def header_for(tolerances=(), qu=False):
+    """HEADER, then per tolerance {region}_nsd@{tol} and {region}_lw_nsd@{tol} for the three regions, then (qu) the
+    QU_COLUMNS."""
     return HEADER + [f"{region}_{field}@{tol:g}" for tol in tolerances for region in REGIONS
-                     for field in ("nsd", "lw_nsd")]
+                     for field in ("nsd", "lw_nsd")] + (QU_COLUMNS if qu else [])
 
 
 def build_parser():
@@ -71,7 +83,48 @@ def build_parser():
     parser.add_argument("--nsd_tolerance", type=float, nargs="+", default=[], metavar="MM",
                         help=f"surface Dice tolerances in mm (at most {MAX_TOLERANCES}; implies --mm): appends "
                              "{region}_nsd@MM and {region}_lw_nsd@MM columns")
+    parser.add_argument("--uncertainty_dir", default=None, metavar="DIR",
+                        help="folder of the uncertainty maps {id}_unc_whole / _unc_core / _unc_enhance.nii.gz: appends "
+                             "the {region}_qu columns")
+    parser.add_argument("--qu_thresholds", type=int, nargs="+", default=None, metavar="T",
+                        help="uncertainty thresholds of the QU score: at most 8 ascending integers in 0..100 "
+                             "(default 25 50 75 100; needs --uncertainty_dir)")
     return parser
+
+
+def qu_thresholds(args):
+    """The QU thresholds of parsed arguments (None without --uncertainty_dir); FlagError for ones that cannot be
+    scored, before any scan is read."""
+    from gts.uncertainty import DEFAULT_THRESHOLDS, check_thresholds
+    from scripts.ensemble_flags import FlagError
+
+    given = getattr(args, "qu_thresholds", None)
+    if not getattr(args, "uncertainty_dir", None):
+        if given:
+            raise FlagError("--qu_thresholds needs --uncertainty_dir")
+        return None
+    try:
+        return check_thresholds(DEFAULT_THRESHOLDS if given is None else given)
+    except ValueError as exc:
+        raise FlagError(f"--qu_thresholds: {exc}") from None
+
+
+def load_maps(uncertainty_dir, scan_id, shape):
+    """Host stage of --uncertainty_dir: the scan's three maps as one C-contiguous uint8 [3, X, Y, Z]."""
+    from gts.uncertainty import map_file_names
+
+    maps = np.empty((3,) + tuple(shape), dtype=np.uint8)
+    for k, name in enumerate(map_file_names(scan_id)):
+        path = os.path.join(uncertainty_dir, name)
+        if not os.path.exists(path):
+            raise FileNotFoundError(f"no uncertainty map {path}")
+        volume = nifti_io.read_nifti(path, np.int16)
+        if volume.shape != tuple(shape):
+            raise ValueError(f"uncertainty map {name} has shape {volume.shape}, the labels {tuple(shape)}")
+        if volume.min() < 0 or volume.max() > 100:
+            raise ValueError(f"uncertainty map {name} holds values outside 0..100")
+        maps[k] = volume
+    return maps
 
 
 def spacing_of(path):
@@ -123,9 +176,9 @@ def format_row(name, values, header=HEADER):
     return ",".join([name] + [format_value(field, value) for field, value in zip(header[1:], values)])
 
 
-def write_csv(path, rows, tolerances=()):
+def write_csv(path, rows, tolerances=(), qu=False):
     """rows: {id: values}; the ids in sorted order, then the mean row (when any scan was scored)."""
-    header = header_for(tolerances)
+    header = header_for(tolerances, qu)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
         f.write(",".join(header) + "\n")
@@ -135,18 +188,21 @@ def write_csv(path, rows, tolerances=()):
             f.write(format_row("mean", mean_row([rows[s] for s in sorted(rows)]), header) + "\n")
 
 
-def score(scans, label_extension, pred_dir, dilation=3, min_lesion_voxels=50, mm=False, tolerances=()):
-    """({id: CSV values}, ids left out) of {id: folder}."""
+def score(scans, label_extension, pred_dir, dilation=3, min_lesion_voxels=50, mm=False, tolerances=(),
+          uncertainty_dir=None, thresholds=None):
+    """({id: CSV values}, ids left out) of {id: folder}.  uncertainty_dir / thresholds: the QU_COLUMNS are appended
+    to every row."""
     import torch
 
-    from gts import lesionwise
+    from gts import lesionwise, uncertainty
 
     ids = sorted(scans)
     rows, failed = {}, []
     with ThreadPoolExecutor(max_workers=IO_WORKERS) as pool:
         def load(i):
             pair = load_pair(scans[ids[i]], ids[i], label_extension, pred_dir)
-            return pair + ((load_spacing(scans[ids[i]], ids[i], label_extension, pred_dir),) if mm else ())
+            maps = (load_maps(uncertainty_dir, ids[i], pair[0].shape),) if uncertainty_dir else ()
+            return pair + maps + ((load_spacing(scans[ids[i]], ids[i], label_extension, pred_dir),) if mm else ())
 
         def submit(i):
             return pool.submit(load, i)
@@ -156,11 +212,16 @@ def score(scans, label_extension, pred_dir, dilation=3, min_lesion_voxels=50, mm
             if i + READ_AHEAD < len(ids):
                 pending[i + READ_AHEAD] = submit(i + READ_AHEAD)
             try:
-                pred, truth, *spacing = pending.pop(i).result()
-                extra = dict(spacing_mm=spacing[0], nsd_tolerances_mm=tuple(tolerances)) if mm else {}
-                rows[scan_id] = row_of(lesionwise.lesionwise_scores(torch.from_numpy(pred).cuda(),
-                                                                    torch.from_numpy(truth).cuda(), dilation,
-                                                                    min_lesion_voxels, **extra), len(tolerances))
+                pred, truth, *rest = pending.pop(i).result()
+                maps = rest.pop(0) if uncertainty_dir else None
+                extra = dict(spacing_mm=rest[0], nsd_tolerances_mm=tuple(tolerances)) if mm else {}
+                pred, truth = torch.from_numpy(pred).cuda(), torch.from_numpy(truth).cuda()
+                row = row_of(lesionwise.lesionwise_scores(pred, truth, dilation, min_lesion_voxels, **extra),
+                             len(tolerances))
+                if maps is not None:
+                    qu = uncertainty.qu_scores(pred, truth, torch.from_numpy(maps).cuda(), thresholds)
+                    row += [qu[region][field] for region in REGIONS for field in QU_FIELDS]
+                rows[scan_id] = row
             except Exception as exc:
                 print(f"{scan_id}: left out ({exc!r})")
                 failed.append(scan_id)
@@ -172,12 +233,18 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if len(args.nsd_tolerance) > MAX_TOLERANCES:
         parser.error(f"--nsd_tolerance takes at most {MAX_TOLERANCES} values")
+    try:
+        thresholds = qu_thresholds(args)
+    except ValueError as exc:       # a FlagError
+        print(f"score_predictions: {exc}", file=sys.stderr)
+        return 2
+    unc_dir = os.path.expanduser(args.uncertainty_dir) if args.uncertainty_dir else None
     mm = args.mm or bool(args.nsd_tolerance)
     scans = prep.find_scans(args.data_dir or Filepaths.INPUT_MRI_DIR, args.data_prefix)
     print(f"{len(scans)} scan folders found; scores go to {args.output}")
     rows, failed = score(scans, args.label_extension, os.path.expanduser(args.pred_dir), args.dilation,
-                         args.min_lesion_voxels, mm, args.nsd_tolerance)
-    write_csv(os.path.expanduser(args.output), rows, args.nsd_tolerance)
+                         args.min_lesion_voxels, mm, args.nsd_tolerance, unc_dir, thresholds)
+    write_csv(os.path.expanduser(args.output), rows, args.nsd_tolerance, unc_dir is not None)
     if rows:
         means = mean_row([rows[s] for s in sorted(rows)])
         for r, region in enumerate(REGIONS):
@@ -188,6 +255,11 @@ def main(argv=None):
             for k, tol in enumerate(args.nsd_tolerance):
                 at = len(HEADER) - 1 + 2 * (len(REGIONS) * k + r)
                 print(f"{region}: surface Dice at {tol:g} mm {means[at]:.4f}, lesion-wise {means[at + 1]:.4f}")
+            if unc_dir is not None:
+                part = dict(zip(QU_FIELDS, means[len(means) - len(QU_COLUMNS) + r * len(QU_FIELDS):]))
+                print(f"{region}: QU score {part['qu']:.4f} at thresholds {' '.join(map(str, thresholds))} (Dice AUC "
+                      f"{part['dice_auc']:.4f}, filtered TP AUC {part['ftp_auc']:.4f}, filtered TN AUC "
+                      f"{part['ftn_auc']:.4f})")
     print(f"{len(rows)} scan(s) scored, {len(failed)} left out")
     return 1 if failed else 0
 

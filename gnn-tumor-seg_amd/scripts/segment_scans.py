@@ -17,12 +17,19 @@ A scan that raises is reported and skipped; the exit status is 1 when any scan w
                                     [--min_component_voxels N --connectivity {6,26} --min_enhancing_voxels T]
                                     [--conform]
                                     [--also_gnn_weights P [P ...] --also_cnn_weights P [P ...]] [--tta_mirror AXES]
+                                    [--uncertainty_dir DIR]
 
 --also_gnn_weights / --also_cnn_weights name further members (the other folds' weight files, paired in order) and
 --tta_mirror AXES (a non-empty subset of xyz) adds the CNN's mirrored views: class probabilities are averaged over
 all members and views before the arg-max (gts.ensemble), and the result equals what
 `generate_joint_predictions` (without -c: `generate_gnn_predictions`) writes with the same flags.  With none of them
 the single-model path runs as before.
+
+--uncertainty_dir DIR also writes DIR/{id}_unc_whole.nii.gz, {id}_unc_core.nii.gz and {id}_unc_enhance.nii.gz: uint8
+maps 0..100 of how unsure the averaged class probabilities are about each region (gts.uncertainty), on
+the grid and with the affine of the label file; scripts.score_predictions --uncertainty_dir scores them.  Given alone
+it runs a one-member ensemble, so with -c the labels come from the HIP convolutions.  The clean-up flags change
+labels only, never the maps.  Not with --conform.
 
 --min_component_voxels N drops connected components of the predicted whole tumour with fewer than N voxels,
 --min_enhancing_voxels T relabels the enhancing tumour to necrotic core when fewer than T voxels of it remain
@@ -55,7 +62,8 @@ if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
 from data_processing import nifti_io, standardization  # noqa: E402
-from data_processing.image_processing import uncrop_to_brats_size, uncrop_to_shape  # noqa: E402
+from data_processing.image_processing import (uncrop_maps_to_brats_size, uncrop_to_brats_size,  # noqa: E402
+                                              uncrop_to_shape)
 from data_processing.labels import INTERNAL_TO_BRATS  # noqa: E402
 from gts import conform, graphgen, intake, ops  # noqa: E402
 from scripts import cleanup as cleanup_flags  # noqa: E402
@@ -127,6 +135,8 @@ class Segmenter:
         gnn = os.path.expanduser(args.gnn_weights)
         members = ensemble_flags.from_args(args, gnn, os.path.expanduser(args.cnn_weights))   # None: one model
         self.ensemble = None
+        self.uncertainty_dir = ensemble_flags.uncertainty_dir(args)     # with it, members is never None
+        self.last_uncertainty = None            # the maps of the scan segment() saw last, uint8 [3, *BRATS_SHAPE]
         if members is not None:
             self.ensemble = members.predictor(args.gnn_type)
             self.graph_net, self.conv_net = None, None
@@ -171,10 +181,15 @@ class Segmenter:
         partition = res["partition"]
         tick("graph")
         if self.ensemble is not None:
+            maps = dict(return_uncertainty=True) if self.uncertainty_dir else {}
             if self.joint:
-                pred = self.ensemble.predict_joint(graph, feats, image, partition, self.relabel, cleanup=self.cleanup)
+                pred = self.ensemble.predict_joint(graph, feats, image, partition, self.relabel, cleanup=self.cleanup,
+                                                   **maps)
             else:
-                pred = self.ensemble.predict_gnn(graph, feats, partition, self.relabel, cleanup=self.cleanup)
+                pred = self.ensemble.predict_gnn(graph, feats, partition, self.relabel, cleanup=self.cleanup, **maps)
+            if maps:
+                pred, unc = pred
+                self.last_uncertainty = uncrop_maps_to_brats_size(crop, unc)
         elif self.conv_net is not None:
             from scripts.generate_joint_predictions import predict_one_sample
 
@@ -197,9 +212,11 @@ class Segmenter:
         tick("unconform")
         return back.cpu().numpy().T          # [X, Y, Z], x fastest: the order the file stores
 
-    def store(self, scan_id, volume, affine=nifti_io.BRATS_AFFINE):
+    def store(self, scan_id, volume, affine=nifti_io.BRATS_AFFINE, maps=None):
         """Host stage: gzip NIfTI encode."""
         nifti_io.save_as_nifti(volume, os.path.join(self.output_dir, scan_id + ".nii.gz"), affine)
+        if maps is not None:
+            ensemble_flags.save_uncertainty_maps(self.uncertainty_dir, scan_id, maps, affine)
 
     def run(self, scans, output_dir):
         """Segment every scan of {id: folder}; returns the ids that were skipped."""
@@ -215,6 +232,7 @@ class Segmenter:
                 try:
                     staged = pending.pop(i).result()
                     volume = self.segment(staged)
+                    maps = self.last_uncertainty if self.uncertainty_dir else None
                     note = f" ({self.cleanup.report()})" if self.cleanup is not None else ""
                     if self.conform:
                         note += f" ({staged[1].describe()})"
@@ -223,7 +241,7 @@ class Segmenter:
                     failed.append(scan_id)
                     continue
                 affine = staged[2] if self.conform else nifti_io.BRATS_AFFINE
-                writes.append((scan_id, note, pool.submit(self.store, scan_id, volume, affine)))
+                writes.append((scan_id, note, pool.submit(self.store, scan_id, volume, affine, maps)))
             for scan_id, note, job in writes:
                 try:
                     job.result()

@@ -985,6 +985,36 @@ int32_t gts_argmax_scatter_rows_i16(const float* scores, const int16_t* relabel,
                                     const int32_t* ys, const int32_t* zs, int16_t* out, int64_t cx, int64_t cy,
                                     int64_t cz, int64_t dim_y, int64_t dim_z, int64_t n_classes, void* stream);
 
+/* ---- U1/U1n/U2: voxel-wise uncertainty maps of an ensemble and their QU-BraTS style counts (no
+ * counterpart in the reference) -------------------------------------------------------------------------------
+ * The uncertainty of a row of fp32 class sums s[0..3] (E1's output, the SUM over `terms` softmaxes; classes
+ * 0 healthy, 1 edema, 2 NET, 3 ET) for region r (0 WT = {1, 2, 3}, 1 CT = {2, 3}, 2 ET = {3}):
+ *   S = the region's sums added as float64 in ascending class order;  p = S / (double)terms clamped to [0, 1];
+ *   u = (uint8) rint(200 * min(p, 1 - p)), round-half-to-even, 0..100; a NaN p gives 100.
+ * Float64 add, divide, min, multiply and rint only, none contracted: the bits of the same numpy expression.
+ * n_classes must be 4 and 1 <= terms <= 2^31, else GTS_ERR_SHAPE.
+ * U1 region_uncertainty_rows: out[r, xs[i], ys[j], zs[k]] = u_r(sums[(i * cy + j) * cz + k, :]) for the three
+ *   regions; `out` is a caller-zeroed uint8 [3, dim_x, dim_y, dim_z] whose other voxels are left alone.  Box
+ *   operands as gts_argmax_scatter_rows_i16, extents at most 32768, c* <= dim_* and cx * cy * cz < 2^31.  A
+ *   `sums` pointer that is not 16-byte aligned is read with scalar loads: same bits. */
+int32_t gts_region_uncertainty_rows_u8(const float* sums, const int32_t* xs, const int32_t* ys, const int32_t* zs,
+                                       uint8_t* out, int64_t cx, int64_t cy, int64_t cz, int64_t dim_x,
+                                       int64_t dim_y, int64_t dim_z, int64_t n_classes, int64_t terms, void* stream);
+/* U1n region_uncertainty_nodes: out[r, v] = u_r(sums[row(svs[v]), :]) over the n_vox voxels of a partitioning,
+ *   row() as gts_project_argmax_i16 resolves an id against n_rows table rows (<= 32768); a background voxel gets
+ *   0 in all three maps.  out is uint8 [3, n_vox], written everywhere. */
+int32_t gts_region_uncertainty_nodes_u8(const int16_t* svs, const float* sums, uint8_t* out, int64_t n_vox,
+                                        int64_t n_rows, int64_t n_classes, int64_t terms, void* stream);
+/* U2 uncertainty_histogram: one pass over pred / truth (int16 internal labels, n each) and unc (uint8 [3, n], the
+ *   three region maps).  hist is int64 [4][4][GTS_UNCERTAINTY_BINS], ADDED to (the caller zeroes it): blocks 0..2
+ *   are the regions, each [outcome: 0 TP, 1 FP, 2 FN, 3 TN of the region masks][map value], bin 101 collecting
+ *   every value above 100; hist[3][0][0] counts the voxels with a label outside 0..3 on either side, which are
+ *   counted nowhere else.  Integer sums: independent of launch geometry.  0 <= n <= 2^40, else GTS_ERR_SHAPE. */
+#define GTS_UNCERTAINTY_BINS 102
+#define GTS_UNCERTAINTY_HIST_WORDS 1632
+int32_t gts_uncertainty_histogram(const int16_t* pred, const int16_t* truth, const uint8_t* unc, int64_t* hist,
+                                  int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
