@@ -176,6 +176,64 @@ __global__ __launch_bounds__(kBlock) void spmm_max_bwd_kernel(
   }
 }
 
+// K2 over a gradient that is never stored: gout = g [n, 4] @ w [4, 256] (the g @ W_neigh of a 4-class top layer, which
+// the 16x16x4 panels used to write as 1 KiB rows that hold 16 bytes of information and K2 to read back).  The same walk as
+// spmm_max_bwd_kernel<4, 64, ARGB> with seq = 1 (one wave per source row, out-edges in chunks, the sum in edge order); a
+// lane keeps its four columns of the four weight rows for the whole kernel and forms an edge's gout values in registers
+// from the destination's 16-byte g row with the roundings the GEMM has at K = 4: one fused multiply-add per k, in k order,
+// from +0.  That is what v_mfma_f32_16x16x4_f32 (one step per k, the other three lane quarters zero) and
+// v_mfma_f32_32x32x2_f32 (the tiles of short operands) both give, bit for bit; a separate multiply and add is not
+// (tests/test_gpu_narrow_ends.py holds the kernel to the stored product at sizes that reach either GEMM).
+constexpr int kLowRank = 4, kLowRankFeat = 256;
+
+template <int ARGB>
+__global__ __launch_bounds__(kBlock) void spmm_max_bwd_lowrank_kernel(
+    const int32_t* __restrict__ t_indptr, const int32_t* __restrict__ t_indices,
+    const int32_t* __restrict__ t_slot, const float* __restrict__ g, const float* __restrict__ w,
+    const void* __restrict__ arg, float* __restrict__ gx, int n_src, int nt) {
+  constexpr int VEC = 4, LPR = kWave, R = kLowRank, F = kLowRankFeat;
+  const int u = owned_row<LPR>(0, 1, n_src);
+  if (u < 0) return;   // wave-uniform
+  const int c = VEC * (threadIdx.x & (kWave - 1));
+  Vec<VEC> wk[R];
+#pragma unroll
+  for (int k = 0; k < R; ++k) wk[k] = Vec<VEC>::load(w + k * F + c);
+  const int beg = t_indptr[u], end = t_indptr[u + 1];
+  float acc[VEC];
+#pragma unroll
+  for (int t = 0; t < VEC; ++t) acc[t] = 0.0f;
+  for_chunks<LPR>(beg, end, [&](auto cnt_c, int k) {
+    constexpr int CNT = decltype(cnt_c)::value;
+    const Chunk<LPR, CNT> dst(t_indices, k, end);
+    const Chunk<LPR, CNT> slt(t_slot, k, end);
+    Vec<R> gr[CNT];
+    int win[CNT][VEC];
+    int want[CNT];
+#pragma unroll
+    for (int j = 0; j < CNT; ++j) {
+      const size_t d = static_cast<size_t>(dst[j]);
+      want[j] = slt[j];
+      gr[j] = Vec<R>::load(g + d * R);
+      load_slots<VEC, ARGB>(arg, d * F + c, win[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < CNT; ++j) {
+#pragma unroll
+      for (int t = 0; t < VEC; ++t) {
+        float v = 0.0f;
+#pragma unroll
+        for (int q = 0; q < R; ++q) v = __builtin_fmaf(gr[j].v[q], wk[q].v[t], v);
+        acc[t] += (win[j][t] == want[j]) ? v : 0.0f;
+      }
+    }
+  });
+  Vec<VEC> o;
+#pragma unroll
+  for (int t = 0; t < VEC; ++t) o.v[t] = acc[t];
+  const size_t off = static_cast<size_t>(u) * F + c;
+  if (nt & 1) o.store_nt(gx + off); else o.store(gx + off);
+}
+
 // ------------------------------------------------------------------ K3/K4: sum family
 template <int VEC, int LPR, bool DIV_IN>
 __global__ __launch_bounds__(kBlock) void spmm_sum_kernel(
@@ -278,6 +336,26 @@ extern "C" int32_t gts_spmm_max_bwd_f32(const int32_t* t_indptr, const int32_t* 
     else
       spmm_max_bwd_kernel<VEC, LPR, 4><<<g.grid, kBlock, 0, st>>>(t_indptr, t_indices, t_slot, gout, arg, relu_src, gx, ns, nf, g.seq, nt);
   })
+  return launch_status();
+}
+
+extern "C" int32_t gts_spmm_max_bwd_lowrank_f32(const int32_t* t_indptr, const int32_t* t_indices,
+                                                const int32_t* t_slot, const float* g, const float* w,
+                                                const void* arg, int32_t arg_bytes, float* gx, int64_t n_src,
+                                                int64_t n_feat, int64_t rank, void* stream) {
+  using namespace gts;
+  if (!t_indptr || !g || !w || !arg || !gx) return GTS_ERR_NULL;
+  if (bad_shape(n_src, n_feat) || n_feat != kLowRankFeat || rank != kLowRank) return GTS_ERR_SHAPE;
+  if (arg_bytes != 1 && arg_bytes != 4) return GTS_ERR_ARGKIND;
+  if (n_src == 0) return GTS_OK;
+  const int nt = g_spmm_nt < 0 ? 0 : g_spmm_nt;   // as K2
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const unsigned grid = static_cast<unsigned>((n_src + kWavesPerBlock - 1) / kWavesPerBlock);   // one wave per source row
+  const int ns = static_cast<int>(n_src);
+  if (arg_bytes == 1)
+    spmm_max_bwd_lowrank_kernel<1><<<grid, kBlock, 0, st>>>(t_indptr, t_indices, t_slot, g, w, arg, gx, ns, nt);
+  else
+    spmm_max_bwd_lowrank_kernel<4><<<grid, kBlock, 0, st>>>(t_indptr, t_indices, t_slot, g, w, arg, gx, ns, nt);
   return launch_status();
 }
 

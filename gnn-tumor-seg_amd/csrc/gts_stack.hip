@@ -76,6 +76,7 @@ struct BwdPlan {
   int64_t g[kMaxLayers], gp[kMaxLayers];   // g[i] (i >= 1): gradient w.r.t. layer i-1's pre-activation output; gp[i]: w.r.t. fc_pool's
   int64_t gm[2];
   int64_t workspace, workspace_bytes;
+  bool first_fused;                        // layer 0 is 4 -> 256: its backward streams g once (gts_sage_first_layer_bwd_f32)
   int64_t counters;                        // unit counters of the clustered K2 launches (as FwdPlan::counters)
   int64_t total;
 };
@@ -124,6 +125,10 @@ inline BwdPlan plan_backward(int64_t n, const int64_t* w, int n_layers) {
     for (const auto& grp : wgrads.groups)
       for (int first = 0; first < grp.count(); first += gts::kMaxProblems)
         ws = std::max(ws, gts_linear_bwd_weight_workspace(n, grp.rows, grp.cols, std::min(gts::kMaxProblems, grp.count() - first)));
+  // ... and the chunk partials of both narrow weight gradients of a 4 -> 256 first layer, side by side
+  const int64_t first = n > 0 ? gts_sage_first_layer_bwd_workspace(n, w[1], w[0], w[0]) : 0;
+  p.first_fused = first > 0;
+  ws = std::max(ws, first);
   p.workspace_bytes = ws;
   p.workspace = take(ws);
   p.counters = take(4 * GTS_CLUSTER_COUNTER_WORDS);
@@ -316,13 +321,25 @@ extern "C" int32_t gts_sage_pool_stack_bwd_f32(const int32_t* t_indptr, const in
     const float* h = input_of(i);
     const float* m = act(fwd.m[i]);
     const void* arg = acts + fwd.arg[i];
-    if (gm == nullptr) {
+    const bool fused = i == 0 && plan.first_fused && gm == nullptr;
+    // a 256 -> 4 top layer with one-byte winners: K2 forms the rows of g @ W_neigh in registers, the product is never stored
+    const bool lowrank = i == n_layers - 1 && gm == nullptr && fout == 4 && fin == 256 && arg_bytes == 1;
+    if (fused) {
+      // g @ W_neigh and the fc_self / bias / fc_neigh gradients in one pass over g (no weight gradient has been launched
+      // yet: the workspace is free)
+      float* buf = f32(plan.gm[cur]);
+      GTS_TRY(gts_sage_first_layer_bwd_f32(g, h, m, w_neigh, buf, grads[2], grads[4], grads[3], f32(plan.workspace),
+                                           plan.workspace_bytes, n_rows, fout, fin, fin, stream));
+      gm = buf;
+    } else if (gm == nullptr && !lowrank) {
       float* buf = f32(plan.gm[cur]);
       GTS_TRY(igrad(g, w_neigh, wt(i, 2), fout, nullptr, nullptr, nullptr, 0, nullptr, nullptr, buf, fin, wtp(i, 2), nullptr));
       gm = buf;
     }
     float* gp = f32(plan.gp[i]);   // ReLU'(p) is already in the winner record
-    if (sched_rec != nullptr && fin == 256 && arg_bytes == 1 && n_rows * 1024 < (1LL << 32)) {
+    if (lowrank) {
+      GTS_TRY(gts_spmm_max_bwd_lowrank_f32(t_indptr, t_indices, t_slot, g, w_neigh, arg, arg_bytes, gp, n_rows, fin, fout, stream));
+    } else if (sched_rec != nullptr && fin == 256 && arg_bytes == 1 && n_rows * 1024 < (1LL << 32)) {
       GTS_TRY(gts_spmm_max_bwd_cluster_f32(sched_rec, sched_clusters, sched_rows, sched_srcs, sched_loc_words, gm, arg, 1, gp,
                                            n_rows, fin, counters, stream));
     } else {
@@ -330,8 +347,10 @@ extern "C" int32_t gts_sage_pool_stack_bwd_f32(const int32_t* t_indptr, const in
     }
     gm = nullptr;
     wgrads.add(fin, fin, gp, h, grads[5 * i], grads[5 * i + 1]);        // fc_pool.weight, fc_pool.bias
-    wgrads.add(fout, fin, g, h, grads[5 * i + 2], grads[5 * i + 4]);    // fc_self.weight, bias
-    wgrads.add(fout, fin, g, m, grads[5 * i + 3], nullptr);             // fc_neigh.weight
+    if (!fused) {
+      wgrads.add(fout, fin, g, h, grads[5 * i + 2], grads[5 * i + 4]);    // fc_self.weight, bias
+      wgrads.add(fout, fin, g, m, grads[5 * i + 3], nullptr);             // fc_neigh.weight
+    }
     if (i > 0) {   // h is layer i-1's ReLU output: its backward is the mask h > 0
       const int64_t below_in = widths[i - 1];
       const uint64_t* hbits = fwd.bits[i - 1] >= 0 ? reinterpret_cast<const uint64_t*>(acts + fwd.bits[i - 1]) : nullptr;

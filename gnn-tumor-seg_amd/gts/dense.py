@@ -429,6 +429,34 @@ def linear_bwd_weight(g, a, want_bias_grad=False):
     return linear_bwd_weight_multi([(g, a, want_bias_grad)])[0]
 
 
+def first_layer_bwd_applies(g, x, m0, w_neigh):
+    """The shapes gts_sage_first_layer_bwd_f32 takes: a 4 -> 256 first layer with rows (the stack's C plan decides alike)."""
+    return g.shape[0] > 0 and g.shape[1] == 256 and x.shape[1] == 4 and m0.shape[1] == 4 and tuple(w_neigh.shape) == (256, 4)
+
+
+def sage_first_layer_bwd(g, x, m0, w_neigh):
+    """(gm, gw_self, g_bias, gw_neigh) of a 4 -> 256 first SAGEConv('pool') layer in one pass over g [M, 256]: the bits of
+    linear_bwd_input(g, w_neigh), linear_bwd_weight(g, x, want_bias_grad=True) and linear_bwd_weight(g, m0)."""
+    if not first_layer_bwd_applies(_mat(g, "g"), _mat(x, "x"), _mat(m0, "m0"), _mat(w_neigh, "w_neigh")):
+        raise _lib.GtsError("sage_first_layer_bwd takes g [M, 256], x [M, 4], m0 [M, 4], w_neigh [256, 4] with M > 0")
+    _same(x.shape[0], g.shape[0], "rows of g / x")
+    _same(m0.shape[0], g.shape[0], "rows of g / m0")
+    g, x, m0, w_neigh = _dense(g, x, m0, w_neigh)
+    dev = _operands(g, x, m0, w_neigh)
+    m = g.shape[0]
+    gm = torch.empty((m, 4), dtype=torch.float32, device=dev)
+    gw_self, gw_neigh = (torch.empty((256, 4), dtype=torch.float32, device=dev) for _ in range(2))
+    g_bias = torch.empty(256, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    nbytes = lib.gts_sage_first_layer_bwd_workspace(m, 256, 4, 4)
+    ws = _gemm_ws.get(dev, nbytes)
+    # not bracketed by GEMM_TIMER: a stream over g, no launch of the kinds that timer sets against the MFMA peak
+    check(lib.gts_sage_first_layer_bwd_f32(ptr(g), ptr(x), ptr(m0), ptr(w_neigh), ptr(gm), ptr(gw_self), ptr(g_bias),
+                                           ptr(gw_neigh), ptr(ws), ws.numel() * 4, m, 256, 4, 4, current_stream()),
+          "gts_sage_first_layer_bwd_f32")
+    return gm, gw_self, g_bias, gw_neigh
+
+
 def relu_bwd(g, out):
     """g * (out > 0) where `out` is the ReLU output (new tensor; g is left untouched)."""
     return g * (out > 0)

@@ -255,13 +255,26 @@ class _SagePoolStack(torch.autograd.Function):
         for i in reversed(range(n)):
             h, m, arg, hbits = acts[4 * i:4 * i + 4]
             w_pool, _b_pool, w_self, w_neigh, _bias = params[5 * i:5 * i + 5]
-            if gm is None:
+            # The narrow-end passes are neither a GEMM launch nor a K2 launch of the kinds bench.py's instrumented block
+            # brackets (GEMM_TIMER kinds against the MFMA peak, "spmm_max_bwd_f256" against its own bytes): that block keeps
+            # the launches those kinds are defined over — the same bits either way (tests/test_gpu_narrow_ends.py).
+            narrow = gm is None and not ops.INSTRUMENTED
+            fused = narrow and i == 0 and dense.first_layer_bwd_applies(g, h, m, w_neigh)
+            if fused:
+                # a 4 -> 256 first layer: g @ W_neigh and the fc_self / bias / fc_neigh gradients in one pass over g
+                gm, grads[2], grads[4], grads[3] = dense.sage_first_layer_bwd(g, h, m, w_neigh)
+            elif narrow and i == n - 1 and ops.lowrank_bwd_applies(g, w_neigh, arg):
+                # a 256 -> 4 top layer: K2 forms the rows of g @ W_neigh in registers, the [N, 256] product is never stored
+                gp = ops.spmm_max_bwd_lowrank(ctx.g, g, w_neigh, arg)
+            elif gm is None:
                 gm = igrad(g, w_neigh)
-            gp = ops.spmm_max_bwd(ctx.g, gm, arg)       # ReLU'(p) is already in the winner record
+            if gm is not None:
+                gp = ops.spmm_max_bwd(ctx.g, gm, arg)   # ReLU'(p) is already in the winner record
             gm = None
             defer(gp, h, 5 * i, 5 * i + 1)              # fc_pool.weight, fc_pool.bias
-            defer(g, h, 5 * i + 2, 5 * i + 4)           # fc_self.weight, bias
-            defer(g, m, 5 * i + 3, None)                # fc_neigh.weight
+            if not fused:
+                defer(g, h, 5 * i + 2, 5 * i + 4)       # fc_self.weight, bias
+                defer(g, m, 5 * i + 3, None)            # fc_neigh.weight
             if i > 0:      # h is layer i-1's ReLU output: its backward is the mask h > 0
                 below = params[5 * (i - 1) + 3]          # W_neigh of the layer below
                 if all(id(w) in turned for w in (w_self, w_pool, below)) and _chainable(g, w_self.t(), gp, below.t()):

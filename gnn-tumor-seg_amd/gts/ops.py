@@ -114,6 +114,33 @@ def spmm_max_bwd(g, gout, arg, relu_src=None):
     return gx
 
 
+def lowrank_bwd_applies(grad, w, arg):
+    """The shapes gts_spmm_max_bwd_lowrank_f32 takes in the layer stack: a 256 -> 4 top layer with one-byte winners (the
+    stack's C plan decides alike)."""
+    return grad.shape[1] == 4 and tuple(w.shape) == (4, 256) and arg.element_size() == 1
+
+
+def spmm_max_bwd_lowrank(g, grad, w, arg):
+    """spmm_max_bwd(g, linear_bwd_input(grad, w), arg) for grad [N, 4], w [4, 256] without storing the [N, 256] product:
+    the same bits.  Not bracketed as "spmm_max_bwd_f256": it moves a quarter of that kernel's bytes."""
+    grad, w = grad.contiguous(), w.contiguous()
+    f32(grad, w)
+    require_device(grad, w, arg)
+    d = g.dev()
+    n = g.n
+    if grad.dim() != 2 or grad.shape != (n, 4) or tuple(w.shape) != (4, 256):
+        raise _lib.GtsError(f"spmm_max_bwd_lowrank takes a gradient [graph nodes = {n}, 4] and weights [4, 256], "
+                            f"got {tuple(grad.shape)} and {tuple(w.shape)}")
+    expect(arg, (n, 256), "arg")
+    if arg.dtype != _ARG_DTYPE[g.arg_bytes]:
+        raise _lib.GtsError(f"arg dtype {arg.dtype} does not belong to this graph ({_ARG_DTYPE[g.arg_bytes]})")
+    gx = torch.empty((n, 256), dtype=torch.float32, device=grad.device)
+    check(_lib.load().gts_spmm_max_bwd_lowrank_f32(ptr(d.t_indptr), ptr(d.t_indices), ptr(d.t_slot), ptr(grad), ptr(w),
+                                                   ptr(arg), arg.element_size(), ptr(gx), n, 256, 4, current_stream()),
+          "gts_spmm_max_bwd_lowrank_f32")
+    return gx
+
+
 def spmm_sum_raw(g, x, transposed=False, div_in=None, div_out=None, add_self=False, accum=None):
     """K3/K4.  Generic sum reducer over the in-CSR (or the out-CSR when transposed); `accum` [N,F] is added
     to the result (a gradient that reached the rows by another path)."""

@@ -61,6 +61,15 @@ int32_t gts_spmm_max_bwd_f32(const int32_t* t_indptr, const int32_t* t_indices,
                              const int32_t* t_slot, const float* gout, const void* arg,
                              int32_t arg_bytes, const float* relu_src, float* gx,
                              int64_t n_src, int64_t n_feat, void* stream);
+/* K2 over a gradient of rank 4 that is never stored (the 4-class top layer of a SAGEConv('pool') stack,
+ * model/networks.py:28-30 under autograd: gout = g @ fc_neigh.weight):
+ *   gx = gts_spmm_max_bwd_f32(gout = gts_linear_bwd_input_t_f32(g, w^T), arg)     bit for bit, for
+ *   g [n_src, rank], w [rank, n_feat] as torch stores fc_neigh.weight, rank = 4, n_feat = 256 (else GTS_ERR_SHAPE).
+ * A lane forms gout[t_indices[e], f] in registers from the destination's 16-byte g row and its columns of w. */
+int32_t gts_spmm_max_bwd_lowrank_f32(const int32_t* t_indptr, const int32_t* t_indices,
+                                     const int32_t* t_slot, const float* g, const float* w, const void* arg,
+                                     int32_t arg_bytes, float* gx, int64_t n_src, int64_t n_feat,
+                                     int64_t rank, void* stream);
 
 /* ---- K1 / K2 over a cluster row schedule (F = 256): LDS-staged neighbour tiles ---------------
  * Same operators as gts_spmm_max_fwd_f32 / gts_spmm_max_bwd_f32 (DGL copy_u + max inside SAGEConv('pool'),
@@ -418,6 +427,19 @@ int32_t gts_linear_bwd_weight_f32(const float* const* g, const float* const* a, 
                                   float* const* gb, int32_t n_problems, float* workspace,
                                   int64_t workspace_bytes, int64_t m, int64_t n, int64_t k,
                                   void* stream);
+/* Backward of a 4-wide FIRST SAGEConv('pool') layer (model/networks.py:25-30: SAGEConv(in_feats, 256, 'pool') under
+ * autograd) in ONE pass over g [m, w], the gradient w.r.t. the layer's pre-activation output:
+ *   gm [m, s1]       = g @ w_neigh            exactly gts_linear_bwd_input_f32(g, w_neigh)          (w_neigh [w, s1] as stored)
+ *   gw_self [w, s0]  = g^T x, g_bias [w]      exactly gts_linear_bwd_weight_f32 of (g, x) with its bias
+ *   gw_neigh [w, s1] = g^T m0                 exactly gts_linear_bwd_weight_f32 of (g, m0)
+ * bit for bit: the three kernels behind those calls give a lane the same columns of a row, and this one keeps each one's
+ * arithmetic.  Takes w = 256 and s0 = s1 = 4 (x [m, 4] the layer's input, m0 [m, 4] its max-pooled neighbours); every other
+ * shape is GTS_ERR_SHAPE and keeps the calls above.  workspace >= gts_sage_first_layer_bwd_workspace(...) bytes (0 = shape
+ * not taken), caller-owned scratch for the chunk partials of the two weight gradients. */
+int64_t gts_sage_first_layer_bwd_workspace(int64_t m, int64_t w, int64_t s0, int64_t s1);
+int32_t gts_sage_first_layer_bwd_f32(const float* g, const float* x, const float* m0, const float* w_neigh, float* gm,
+                                     float* gw_self, float* g_bias, float* gw_neigh, float* workspace,
+                                     int64_t workspace_bytes, int64_t m, int64_t w, int64_t s0, int64_t s1, void* stream);
 
 /* ---- a whole stack of SAGEConv('pool') layers in one call each way -------------------------------
  * Replaces the layer loop of GraphSage.forward (model/networks.py:32-36: `for layer in self.layers: h = layer(graph, h)`)
@@ -432,7 +454,9 @@ int32_t gts_linear_bwd_weight_f32(const float* const* g, const float* const* a, 
  *   relu_bits: 1 = the forward GEMMs record the ReLU masks as bits (where gts_relu_bits_pay says so) and the backward reads
  *          them; 0 = the backward reads the masks from the saved activations.  The same value in all four calls of a step.
  *   Which launches are chained (consecutive GEMMs in one) and which weights the backward reads transposed is decided by
- *   shape alone: widths <= 256 chain, weights with >= 128 columns are transposed once per backward call.
+ *   shape alone: widths <= 256 chain, weights with >= 128 columns are transposed once per backward call; the backward of a
+ *   4 -> 256 first layer goes through gts_sage_first_layer_bwd_f32, that of a 256 -> 4 top layer with one-byte winners
+ *   through gts_spmm_max_bwd_lowrank_f32 (same bits as the calls they stand for).
  * Forward: everything it produces lives in `arena` (>= gts_sage_pool_stack_fwd_arena(...) bytes, which also reports the
  * byte offsets: offsets[4 i .. 4 i + 3] = max-pooled features m_i [n, w_i], winners arg_i [n, w_i] (arg_bytes each; -1
  * when not training), output out_i [n, w_{i+1}] (the next layer's input; the last one holds the logits), ReLU bits of out_i
