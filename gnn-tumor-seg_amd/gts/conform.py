@@ -133,6 +133,25 @@ def plan_for_modalities(affines, shapes):
     return plan(first, shapes[0])
 
 
+def conformed_affine(plan, affine):
+    """The 4x4 that takes an index (i, j, k) of the conformed volume to world mm, for the scan whose header holds
+    `affine` and whose Plan is `plan`.  Conformed axis w reads input axis j = plan.source[w] at i / spacing[j], or at
+    (n_j - 1) - i / spacing[j] when the axis is reversed (forward_tables); the scan's own affine does the rest."""
+    affine = np.asarray(affine, dtype=np.float64)
+    if affine.shape != (4, 4):
+        raise ValueError(f"conformed_affine takes a 4x4 affine, got {affine.shape}")
+    to_input = np.zeros((4, 4), dtype=np.float64)
+    to_input[3, 3] = 1.0
+    for w in range(3):
+        j = plan.source[w]
+        if plan.flips[j]:
+            to_input[j, w] = -1.0 / plan.spacing[j]
+            to_input[j, 3] = float(plan.shape[j] - 1)
+        else:
+            to_input[j, w] = 1.0 / plan.spacing[j]
+    return affine @ to_input
+
+
 # ---- device side -------------------------------------------------------------------------------------------------
 
 _DTYPE_CODES = {"torch.int16": 4, "torch.float32": 16}

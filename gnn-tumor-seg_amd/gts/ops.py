@@ -1134,3 +1134,81 @@ def weighted_cross_entropy_stats(logits, labels, class_w=None):
     data-parallel step, which normalises by the global denominator after the all-reduce)."""
     _, total, stats = _WeightedCE.apply(logits, labels, class_w)
     return total, stats
+
+
+# ---------------------------------------------------------------- co-registration (DESIGN.md 4v)
+REGISTER_MAX_MATRICES = _lib.const("GTS_REGISTER_MAX_MATRICES")
+REGISTER_BINS = (16, 32, 64)
+RESAMPLE_AUTO, RESAMPLE_PLAIN, RESAMPLE_TILED = 0, 1, 2
+_VOLUME_CODES = {torch.int16: 4, torch.float32: 16}
+
+
+def _moving_volume(volume, what):
+    if not isinstance(volume, torch.Tensor) or volume.dim() != 3 or volume.numel() == 0:
+        raise _lib.GtsError(f"{what} takes a non-empty [Z, Y, X] tensor")
+    if volume.dtype not in _VOLUME_CODES:
+        raise _lib.GtsError(f"{what}: dtype {volume.dtype} is not supported (int16 or float32)")
+    require_device(volume)
+    return _VOLUME_CODES[volume.dtype]
+
+
+def _matrices_arg(matrices, what):
+    """Row-major 3 x 4 (or 4 x 4, last row dropped) float64 matrices as the host doubles R1 / R2 read: [K, 12]."""
+    import numpy as np
+
+    m = np.asarray(matrices, dtype=np.float64)
+    if m.ndim >= 2 and m.shape[-2:] == (4, 4):
+        m = m[..., :3, :]
+    if m.size == 0 or m.size % 12 or not np.all(np.isfinite(m)):
+        raise _lib.GtsError(f"{what} takes finite 3 x 4 matrices, got an array of shape {m.shape}")
+    return np.ascontiguousarray(m.reshape(-1, 12))
+
+
+def affine_resample(volume, matrix, out_shape, out=None, path=RESAMPLE_AUTO):
+    """R1.  float32 [OZ, OY, OX]: `volume` ([Z, Y, X] int16 or float32, x fastest) sampled trilinearly where the 3 x 4
+    float64 `matrix` sends the output voxel index (x, y, z); 0 outside (include/gts_hip.h).  out_shape = (OX, OY, OZ).
+    out: a contiguous float32 tensor of that shape to write (a channel slice of a scan).  path: RESAMPLE_AUTO, or one
+    of the two lane maps forced (same bits)."""
+    code = _moving_volume(volume, "affine_resample")
+    ox, oy, oz = (int(n) for n in out_shape)
+    m = _matrices_arg(matrix, "affine_resample")
+    if len(m) != 1:
+        raise _lib.GtsError(f"affine_resample takes one matrix, got {len(m)}")
+    if out is None:
+        out = torch.empty((oz, oy, ox), dtype=torch.float32, device=volume.device)
+    else:
+        f32(out)
+        expect(out, (oz, oy, ox), "out")
+        require_device(volume, out)
+    z, y, x = (int(n) for n in volume.shape)
+    check(_lib.load().gts_affine_resample(ptr(volume), code, x, y, z, m.ctypes.data, ox, oy, oz, ptr(out), int(path),
+                                          current_stream()), "gts_affine_resample")
+    return out
+
+
+def joint_histogram(fixed, moving, matrices, stride, bins, ranges, grid_blocks=0):
+    """R2.  int64 [K, bins * bins + 1] on the device: for each of the K 3 x 4 float64 `matrices` (fixed voxel index ->
+    moving voxel coordinates) the joint histogram of `fixed` (float32 [FZ, FY, FX]) and the trilinearly sampled
+    `moving` ([Z, Y, X] int16 or float32) over the fixed voxels whose indices are multiples of `stride`; the last entry
+    of a row counts the samples outside the moving volume.  ranges = (lo_f, scale_f, lo_m, scale_m): bin = clamp(floor(
+    (v - lo) * scale), 0, bins - 1), a non-finite value goes to bin 0.  grid_blocks: workgroups (0: the library's
+    choice); the counts do not depend on it."""
+    code = _moving_volume(moving, "joint_histogram")
+    if not isinstance(fixed, torch.Tensor) or fixed.dim() != 3 or fixed.numel() == 0:
+        raise _lib.GtsError("joint_histogram takes a non-empty fixed volume [FZ, FY, FX]")
+    f32(fixed)
+    require_device(fixed, moving)
+    m = _matrices_arg(matrices, "joint_histogram")
+    k = len(m)
+    if k > REGISTER_MAX_MATRICES:
+        raise _lib.GtsError(f"joint_histogram takes 1..{REGISTER_MAX_MATRICES} matrices, got {k}")
+    if int(bins) not in REGISTER_BINS or int(stride) != stride or stride < 1:
+        raise _lib.GtsError(f"joint_histogram: bins in {REGISTER_BINS} and a whole stride >= 1, got {bins!r}, {stride!r}")
+    lo_f, scale_f, lo_m, scale_m = (float(v) for v in ranges)
+    counts = torch.empty((k, int(bins) ** 2 + 1), dtype=torch.int64, device=fixed.device)
+    fz, fy, fx = (int(n) for n in fixed.shape)
+    z, y, x = (int(n) for n in moving.shape)
+    check(_lib.load().gts_joint_histogram(ptr(fixed), fx, fy, fz, ptr(moving), code, x, y, z, m.ctypes.data, k,
+                                          int(stride), int(bins), lo_f, scale_f, lo_m, scale_m, ptr(counts),
+                                          int(grid_blocks), current_stream()), "gts_joint_histogram")
+    return counts

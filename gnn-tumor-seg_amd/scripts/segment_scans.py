@@ -15,7 +15,9 @@ A scan that raises is reported and skipped; the exit status is 1 when any scan w
 
     python -m scripts.segment_scans -d INPUT -o OUT -g GNN.pt [-c CNN.pt] [-m GSpool] [-n 15000 -b 0.5 -k 10]
                                     [--min_component_voxels N --connectivity {6,26} --min_enhancing_voxels T]
-                                    [--conform]
+                                    [--conform] [--coregister [MODALITY] [--coregister_header_only]
+                                     --coregister_levels S [S ...] --coregister_bins {16,32,64}
+                                     --coregister_max_rotate DEG --coregister_report FILE.json]
                                     [--also_gnn_weights P [P ...] --also_cnn_weights P [P ...]] [--tta_mirror AXES]
                                     [--uncertainty_dir DIR]
 
@@ -48,6 +50,17 @@ grid (nearest neighbour) and OUT/{id}.nii.gz has the scan's own shape and the fi
 clean-up flags then count voxels of 1 mm^3.  The modalities of a scan must share one shape and agree in their
 affines to 1e-3, else the scan is skipped.  Without the flag headers are not read: scans are taken as BraTS-shaped
 LPS 1 mm volumes and written with the BraTS affine, as before.
+
+--coregister [MODALITY] (implies --conform) lifts that last condition: the modalities of a scan may lie on different
+grids and the patient may have moved between the series (gts.register).  MODALITY is the extension of
+the reference modality (default: the first).  It is conformed as --conform conforms it; every other modality is
+resampled from its own grid straight into that frame through the two header affines, one trilinear interpolation on
+the device, after a six-parameter rigid refinement that maximises the mutual information with the reference
+(--coregister_header_only skips the refinement; --coregister_levels are the sample strides of the search's levels,
+--coregister_bins the histogram's bins per side, --coregister_max_rotate the bound on each rotation in degrees).
+The labels go back onto the reference modality's grid with its affine.  --coregister_report FILE.json writes the
+parameters, scores and launch counts found per scan and modality; the scan's line of output names the largest
+translation and rotation.
 """
 import argparse
 import os
@@ -65,7 +78,7 @@ from data_processing import nifti_io, standardization  # noqa: E402
 from data_processing.image_processing import (uncrop_maps_to_brats_size, uncrop_to_brats_size,  # noqa: E402
                                               uncrop_to_shape)
 from data_processing.labels import INTERNAL_TO_BRATS  # noqa: E402
-from gts import conform, graphgen, intake, ops  # noqa: E402
+from gts import conform, graphgen, intake, ops, register  # noqa: E402
 from scripts import cleanup as cleanup_flags  # noqa: E402
 from scripts import ensemble_flags  # noqa: E402
 from scripts import preprocess_dataset as prep  # noqa: E402
@@ -97,7 +110,43 @@ def build_parser():
     parser.add_argument("--conform", action="store_true",
                         help="read each scan's orientation and voxel spacing from its headers, segment it in the "
                              "LPS 1 mm frame and write the labels on the scan's own grid with its own affine")
+    parser.add_argument("--coregister", nargs="?", const="", default=None, metavar="MODALITY",
+                        help="co-register the modalities of each scan onto this one (its extension; default: the "
+                             "first) on the device: header alignment plus a rigid mutual-information refinement.  "
+                             "Implies --conform")
+    parser.add_argument("--coregister_header_only", action="store_true",
+                        help="with --coregister: align by the headers alone, no rigid refinement")
+    parser.add_argument("--coregister_levels", nargs="+", type=int, default=list(register.DEFAULT_LEVELS),
+                        metavar="S", help="sample strides of the search's levels, coarse to fine")
+    parser.add_argument("--coregister_bins", type=int, choices=(16, 32, 64), default=register.DEFAULT_BINS,
+                        help="bins per side of the joint histogram")
+    parser.add_argument("--coregister_max_rotate", type=float, default=register.DEFAULT_MAX_ROTATE, metavar="DEG",
+                        help="bound on each rotation angle of the search")
+    parser.add_argument("--coregister_report", default=None, metavar="FILE.json",
+                        help="write the parameters, scores and launch counts found per scan and modality")
     return ensemble_flags.add_flags(cleanup_flags.add_flags(parser))
+
+
+def parse_args(argv=None):
+    """The parsed flags, --coregister resolved: it turns --conform on and names the reference modality's index
+    (args.coregister_ref; None without the flag).  Raises ValueError for flags that do not go together."""
+    args = build_parser().parse_args(argv)
+    args.coregister_ref = None
+    if args.coregister is None:
+        if args.coregister_header_only or args.coregister_report:
+            raise ValueError("--coregister_header_only and --coregister_report need --coregister")
+        return args
+    args.conform = True
+    if args.coregister == "":
+        args.coregister_ref = 0
+    elif args.coregister in args.modality_extensions:
+        args.coregister_ref = args.modality_extensions.index(args.coregister)
+    else:
+        raise ValueError(f"--coregister {args.coregister!r} is none of the modality extensions "
+                         f"{args.modality_extensions}")
+    if any(s < 1 for s in args.coregister_levels) or not args.coregister_max_rotate >= 0:
+        raise ValueError("--coregister_levels are strides >= 1 and --coregister_max_rotate is not negative")
+    return args
 
 
 def find_inputs(data_dir, modality_exts, prefix=""):
@@ -128,6 +177,8 @@ class Segmenter:
         self.k = args.num_neighbors or 0
         self.cleanup = cleanup_flags.from_args(args)       # None with the flags at their defaults
         self.conform = bool(getattr(args, "conform", False))
+        self.coregister_ref = getattr(args, "coregister_ref", None)     # None: the modalities share one grid
+        self.coregister_report = {}                                     # scan id -> per-modality findings
         if getattr(args, "stats", None):
             self.mean, self.std = standardization.load_stats(os.path.expanduser(args.stats), args.modality_extensions)
         else:
@@ -153,21 +204,47 @@ class Segmenter:
 
     def load(self, folder):
         """Host stage: decode the modalities and stage them for the upload.  With --conform: (staged volumes, the
-        conform plan of their headers' geometry, the first modality's affine)."""
+        conform plan of their headers' geometry, the first modality's affine); with --coregister: (one staged volume
+        per modality, each on its own grid, None, every modality's affine)."""
         if not self.conform:
             return intake.stage_scan(nifti_io.read_in_patient_sample_raw(folder, self.args.modality_extensions))
         paths = nifti_io.find_modality_files(folder, self.args.modality_extensions)
         volumes = [nifti_io.read_nifti_raw(p) for p in paths]
         affines = [nifti_io.read_affine(p)[0] for p in paths]
+        if self.coregister_ref is not None:         # each modality keeps its own grid: (volumes, None, affines)
+            return [self._stage_volume(v) for v in volumes], None, affines
         plan = conform.plan_for_modalities(affines, [v.shape for v in volumes])
         return intake.stage_scan(volumes), plan, affines[0]
+
+    @staticmethod
+    def _stage_volume(volume):
+        """One [X, Y, Z] volume as the host tensor [Z, Y, X] in its stored dtype (int16 or float32, else float32)."""
+        volume = np.asarray(volume)
+        if volume.dtype not in (np.int16, np.float32):
+            volume = volume.astype(np.float32)
+        return torch.from_numpy(np.array(volume.T, order="C"))      # a copy: the decoded bytes are read-only
+
+    def align(self, loaded):
+        """With --coregister: load's triple -> (the scan [C, OZ, OY, OX] float32 in the reference modality's
+        conformed frame, its plan, the per-modality findings)."""
+        volumes, _, affines = loaded
+        a = self.args
+        return register.align_study([v.to(self.device, non_blocking=True) for v in volumes], affines,
+                                    self.coregister_ref, header_only=a.coregister_header_only,
+                                    levels=tuple(a.coregister_levels), bins=a.coregister_bins,
+                                    max_rotate=a.coregister_max_rotate)
 
     def segment(self, staged, timer=None):
         """Device stage: int16 label volume in BraTS coding, at BraTS size; with --conform (staged is load's
         triple) on the scan's own grid."""
         tick = timer or (lambda name: None)
         plan = None
-        if self.conform:
+        self.last_registration = None
+        if self.coregister_ref is not None:
+            staged, plan, self.last_registration = self.align(staged)
+            self.last_plan = plan                   # of the reference modality: run() describes it
+            tick("coregister")
+        elif self.conform:
             staged, plan, _ = staged
             staged = conform.conform_scan(staged.to(self.device, non_blocking=True), plan)
             tick("conform")
@@ -234,13 +311,19 @@ class Segmenter:
                     volume = self.segment(staged)
                     maps = self.last_uncertainty if self.uncertainty_dir else None
                     note = f" ({self.cleanup.report()})" if self.cleanup is not None else ""
-                    if self.conform:
+                    if self.coregister_ref is not None:
+                        self.coregister_report[scan_id] = self.last_registration
+                        note += f" ({self.last_plan.describe()}) ({self.registration_note()})"
+                    elif self.conform:
                         note += f" ({staged[1].describe()})"
                 except Exception as exc:
                     print(f"{scan_id}: skipped ({exc!r})")
                     failed.append(scan_id)
                     continue
-                affine = staged[2] if self.conform else nifti_io.BRATS_AFFINE
+                if self.coregister_ref is not None:
+                    affine = staged[2][self.coregister_ref]
+                else:
+                    affine = staged[2] if self.conform else nifti_io.BRATS_AFFINE
                 writes.append((scan_id, note, pool.submit(self.store, scan_id, volume, affine, maps)))
             for scan_id, note, job in writes:
                 try:
@@ -249,11 +332,34 @@ class Segmenter:
                 except Exception as exc:
                     print(f"{scan_id}: writing failed ({exc!r})")
                     failed.append(scan_id)
+        if getattr(self.args, "coregister_report", None):
+            import json
+
+            with open(os.path.expanduser(self.args.coregister_report), "w") as f:
+                json.dump({"reference": self.args.modality_extensions[self.coregister_ref],
+                           "modalities": list(self.args.modality_extensions), "scans": self.coregister_report}, f,
+                          indent=1)
+                f.write("\n")
         return failed
+
+    def registration_note(self):
+        """The largest translation and rotation found for the scan segment() saw last."""
+        found = [r["params"] for r in self.last_registration if not r["reference"]]
+        shift = max((float(np.linalg.norm(p[:3])) for p in found), default=0.0)
+        turn = max((float(np.max(np.abs(p[3:]))) for p in found), default=0.0)
+        how = "headers only" if self.args.coregister_header_only else "rigid"
+        note = f"coregister: {how}, largest translation {shift:.2f} mm, largest rotation {turn:.2f}°"
+        if found and not self.args.coregister_header_only and turn >= self.args.coregister_max_rotate > 0:
+            note += ", a rotation ran to its bound: check this scan"
+        return note
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    try:
+        args = parse_args(argv)
+    except ValueError as exc:
+        print(f"segment_scans: {exc}", file=sys.stderr)
+        return 2
     try:        # flags that do not go together: found here, before any scan is read or the GPU touched
         ensemble_flags.from_args(args, args.gnn_weights, args.cnn_weights)
     except ensemble_flags.FlagError as exc:

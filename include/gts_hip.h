@@ -1039,6 +1039,36 @@ int32_t gts_region_uncertainty_nodes_u8(const int16_t* svs, const float* sums, u
 int32_t gts_uncertainty_histogram(const int16_t* pred, const int16_t* truth, const uint8_t* unc, int64_t* hist,
                                   int64_t n, void* stream);
 
+/* ---- R1/R2: co-register modalities that lie on different grids (no counterpart in the reference) --
+ * A MOVING volume [Z][Y][X] (x fastest), dtype by its NIfTI code 4 (int16) or 16 (float32), else GTS_ERR_ARGKIND,
+ * is sampled where a row-major 3 x 4 float64 matrix T (HOST memory, read at the call) sends the voxel index
+ * (x, y, z) of another grid:
+ *   u = ((T00 x + T01 y) + T02 z) + T03, v and w likewise from rows 1 and 2, in float64 without contraction;
+ *   the sample is inside when 0 <= u <= X-1, 0 <= v <= Y-1 and 0 <= w <= Z-1 (a NaN coordinate is outside);
+ *   inside: i0 = min(floor(u), X-1), i1 = min(i0 + 1, X-1), t = u - i0 per axis, the eight neighbours as float64,
+ *   lerped along x, then y, then z, each lerp a + (b - a) * t and t == 0 giving a itself (gts_conform_gather's).
+ * Every extent in [1, 65535] and every volume below 2^31 voxels, else GTS_ERR_SHAPE; a matrix entry that is not
+ * finite: GTS_ERR_ARGKIND.  Nothing is launched for a rejected argument.
+ * gts_affine_resample (R1): dst float32 [OZ][OY][OX] = that value rounded once, 0.0f outside.  path 0 picks the
+ *   map of lanes to voxels (plain when |T00| is the largest of |T00|, |T10|, |T20|, else a 64 x 64 LDS tile whose
+ *   reads run along the input's x), 1 forces the plain map, 2 the tiled one; all give the same bits for every T.
+ * gts_joint_histogram (R2): `fixed` is float32 [FZ][FY][FX]; matrices HOST float64 [K][12], 1 <= K <=
+ *   GTS_REGISTER_MAX_MATRICES; for every fixed voxel whose x, y and z are multiples of stride (>= 1) and every
+ *   matrix k, with f the fixed value and m the moving value (float64, not rounded):
+ *     outside: counts[k][B*B] += 1;   inside: counts[k][bin(f, lo_f, scale_f) * B + bin(m, lo_m, scale_m)] += 1,
+ *     bin(v, lo, scale) = 0 when v is not finite (tested as v - v == 0.0), else with q = floor((v - lo) * scale):
+ *     q >= 1 ? (q < B-1 ? (int)q : B-1) : 0, so a NaN q gives 0 as well.
+ *   counts is int64 [K][B*B + 1], zeroed by the call; B = bins in {16, 32, 64}, else GTS_ERR_ARGKIND, as are range
+ *   values that are not finite.  Integer LDS tables and integer global atomics only: the counts do not depend on
+ *   grid_blocks (0: chosen by the library; tests pass small and large ones) or on any order of arrival. */
+#define GTS_REGISTER_MAX_MATRICES 16
+int32_t gts_affine_resample(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, const double* matrix,
+                            int64_t OX, int64_t OY, int64_t OZ, float* dst, int32_t path, void* stream);
+int32_t gts_joint_histogram(const float* fixed, int64_t FX, int64_t FY, int64_t FZ, const void* moving, int32_t dtype,
+                            int64_t X, int64_t Y, int64_t Z, const double* matrices, int64_t K, int64_t stride,
+                            int64_t bins, double lo_f, double scale_f, double lo_m, double scale_m, int64_t* counts,
+                            int64_t grid_blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
