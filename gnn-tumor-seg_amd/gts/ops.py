@@ -1212,3 +1212,139 @@ def joint_histogram(fixed, moving, matrices, stride, bins, ranges, grid_blocks=0
                                           int(stride), int(bins), lo_f, scale_f, lo_m, scale_m, ptr(counts),
                                           int(grid_blocks), current_stream()), "gts_joint_histogram")
     return counts
+
+
+# ---------------------------------------------------------------- bias-field correction
+BIAS_BINS = _lib.const("GTS_BIAS_BINS")
+BIAS_MAX_SPANS = _lib.const("GTS_BIAS_MAX_SPANS")
+
+
+class BiasTables:
+    """The device operands Z2-Z5 share for one volume shape (X, Y, Z) and one lattice set: the B-spline weights and
+    cells of every axis index at every level (float64 / int32 arrays laid out as include/gts_hip.h says; gts.bias.tables
+    builds them), per level the fit weights of Z4, and the kernels' workspace."""
+
+    def __init__(self, shape, spans0, levels, weights, cells, fit, device):
+        import numpy as np
+
+        self.shape = tuple(int(n) for n in shape)
+        self.spans0, self.levels = int(spans0), int(levels)
+        if self.spans0 < 1 or self.levels < 1 or self.spans0 << (self.levels - 1) > BIAS_MAX_SPANS:
+            raise _lib.GtsError(f"bias lattices: spans0 {spans0} and levels {levels} give more than {BIAS_MAX_SPANS} "
+                                "spans, or none")
+        total = sum(self.shape)
+        weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        cells = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1)
+        if weights.size != self.levels * 4 * total or cells.size != self.levels * total or len(fit) != self.levels:
+            raise _lib.GtsError("bias tables do not match the shape and the number of levels")
+        nbytes = int(_lib.load().gts_bias_workspace(*self.shape, self.spans0 << (self.levels - 1)))
+        if nbytes < 0:
+            raise _lib.GtsError(f"volume {self.shape} is outside the kernels' limits (extent <= 65535, < 2^31 voxels)")
+        self.weights = torch.from_numpy(weights).to(device)
+        self.cells = torch.from_numpy(cells).to(device)
+        self.fit = []
+        for f in fit:
+            f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1)
+            if f.size != 8 * total:
+                raise _lib.GtsError("bias fit weights do not match the shape")
+            self.fit.append(torch.from_numpy(f).to(device))
+        self.ws = scratch(nbytes, device, torch.uint8)
+        self.device = self.weights.device
+
+    def points(self, level):
+        return (self.spans0 << level) + 3
+
+    def lattice_size(self):
+        return sum(self.points(level) ** 3 for level in range(self.levels))
+
+    def lattice_slice(self, level):
+        start = sum(self.points(k) ** 3 for k in range(level))
+        return slice(start, start + self.points(level) ** 3)
+
+
+def _bias_operands(u, tables, lattice, what, dtype=torch.float32):
+    if not isinstance(u, torch.Tensor) or u.dim() != 3 or tuple(u.shape) != tables.shape[::-1]:
+        raise _lib.GtsError(f"{what} takes a [Z, Y, X] tensor of the tables' shape {tables.shape[::-1]}")
+    if dtype is not None and u.dtype != dtype:
+        raise _lib.GtsError(f"{what}: dtype {u.dtype} is not supported ({dtype})")
+    if lattice.dtype != torch.float64 or lattice.numel() != tables.lattice_size():
+        raise _lib.GtsError(f"{what} takes the float64 lattices of every level, {tables.lattice_size()} entries")
+    require_device(u, lattice, tables.weights)
+    x, y, z = tables.shape
+    return (x, y, z, ptr(tables.weights), ptr(tables.cells), ptr(lattice), tables.spans0, tables.levels)
+
+
+def bias_log(volume, threshold=0.0):
+    """Z1.  (u, n): u float32 [Z, Y, X] = float32(log(float64(v))) where the volume ([Z, Y, X] int16 or float32) is
+    finite and above `threshold` (>= 0), NaN elsewhere; n, an int64 device tensor [1], counts the mask voxels."""
+    code = _moving_volume(volume, "bias_log")
+    u = torch.empty(volume.shape, dtype=torch.float32, device=volume.device)
+    count = torch.empty(1, dtype=torch.int64, device=volume.device)
+    z, y, x = (int(n) for n in volume.shape)
+    check(_lib.load().gts_bias_log(ptr(volume), code, x, y, z, float(threshold), ptr(u), ptr(count), current_stream()),
+          "gts_bias_log")
+    return u, count
+
+
+def bias_range(u, tables, lattice, grid_blocks=0):
+    """Z2.  float64 [2] on the device: min and max of d = float64(u) - field over the mask (the voxels where u is not
+    NaN); (+inf, -inf) for an empty mask."""
+    args = _bias_operands(u, tables, lattice, "bias_range")
+    out = torch.empty(2, dtype=torch.float64, device=u.device)
+    check(_lib.load().gts_bias_range(ptr(u), *args, ptr(out), ptr(tables.ws), tables.ws.numel(), int(grid_blocks),
+                                     current_stream()), "gts_bias_range")
+    return out
+
+
+def bias_histogram(u, tables, lattice, lo, hi, grid_blocks=0):
+    """Z3.  int64 [BIAS_BINS] on the device: the mask voxels by clamp(floor((d - lo) / w + 0.5), 0, BINS - 1), w = (hi -
+    lo) / (BINS - 1).  The counts do not depend on grid_blocks."""
+    args = _bias_operands(u, tables, lattice, "bias_histogram")
+    counts = torch.empty(BIAS_BINS, dtype=torch.int64, device=u.device)
+    check(_lib.load().gts_bias_histogram(ptr(u), *args, float(lo), float(hi), ptr(counts), int(grid_blocks),
+                                         current_stream()), "gts_bias_histogram")
+    return counts
+
+
+def bias_fit(u, tables, lattice, level, lo, hi, table, grid_blocks=0):
+    """Z4.  float64 [3, n, n, n] on the device (n = the level's control points per axis): num, den and delta = num /
+    den (0 where den == 0) of the B-spline fit of r = d - E(d) at `level`; `table` holds the BIAS_BINS sharpened values
+    E is linear between.  Bit-equal between runs and for every grid_blocks."""
+    import numpy as np
+
+    args = _bias_operands(u, tables, lattice, "bias_fit")
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    if table.shape != (BIAS_BINS,) or not 0 <= int(level) < tables.levels:
+        raise _lib.GtsError(f"bias_fit takes a table of {BIAS_BINS} values and a level below {tables.levels}")
+    n = tables.points(int(level))
+    out = torch.empty((3, n, n, n), dtype=torch.float64, device=u.device)
+    check(_lib.load().gts_bias_fit(ptr(u), *args, int(level), ptr(tables.fit[int(level)]), float(lo), float(hi),
+                                   table.ctypes.data, ptr(out), ptr(tables.ws), tables.ws.numel(), int(grid_blocks),
+                                   current_stream()), "gts_bias_fit")
+    return out
+
+
+def bias_mean(u, tables, lattice, grid_blocks=0):
+    """Z5.  float64 [3] on the device: the sum of the field over the mask, the mask's size, the mean (0 when empty)."""
+    args = _bias_operands(u, tables, lattice, "bias_mean")
+    out = torch.empty(3, dtype=torch.float64, device=u.device)
+    check(_lib.load().gts_bias_mean(ptr(u), *args, ptr(out), ptr(tables.ws), tables.ws.numel(), int(grid_blocks),
+                                    current_stream()), "gts_bias_mean")
+    return out
+
+
+def bias_apply(volume, tables, lattice, mean, want_field=False, out=None, grid_blocks=0):
+    """Z5.  float32 [Z, Y, X] = float32(float64(v) / exp(field - mean)) at every voxel of the volume (int16 or float32);
+    with want_field also float32(field - mean).  out: a contiguous float32 tensor to write (a channel of a scan)."""
+    code = _moving_volume(volume, "bias_apply")
+    args = _bias_operands(volume, tables, lattice, "bias_apply", dtype=None)
+    if out is None:
+        out = torch.empty(volume.shape, dtype=torch.float32, device=volume.device)
+    else:
+        f32(out)
+        expect(out, volume.shape, "out")
+        require_device(volume, out)
+    field = torch.empty(volume.shape, dtype=torch.float32, device=volume.device) if want_field else None
+    check(_lib.load().gts_bias_apply(ptr(volume), code, *args, float(mean), ptr(out), ptr(field), int(grid_blocks),
+                                     current_stream()), "gts_bias_apply")
+    return (out, field) if want_field else out

@@ -14,6 +14,10 @@ a small thread pool decodes the next ones.  A scan that raises is reported and l
 the exit status is 1 when any scan was left out.
 
     python -m scripts.compute_dataset_stats -d RAW_DIR -l _seg.nii.gz -o STATS.json
+
+--bias_correct (and the --bias_* settings, as scripts.segment_scans documents them) removes each modality's bias field
+on the device (gts.bias) before the statistics are taken, for datasets that are preprocessed and
+segmented with the same flag.
 """
 import argparse
 import os
@@ -44,7 +48,9 @@ def build_parser():
                         help="file suffix of the label volume (required: the statistics are taken over healthy tissue)")
     parser.add_argument("-p", "--data_prefix", default="", help="common prefix of the scan folders, e.g. BraTS2021")
     parser.add_argument("-o", "--output", default=None, type=str, help="the statistics file to write (JSON)")
-    return parser
+    from gts import bias
+
+    return bias.add_flags(parser)
 
 
 def check_request(modality_extensions, label_extension):
@@ -66,9 +72,11 @@ def load_scan(folder, modality_extensions, label_extension):
     return staged, dataset_stats.stage_labels(nifti_io.read_in_labels(folder, label_extension))
 
 
-def compute(scans, modality_extensions, label_extension, q=QUANTILE):
-    """Per-scan statistics of {id: folder}: ({id: ScanStats}, ids left out)."""
-    from gts import dataset_stats
+def compute(scans, modality_extensions, label_extension, q=QUANTILE, bias_settings=None, bias_report=None):
+    """Per-scan statistics of {id: folder}: ({id: ScanStats}, ids left out).  bias_settings: gts.bias.correct_volume's
+    settings, to correct every modality on the device first (None: the values as stored); bias_report, a dict,
+    receives the correction's per-modality reports by scan id."""
+    from gts import bias, dataset_stats, intake
 
     check_request(modality_extensions, label_extension)
     ids = sorted(scans)
@@ -83,6 +91,10 @@ def compute(scans, modality_extensions, label_extension, q=QUANTILE):
                 pending[i + READ_AHEAD] = submit(i + READ_AHEAD)
             try:
                 staged, labels = pending.pop(i).result()
+                if bias_settings is not None:
+                    staged, reports = bias.correct_scan(staged.to(intake._device(), non_blocking=True), **bias_settings)
+                    if bias_report is not None:
+                        bias_report[scan_id] = reports
                 per_scan[scan_id] = dataset_stats.scan_stats(staged, labels, q)
             except Exception as exc:
                 print(f"{scan_id}: left out ({exc!r})")
@@ -90,12 +102,13 @@ def compute(scans, modality_extensions, label_extension, q=QUANTILE):
     return per_scan, failed
 
 
-def compute_and_save(scans, modality_extensions, label_extension, path, q=QUANTILE):
+def compute_and_save(scans, modality_extensions, label_extension, path, q=QUANTILE, bias_settings=None,
+                     bias_report=None):
     """compute, then the medians into the file at path: (mean, std, ids left out).  StatsError when no
     scan gave statistics (nothing is written then)."""
     from gts import dataset_stats
 
-    per_scan, failed = compute(scans, modality_extensions, label_extension, q)
+    per_scan, failed = compute(scans, modality_extensions, label_extension, q, bias_settings, bias_report)
     if not per_scan:
         raise standardization.StatsError(f"none of the {len(scans)} scan(s) gave statistics")
     mean, std = dataset_stats.dataset_stats([per_scan[s] for s in sorted(per_scan)])
@@ -113,14 +126,24 @@ def main(argv=None):
         check_request(args.modality_extensions, args.label_extension)
     except standardization.StatsError as exc:
         parser.error(str(exc))
+    from gts import bias
+
+    try:
+        settings = bias.settings_from_args(args)
+    except ValueError as exc:
+        parser.error(str(exc))
+    report = {}
     scans = prep.find_scans(args.data_dir or Filepaths.INPUT_MRI_DIR, args.data_prefix)
     print(f"{len(scans)} scan folders found; statistics go to {args.output}")
     try:
         mean, std, failed = compute_and_save(scans, args.modality_extensions, args.label_extension,
-                                             os.path.expanduser(args.output))
+                                             os.path.expanduser(args.output), bias_settings=settings,
+                                             bias_report=report)
     except standardization.StatsError as exc:
         print(f"no statistics written: {exc}")
         return 1
+    if args.bias_report:
+        bias.save_report(args.bias_report, args.modality_extensions, settings, report)
     print(f"mean {mean.tolist()}, standard deviation {std.tolist()} over {len(scans) - len(failed)} scan(s), "
           f"{len(failed)} left out")
     return 1 if failed else 0

@@ -17,6 +17,11 @@ Standardization uses the reference's BraTS-2021 constants unless --stats is give
 the values of a file written by scripts.compute_dataset_stats; --stats compute takes them first over the
 input folder (needs -l), as the reference does when its constant is None, and writes
 OUT_DIR/standardization.json.
+
+--bias_correct (with --bias_levels, --bias_spans, --bias_iterations, --bias_tol, --bias_threshold, --bias_report, as
+scripts.segment_scans documents them) removes each modality's bias field on the device (gts.bias)
+before the crop, the normalization and, with --stats compute, the statistics: the graphs a model is trained on then
+see the correction that `segment_scans --bias_correct` applies to the scans it segments.
 """
 import argparse
 import glob
@@ -65,7 +70,9 @@ def build_parser():
     parser.add_argument("--stats", default=None, metavar="STATS.json|compute",
                         help="standardization statistics: a file of scripts.compute_dataset_stats, or 'compute' to take "
                              "them over the input folder first (default: the BraTS-2021 constants)")
-    return parser
+    from gts import bias
+
+    return bias.add_flags(parser)
 
 
 def default_output_dir(args):
@@ -89,6 +96,10 @@ class DataPreprocessor:
         self.scans = find_scans(args.data_dir or Filepaths.INPUT_MRI_DIR, args.data_prefix)
         self.all_ids = sorted(self.scans)
         self.stats_failed = []
+        from gts import bias
+
+        self.bias = bias.settings_from_args(args)       # None without --bias_correct
+        self.bias_report = {}
         self.mean, self.std = self.standardization_stats(getattr(args, "stats", None))
         print(f"{len(self.all_ids)} scan folders found; graphs go to {self.output_dir}")
 
@@ -102,7 +113,7 @@ class DataPreprocessor:
 
         path = os.path.join(self.output_dir, standardization.FILE_NAME)
         mean, std, self.stats_failed = compute_dataset_stats.compute_and_save(
-            self.scans, self.args.modality_extensions, self.args.label_extension, path)
+            self.scans, self.args.modality_extensions, self.args.label_extension, path, bias_settings=self.bias)
         print(f"standardization statistics over {len(self.scans) - len(self.stats_failed)} scan(s) written to {path}")
         return standardization.load_stats(path, self.args.modality_extensions)
 
@@ -110,12 +121,25 @@ class DataPreprocessor:
         """Host stage: decode, crop, relabel, normalize, standardize."""
         folder = self.scans[scan_id]
         image = nifti_io.read_in_patient_sample(folder, self.args.modality_extensions)
+        if self.bias is not None:       # corrected on the device first: run() calls finish() for the rest of this stage
+            labels = nifti_io.read_in_labels(folder, self.args.label_extension) if self.args.label_extension else None
+            return image, labels, None
         crop = determine_brain_crop(image)
         labels = None
         if self.args.label_extension:
             labels = swap_labels_from_brats(nifti_io.read_in_labels(folder, self.args.label_extension)[crop])
         image = standardize_img(normalize_img(image[crop]), self.mean, self.std)
         return image, labels, crop
+
+    def finish(self, scan_id, image, labels):
+        """With --bias_correct: the correction on the device, then what load() does to an uncorrected scan."""
+        from gts import bias
+
+        image, self.bias_report[scan_id] = bias.correct_image(image, **self.bias)
+        crop = determine_brain_crop(image)
+        if labels is not None:
+            labels = swap_labels_from_brats(labels[crop])
+        return standardize_img(normalize_img(image[crop]), self.mean, self.std), labels, crop
 
     def store(self, scan_id, graph, image, labels, partition, crop):
         """Host stage: JSON + gzip NIfTI encode."""
@@ -130,6 +154,7 @@ class DataPreprocessor:
 
     def run(self):
         """Process every scan; returns the ids that failed."""
+        from gts import bias
         from mri2graph.graphgen import img2graph
 
         failed, writes = [], []
@@ -141,6 +166,8 @@ class DataPreprocessor:
                     pending[i + READ_AHEAD] = pool.submit(self.load, ids[i + READ_AHEAD])
                 try:
                     image, labels, crop = pending.pop(i).result()
+                    if crop is None:
+                        image, labels, crop = self.finish(scan_id, image, labels)
                     graph, _, partition = img2graph(image, labels, self.args.num_nodes, self.args.boxiness, self.k)
                 except Exception as exc:
                     print(f"{scan_id}: skipped ({exc!r})")
@@ -150,10 +177,13 @@ class DataPreprocessor:
             for scan_id, job in writes:
                 try:
                     job.result()
-                    print(f"{scan_id}: done")
+                    note = f" ({bias.describe(self.bias_report[scan_id])})" if scan_id in self.bias_report else ""
+                    print(f"{scan_id}: done{note}")
                 except Exception as exc:
                     print(f"{scan_id}: writing failed ({exc!r})")
                     failed.append(scan_id)
+        if getattr(self.args, "bias_report", None):
+            bias.save_report(self.args.bias_report, self.args.modality_extensions, self.bias, self.bias_report)
         return failed
 
 
@@ -161,6 +191,9 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     try:
         gen = DataPreprocessor(args)
+    except ValueError as exc:                   # --bias_* settings that cannot run
+        print(f"preprocess_dataset: {exc}", file=sys.stderr)
+        return 2
     except standardization.StatsError as exc:   # a statistics file that does not fit this run, or none could be computed
         print(f"preprocess_dataset: {exc}", file=sys.stderr)
         return 2

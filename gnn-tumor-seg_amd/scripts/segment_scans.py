@@ -20,6 +20,8 @@ A scan that raises is reported and skipped; the exit status is 1 when any scan w
                                      --coregister_max_rotate DEG --coregister_report FILE.json]
                                     [--also_gnn_weights P [P ...] --also_cnn_weights P [P ...]] [--tta_mirror AXES]
                                     [--uncertainty_dir DIR]
+                                    [--bias_correct [--bias_levels L --bias_spans S --bias_iterations N --bias_tol T
+                                     --bias_threshold V --bias_report FILE.json]]
 
 --also_gnn_weights / --also_cnn_weights name further members (the other folds' weight files, paired in order) and
 --tta_mirror AXES (a non-empty subset of xyz) adds the CNN's mirrored views: class probabilities are averaged over
@@ -61,6 +63,17 @@ the device, after a six-parameter rigid refinement that maximises the mutual inf
 The labels go back onto the reference modality's grid with its affine.  --coregister_report FILE.json writes the
 parameters, scores and launch counts found per scan and modality; the scan's line of output names the largest
 translation and rotation.
+
+--bias_correct removes each modality's bias field, the slow multiplicative intensity inhomogeneity of a scan as the
+scanner writes it, on the device (gts.bias, DESIGN.md 4w: N4's scheme of histogram sharpening and multilevel B-spline
+fitting) after --conform / --coregister or the plain upload and before the intake, once per modality.  The mask the
+field is estimated from is every voxel above --bias_threshold (default 0): meant for skull-stripped scans, whose
+background is 0.  --bias_levels lattices, the coarsest with --bias_spans cells per axis and each finer one with twice
+as many (at most 32), are fitted for at most --bias_iterations rounds each, a level ending early when no control point
+moves by --bias_tol.  --bias_report FILE.json writes the rounds run, the last change and the field's range per scan
+and modality; the scan's line of output names the field's range.  scripts.preprocess_dataset and
+scripts.compute_dataset_stats take the same flags: the graphs and the statistics a model is trained on should see the
+correction its scans will see here.  Without the flag nothing changes.
 """
 import argparse
 import os
@@ -78,7 +91,7 @@ from data_processing import nifti_io, standardization  # noqa: E402
 from data_processing.image_processing import (uncrop_maps_to_brats_size, uncrop_to_brats_size,  # noqa: E402
                                               uncrop_to_shape)
 from data_processing.labels import INTERNAL_TO_BRATS  # noqa: E402
-from gts import conform, graphgen, intake, ops, register  # noqa: E402
+from gts import bias, conform, graphgen, intake, ops, register  # noqa: E402
 from scripts import cleanup as cleanup_flags  # noqa: E402
 from scripts import ensemble_flags  # noqa: E402
 from scripts import preprocess_dataset as prep  # noqa: E402
@@ -124,13 +137,15 @@ def build_parser():
                         help="bound on each rotation angle of the search")
     parser.add_argument("--coregister_report", default=None, metavar="FILE.json",
                         help="write the parameters, scores and launch counts found per scan and modality")
-    return ensemble_flags.add_flags(cleanup_flags.add_flags(parser))
+    return bias.add_flags(ensemble_flags.add_flags(cleanup_flags.add_flags(parser)))
 
 
 def parse_args(argv=None):
     """The parsed flags, --coregister resolved: it turns --conform on and names the reference modality's index
-    (args.coregister_ref; None without the flag).  Raises ValueError for flags that do not go together."""
+    (args.coregister_ref; None without the flag), and the --bias_* flags as args.bias (None without --bias_correct,
+    else gts.bias.correct_volume's settings).  Raises ValueError for flags that do not go together or cannot run."""
     args = build_parser().parse_args(argv)
+    args.bias = bias.settings_from_args(args)
     args.coregister_ref = None
     if args.coregister is None:
         if args.coregister_header_only or args.coregister_report:
@@ -179,6 +194,8 @@ class Segmenter:
         self.conform = bool(getattr(args, "conform", False))
         self.coregister_ref = getattr(args, "coregister_ref", None)     # None: the modalities share one grid
         self.coregister_report = {}                                     # scan id -> per-modality findings
+        self.bias = getattr(args, "bias", None)                         # None: intensities are taken as stored
+        self.bias_report = {}                                           # scan id -> per-modality reports
         if getattr(args, "stats", None):
             self.mean, self.std = standardization.load_stats(os.path.expanduser(args.stats), args.modality_extensions)
         else:
@@ -248,6 +265,9 @@ class Segmenter:
             staged, plan, _ = staged
             staged = conform.conform_scan(staged.to(self.device, non_blocking=True), plan)
             tick("conform")
+        if self.bias is not None:
+            staged, self.last_bias = bias.correct_scan(staged.to(self.device, non_blocking=True), **self.bias)
+            tick("bias")
         image, crop, _ = intake.prepare_scan(staged, self.mean, self.std, timer=tick)
         res = graphgen.build_graph(image, None, self.args.num_nodes, self.args.boxiness, self.k, keep_on_device=True)
         graph = graphgen.graph_from_edges(res["edges"], res["feats"].shape[0])
@@ -316,6 +336,9 @@ class Segmenter:
                         note += f" ({self.last_plan.describe()}) ({self.registration_note()})"
                     elif self.conform:
                         note += f" ({staged[1].describe()})"
+                    if self.bias is not None:
+                        self.bias_report[scan_id] = self.last_bias
+                        note += f" ({bias.describe(self.last_bias)})"
                 except Exception as exc:
                     print(f"{scan_id}: skipped ({exc!r})")
                     failed.append(scan_id)
@@ -340,6 +363,8 @@ class Segmenter:
                            "modalities": list(self.args.modality_extensions), "scans": self.coregister_report}, f,
                           indent=1)
                 f.write("\n")
+        if getattr(self.args, "bias_report", None):
+            bias.save_report(self.args.bias_report, self.args.modality_extensions, self.bias, self.bias_report)
         return failed
 
     def registration_note(self):

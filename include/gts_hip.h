@@ -1069,6 +1069,59 @@ int32_t gts_joint_histogram(const float* fixed, int64_t FX, int64_t FY, int64_t 
                             int64_t bins, double lo_f, double scale_f, double lo_m, double scale_m, int64_t* counts,
                             int64_t grid_blocks, void* stream);
 
+/* ---- Z1-Z5: bias-field correction of one MRI volume, N4's scheme (no counterpart in the reference) --
+ * A volume v[Z][Y][X] (x fastest), dtype by its NIfTI code 4 (int16) or 16 (float32), else GTS_ERR_ARGKIND.  Every
+ * extent in [1, 65535] and fewer than 2^31 voxels, else GTS_ERR_SHAPE.  Nothing is launched for a rejected argument.
+ * The log field is a sum of `levels` uniform cubic B-spline lattices; level l has spans0 << l cells and n_l = (spans0
+ * << l) + 3 control points per axis, spans0 >= 1, 1 <= levels <= 6, spans0 << (levels - 1) <= GTS_BIAS_MAX_SPANS,
+ * else GTS_ERR_SHAPE.  Device operands that describe it, shared by Z2-Z5:
+ *   lattice  float64, the levels one after another, level l as [n_l][n_l][n_l] with z slowest;
+ *   weights  float64 x: [levels][4][X], then y: [levels][4][Y], then z: [levels][4][Z]: the four B-spline weights of
+ *            every index of an axis at every level;   cells  int32 x: [levels][X], y: [levels][Y], z: [levels][Z]: the
+ *            first control point they sit on (clamped to 0 .. spans - 1 by the kernels).  gts/bias.py tabulates both.
+ *   field(x, y, z) = sum_l sum_a Bx_a * (sum_b By_b * (sum_c Bz_c * L_l[cz + c][cy + b][cx + a])): float64 products
+ *            and sums, nothing contracted, every sum ascending from its first term, the levels last.
+ * u is float32 [Z][Y][X]; its NaNs are outside the mask; d = float64(u) - field.  grid_blocks: workgroups of the
+ * pass over the rows (0: the library's choice, else 1 .. 2^31 - 1); no result below depends on it.
+ * workspace: gts_bias_workspace(X, Y, Z, spans of the last level) bytes, else GTS_ERR_SHAPE.
+ * gts_bias_log (Z1): u = float32(log(float64(v))) where v is finite and v > threshold, NaN elsewhere; *count (device)
+ *   = the number of mask voxels.  threshold finite and >= 0, else GTS_ERR_ARGKIND.
+ * gts_bias_range (Z2): range (device float64 [2]) = min and max of d over the mask, (+Inf, -Inf) for an empty one.
+ * gts_bias_histogram (Z3): counts (device int64 [GTS_BIAS_BINS], zeroed by the call): one count per mask voxel at
+ *   clamp(floor((d - lo) / w + 0.5), 0, BINS - 1), w = (hi - lo) / (BINS - 1).  lo, hi finite with hi > lo, else
+ *   GTS_ERR_ARGKIND.  LDS integer tables and integer global atomics.
+ * gts_bias_fit (Z4): with pos = (d - lo) / w, i0 = clamp(floor(pos), 0, BINS - 2) and the HOST float64 table
+ *   [GTS_BIAS_BINS] (finite, else GTS_ERR_ARGKIND): r = d - (table[i0] + (table[i0 + 1] - table[i0]) * (pos - i0)).
+ *   fit_weights (device float64 x: [8][X], y: [8][Y], z: [8][Z]) holds, for the fitted `level`, p_a = B_a^3 / sum_a
+ *   B_a^2 (rows 0..3) and q_a = B_a^2 (rows 4..7).  out (device float64 [3][n][n][n], n of that level) = num, den,
+ *   delta: num[c][b][a] = sum over the mask of pz py px r, den = sum of qz qy qx over the control points each voxel
+ *   sits on, delta = num / den and 0 where den == 0.  Float64, no atomics, the same bits on every run and grid.
+ * gts_bias_mean (Z5): out (device float64 [3]) = the sum of the field over the mask, the mask's size, their ratio (0
+ *   for an empty mask); fixed order, no atomics.
+ * gts_bias_apply (Z5): out = float32(float64(v) / exp(field - mean)) at every voxel; field_out, when not NULL,
+ *   float32(field - mean).  mean finite, else GTS_ERR_ARGKIND. */
+#define GTS_BIAS_BINS 200
+#define GTS_BIAS_MAX_SPANS 32
+int64_t gts_bias_workspace(int64_t X, int64_t Y, int64_t Z, int64_t spans);
+int32_t gts_bias_log(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, double threshold, float* u,
+                     uint64_t* count, void* stream);
+int32_t gts_bias_range(const float* u, int64_t X, int64_t Y, int64_t Z, const double* weights, const int32_t* cells,
+                       const double* lattice, int64_t spans0, int64_t levels, double* range, void* workspace,
+                       int64_t workspace_bytes, int64_t grid_blocks, void* stream);
+int32_t gts_bias_histogram(const float* u, int64_t X, int64_t Y, int64_t Z, const double* weights, const int32_t* cells,
+                           const double* lattice, int64_t spans0, int64_t levels, double lo, double hi, int64_t* counts,
+                           int64_t grid_blocks, void* stream);
+int32_t gts_bias_fit(const float* u, int64_t X, int64_t Y, int64_t Z, const double* weights, const int32_t* cells,
+                     const double* lattice, int64_t spans0, int64_t levels, int64_t level, const double* fit_weights,
+                     double lo, double hi, const double* table, double* out, void* workspace, int64_t workspace_bytes,
+                     int64_t grid_blocks, void* stream);
+int32_t gts_bias_mean(const float* u, int64_t X, int64_t Y, int64_t Z, const double* weights, const int32_t* cells,
+                      const double* lattice, int64_t spans0, int64_t levels, double* out, void* workspace,
+                      int64_t workspace_bytes, int64_t grid_blocks, void* stream);
+int32_t gts_bias_apply(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, const double* weights,
+                       const int32_t* cells, const double* lattice, int64_t spans0, int64_t levels, double mean,
+                       float* out, float* field_out, int64_t grid_blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
