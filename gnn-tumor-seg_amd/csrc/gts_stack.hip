@@ -167,12 +167,25 @@ extern "C" int64_t gts_sage_pool_stack_fwd_arena(int64_t n_rows, const int64_t* 
   return p.total;
 }
 
-extern "C" int32_t gts_sage_pool_stack_fwd_f32(const int32_t* indptr, const int32_t* indices, const int32_t* sched_rec,
-                                               int64_t sched_clusters, int32_t sched_rows, int32_t sched_srcs,
-                                               int32_t sched_loc_words, const float* x, const float* const* params,
-                                               int64_t n_rows, const int64_t* widths, int32_t n_layers, int32_t training,
-                                               int32_t arg_bytes, int32_t relu_bits, void* arena, int64_t arena_bytes,
-                                               void* stream) {
+namespace {
+
+// what the training step's forward hands its top layer (gts_sage_top_layer_train_f32) beyond the layer's own operands
+struct TopTurn {
+  const int64_t* labels;
+  const float* class_w;
+  int32_t normalise;
+  float* g_top;
+  float* const* grads;
+  float* out3;
+  float* workspace;
+  int64_t workspace_bytes;
+};
+
+int32_t stack_forward(const int32_t* indptr, const int32_t* indices, const int32_t* sched_rec, int64_t sched_clusters,
+                      int32_t sched_rows, int32_t sched_srcs, int32_t sched_loc_words, const float* x,
+                      const float* const* params, int64_t n_rows, const int64_t* widths, int32_t n_layers, int32_t training,
+                      int32_t arg_bytes, int32_t relu_bits, void* arena, int64_t arena_bytes, const TopTurn* top,
+                      void* stream) {
   if (!indptr || !x || !params || !arena) return GTS_ERR_NULL;
   if (bad_stack(n_rows, widths, n_layers)) return GTS_ERR_SHAPE;
   if (training && arg_bytes != 1 && arg_bytes != 4) return GTS_ERR_ARGKIND;
@@ -181,6 +194,13 @@ extern "C" int32_t gts_sage_pool_stack_fwd_f32(const int32_t* indptr, const int3
   const bool train = training != 0;
   const FwdPlan plan = plan_forward(n_rows, widths, n_layers, train, arg_bytes, relu_bits != 0);
   if (arena_bytes < plan.total) return GTS_ERR_SHAPE;
+  if (top != nullptr) {
+    if (!top->labels || !top->g_top || !top->grads || !top->out3 || !top->workspace) return GTS_ERR_NULL;
+    const int64_t need = gts_sage_top_layer_train_workspace(n_rows, widths[n_layers - 1], widths[n_layers]);
+    if (need == 0 || top->workspace_bytes < need) return GTS_ERR_SHAPE;
+    for (int q = 2; q < 5; ++q)
+      if (!top->grads[5 * (n_layers - 1) + q]) return GTS_ERR_NULL;
+  }
   if (n_rows == 0) return GTS_OK;
   char* base = static_cast<char*>(arena);
   auto f32 = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
@@ -232,6 +252,13 @@ extern "C" int32_t gts_sage_pool_stack_fwd_f32(const int32_t* indptr, const int3
       GTS_TRY(gts_linear_fwd_chain_f32(h, w_self, m, w_neigh, bias, out, params[5 * (i + 1)], params[5 * (i + 1) + 1], p_next,
                                        n_rows, fout, fin, fin, 1, fout, 1, bits, packed, stream));
       p = p_next, cur ^= 1;
+    } else if (last && top != nullptr) {
+      // classifier, loss, the gradient w.r.t. the logits and the layer's narrow weight gradients in one pass over h and m
+      float* const* gr = top->grads + 5 * i;
+      GTS_TRY(gts_sage_top_layer_train_f32(h, m, w_self, w_neigh, bias, top->labels, top->class_w, top->normalise, out,
+                                           top->g_top, gr[2], gr[3], gr[4], top->out3, top->workspace, top->workspace_bytes,
+                                           n_rows, fin, fout, stream));
+      p = nullptr;
     } else {
       const float* packed[2] = {wp(i, 1), wp(i, 2)};
       GTS_TRY(gts_linear_fwd_f32(h, w_self, m, w_neigh, bias, out, n_rows, fout, fin, fin, last ? 0 : 1, bits, packed, stream));
@@ -240,6 +267,31 @@ extern "C" int32_t gts_sage_pool_stack_fwd_f32(const int32_t* indptr, const int3
     h = out;
   }
   return GTS_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t gts_sage_pool_stack_fwd_f32(const int32_t* indptr, const int32_t* indices, const int32_t* sched_rec,
+                                               int64_t sched_clusters, int32_t sched_rows, int32_t sched_srcs,
+                                               int32_t sched_loc_words, const float* x, const float* const* params,
+                                               int64_t n_rows, const int64_t* widths, int32_t n_layers, int32_t training,
+                                               int32_t arg_bytes, int32_t relu_bits, void* arena, int64_t arena_bytes,
+                                               void* stream) {
+  return stack_forward(indptr, indices, sched_rec, sched_clusters, sched_rows, sched_srcs, sched_loc_words, x, params, n_rows,
+                       widths, n_layers, training, arg_bytes, relu_bits, arena, arena_bytes, nullptr, stream);
+}
+
+extern "C" int32_t gts_sage_pool_stack_train_fwd_f32(const int32_t* indptr, const int32_t* indices, const int32_t* sched_rec,
+                                                     int64_t sched_clusters, int32_t sched_rows, int32_t sched_srcs,
+                                                     int32_t sched_loc_words, const float* x, const float* const* params,
+                                                     int64_t n_rows, const int64_t* widths, int32_t n_layers,
+                                                     int32_t arg_bytes, int32_t relu_bits, void* arena, int64_t arena_bytes,
+                                                     const int64_t* labels, const float* class_w, int32_t normalise,
+                                                     float* g_top, float* const* grads, float* out3, float* top_workspace,
+                                                     int64_t top_workspace_bytes, void* stream) {
+  const TopTurn top{labels, class_w, normalise, g_top, grads, out3, top_workspace, top_workspace_bytes};
+  return stack_forward(indptr, indices, sched_rec, sched_clusters, sched_rows, sched_srcs, sched_loc_words, x, params, n_rows,
+                       widths, n_layers, 1, arg_bytes, relu_bits, arena, arena_bytes, &top, stream);
 }
 
 extern "C" int64_t gts_sage_pool_stack_bwd_scratch(int64_t n_rows, const int64_t* widths, int32_t n_layers,
@@ -255,8 +307,23 @@ extern "C" int32_t gts_sage_pool_stack_bwd_f32(const int32_t* t_indptr, const in
                                                int32_t n_layers, int32_t arg_bytes, int32_t relu_bits, const void* fwd_arena,
                                                float* const* grads, float* gx, void* scratch, int64_t scratch_bytes,
                                                void* stream) {
+  return gts_sage_pool_stack_bwd_top_f32(t_indptr, t_indices, t_slot, sched_rec, sched_clusters, sched_rows, sched_srcs,
+                                         sched_loc_words, gout, x, params, n_rows, widths, n_layers, arg_bytes, relu_bits,
+                                         fwd_arena, grads, gx, scratch, scratch_bytes, 0, stream);
+}
+
+extern "C" int32_t gts_sage_pool_stack_bwd_top_f32(const int32_t* t_indptr, const int32_t* t_indices, const int32_t* t_slot,
+                                                   const int32_t* sched_rec, int64_t sched_clusters, int32_t sched_rows,
+                                                   int32_t sched_srcs, int32_t sched_loc_words, const float* gout,
+                                                   const float* x, const float* const* params, int64_t n_rows,
+                                                   const int64_t* widths, int32_t n_layers, int32_t arg_bytes,
+                                                   int32_t relu_bits, const void* fwd_arena, float* const* grads, float* gx,
+                                                   void* scratch, int64_t scratch_bytes, int32_t top_done, void* stream) {
   if (!t_indptr || !gout || !x || !params || !fwd_arena || !grads || !scratch) return GTS_ERR_NULL;
   if (bad_stack(n_rows, widths, n_layers)) return GTS_ERR_SHAPE;
+  // the forward that leaves the top layer's gradients takes one shape (gts_sage_top_layer_train_f32)
+  if (top_done && (n_rows == 0 || gts_sage_top_layer_train_workspace(n_rows, widths[n_layers - 1], widths[n_layers]) == 0))
+    return GTS_ERR_SHAPE;
   if (arg_bytes != 1 && arg_bytes != 4) return GTS_ERR_ARGKIND;
   for (int i = 0; i < 5 * n_layers; ++i)
     if (!params[i] || !grads[i]) return GTS_ERR_NULL;
@@ -347,7 +414,7 @@ extern "C" int32_t gts_sage_pool_stack_bwd_f32(const int32_t* t_indptr, const in
     }
     gm = nullptr;
     wgrads.add(fin, fin, gp, h, grads[5 * i], grads[5 * i + 1]);        // fc_pool.weight, fc_pool.bias
-    if (!fused) {
+    if (!fused && !(top_done && i == n_layers - 1)) {
       wgrads.add(fout, fin, g, h, grads[5 * i + 2], grads[5 * i + 4]);    // fc_self.weight, bias
       wgrads.add(fout, fin, g, m, grads[5 * i + 3], nullptr);             // fc_neigh.weight
     }

@@ -457,6 +457,52 @@ def sage_first_layer_bwd(g, x, m0, w_neigh):
     return gm, gw_self, g_bias, gw_neigh
 
 
+def top_layer_train_applies(h, m, w_self, w_neigh):
+    """The shapes gts_sage_top_layer_train_f32 takes: a 256 -> 4 top layer with rows (the stack's C plan decides alike)."""
+    return h.shape[0] > 0 and h.shape[1] == 256 and m.shape[1] == 256 and tuple(w_self.shape) == (4, 256) \
+        and tuple(w_neigh.shape) == (4, 256)
+
+
+_top_ws = StreamBuffers()
+
+
+def top_layer_train_workspace(rows, device):
+    """The scratch of gts_sage_top_layer_train_f32 for `rows` rows: (tensor, bytes), kept per (device, stream)."""
+    nbytes = _lib.load().gts_sage_top_layer_train_workspace(rows, 256, 4)
+    return _top_ws.get(device, nbytes), nbytes
+
+
+def sage_top_layer_train(h, m, w_self, w_neigh, bias, labels, class_w=None, normalise=True, out=None):
+    """(logits, g, gw_self, gw_neigh, g_bias, stats) of a 256 -> 4 top SAGEConv('pool') layer in a training step, in one
+    pass over h and m [M, 256]: the bits of linear_fwd(h, w_self, m, w_neigh, bias), of the weighted cross-entropy's
+    [num, den, num / den] and unscaled gradient on those logits, of its division by den (`normalise`; False keeps the
+    numerator's gradient), and of linear_bwd_weight(g, h, want_bias_grad=True) and linear_bwd_weight(g, m).
+    `out`: optional (gw_self, gw_neigh, g_bias) destinations."""
+    if not top_layer_train_applies(_mat(h, "h"), _mat(m, "m"), _mat(w_self, "w_self"), _mat(w_neigh, "w_neigh")):
+        raise _lib.GtsError("sage_top_layer_train takes h [M, 256], m [M, 256], w_self [4, 256], w_neigh [4, 256] with M > 0")
+    _same(m.shape[0], h.shape[0], "rows of h / m")
+    h, m, w_self, w_neigh, bias = _dense(h, m, w_self, w_neigh, bias)
+    dev = _operands(h, m, w_self, w_neigh, bias, class_w)
+    rows = h.shape[0]
+    if tuple(bias.shape) != (4,) or (class_w is not None and tuple(class_w.shape) != (4,)):
+        raise _lib.GtsError("sage_top_layer_train takes bias [4] and class weights [4]")
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (rows,) or not labels.is_contiguous() or labels.device != dev:
+        raise _lib.GtsError(f"labels must be contiguous int64 [{rows}] on {dev}")
+    logits, g = (torch.empty((rows, 4), dtype=torch.float32, device=dev) for _ in range(2))
+    if out is None:
+        out = (torch.empty((4, 256), dtype=torch.float32, device=dev), torch.empty((4, 256), dtype=torch.float32, device=dev),
+               torch.empty(4, dtype=torch.float32, device=dev))
+    gw_self, gw_neigh, g_bias = out
+    stats = torch.empty(3, dtype=torch.float32, device=dev)
+    ws, nbytes = top_layer_train_workspace(rows, dev)
+    # not bracketed by GEMM_TIMER: a stream over h and m, no launch of the kinds that timer sets against the MFMA peak
+    check(_lib.load().gts_sage_top_layer_train_f32(
+        ptr(h), ptr(m), ptr(w_self), ptr(w_neigh), ptr(bias), ptr(labels), ptr(class_w), 1 if normalise else 0, ptr(logits),
+        ptr(g), ptr(gw_self), ptr(gw_neigh), ptr(g_bias), ptr(stats), ptr(ws), ws.numel() * 4, rows, 256, 4,
+        current_stream()), "gts_sage_top_layer_train_f32")
+    return logits, g, gw_self, gw_neigh, g_bias, stats
+
+
 def relu_bwd(g, out):
     """g * (out > 0) where `out` is the ReLU output (new tensor; g is left untouched)."""
     return g * (out > 0)

@@ -214,6 +214,22 @@ class FlatGradSync:
             logits.backward(grad)                               # d(numerator): the kernel's gradient as it is
         self._scalars = (stats[1:2], stats[0:1])                # (denominator, numerator): views, no launch
 
+    def fused_stack_backward(self, graph, features, layers, labels, class_weights):
+        """weighted_ce_backward for a network that is one fused pool stack with a 256 -> 4 top layer, forward included and
+        outside autograd (gts.nn.sage_pool_stack_train with the numerator's gradient: same bits).  False when the step
+        does not have that shape: nothing has been launched and the caller takes the path through autograd."""
+        from . import nn
+        if self._sink is None:
+            self._sink = nn.GradSink(self.params, extra=2)
+        done = nn.sage_pool_stack_train(graph, features, layers, labels, class_weights, self._sink, normalise=False)
+        if done is None:
+            return False
+        for p in self.params:
+            p.grad = None
+        stats = done[1]
+        self._scalars = (stats[1:2], stats[0:1])                # (denominator, numerator): views, no launch
+        return True
+
     def empty_step(self, device=None):
         """This rank has no sample in the (short, last) global batch of the epoch: it contributes
         zero gradients, numerator and denominator, and still takes part in the collective."""

@@ -185,10 +185,14 @@ class _SagePoolStack(torch.autograd.Function):
     activation is stored once (layer L's input is layer L-1's output)."""
 
     @staticmethod
-    def forward(ctx, g, x, need_bwd, *params):
+    def launch_forward(g, x, need_bwd, params, top=None):
+        """The forward's launches: (output, [h, m, arg, hbits] per layer, top).  `top` = (labels, class_w, normalise,
+        destinations or None) makes the last layer's classifier launch dense.sage_top_layer_train, whose
+        (g, gw_self, gw_neigh, g_bias, stats) are returned as the third value: the training step's turn to the backward."""
         n_layers = len(params) // 5
         h = x.contiguous()
         saved = []
+        turn = None
         hbits = None                      # h > 0 as bits (h is a ReLU output from layer 1 on): the backward's mask
         p = None                          # relu(fc_pool(h)) of the layer about to run, when already computed
         # the weights the panel GEMMs may read (outputs wider than 128 columns), in fragment order: one launch per shape,
@@ -209,13 +213,21 @@ class _SagePoolStack(torch.autograd.Function):
                 # fc_self + fc_neigh of this layer and fc_pool of the next one in one launch
                 out, p = dense.linear_fwd_chain(h, w_self, m, w_neigh, bias, True, nxt[0], nxt[1], True, relu_bits=obits,
                                                 packed=(fragment.get(id(w_self)), fragment.get(id(w_neigh)), fragment.get(id(nxt[0]))))
+            elif last and top is not None:
+                labels, class_w, normalise, dst = top
+                out, *turn = dense.sage_top_layer_train(h, m, w_self, w_neigh, bias, labels, class_w, normalise, out=dst)
             else:
                 out = dense.linear_fwd(h, w_self, m, w_neigh, bias=bias, relu=not last, relu_bits=obits,
                                        packed=(fragment.get(id(w_self)), fragment.get(id(w_neigh))))
             saved += [h, m, arg, hbits]
             h, hbits = out, obits
+        return h, saved, turn
+
+    @staticmethod
+    def forward(ctx, g, x, need_bwd, *params):
+        h, saved, _ = _SagePoolStack.launch_forward(g, x, need_bwd, params)
         if need_bwd:
-            ctx.g, ctx.n_layers = g, n_layers
+            ctx.g, ctx.n_layers = g, len(params) // 5
             ctx.save_for_backward(*saved, *params)
         return h
 
@@ -223,7 +235,14 @@ class _SagePoolStack(torch.autograd.Function):
     def backward(ctx, gout):
         n = ctx.n_layers
         tensors = ctx.saved_tensors
-        acts, params = tensors[:4 * n], tensors[4 * n:]
+        gx, grads = _SagePoolStack.launch_backward(ctx.g, tensors[:4 * n], tensors[4 * n:], gout, ctx.needs_input_grad[1])
+        return (None, gx, None, *grads)
+
+    @staticmethod
+    def launch_backward(graph, acts, params, gout, need_gx, top_done=False):
+        """The backward's launches: (gx or None, the 5 n parameter gradients).  top_done: the forward was launch_forward
+        with `top`, which has left the top layer's fc_self / fc_neigh / bias gradients (their entries stay None)."""
+        n = len(params) // 5
         grads = [None] * (5 * n)
         g = gout.contiguous()            # gradient w.r.t. the pre-activation output of layer i
         gx = None
@@ -265,14 +284,14 @@ class _SagePoolStack(torch.autograd.Function):
                 gm, grads[2], grads[4], grads[3] = dense.sage_first_layer_bwd(g, h, m, w_neigh)
             elif narrow and i == n - 1 and ops.lowrank_bwd_applies(g, w_neigh, arg):
                 # a 256 -> 4 top layer: K2 forms the rows of g @ W_neigh in registers, the [N, 256] product is never stored
-                gp = ops.spmm_max_bwd_lowrank(ctx.g, g, w_neigh, arg)
+                gp = ops.spmm_max_bwd_lowrank(graph, g, w_neigh, arg)
             elif gm is None:
                 gm = igrad(g, w_neigh)
             if gm is not None:
-                gp = ops.spmm_max_bwd(ctx.g, gm, arg)   # ReLU'(p) is already in the winner record
+                gp = ops.spmm_max_bwd(graph, gm, arg)   # ReLU'(p) is already in the winner record
             gm = None
             defer(gp, h, 5 * i, 5 * i + 1)              # fc_pool.weight, fc_pool.bias
-            if not fused:
+            if not fused and not (top_done and i == n - 1):
                 defer(g, h, 5 * i + 2, 5 * i + 4)       # fc_self.weight, bias
                 defer(g, m, 5 * i + 3, None)            # fc_neigh.weight
             if i > 0:      # h is layer i-1's ReLU output: its backward is the mask h > 0
@@ -285,7 +304,7 @@ class _SagePoolStack(torch.autograd.Function):
                                                                    turned_fragment[id(below)]))
                 else:
                     g = igrad(g, w_self, gp, w_pool, relu_mask=h, relu_bits=hbits)
-            elif ctx.needs_input_grad[1]:
+            elif need_gx:
                 gx = igrad(g, w_self, gp, w_pool)
         for problems in deferred.values():
             results = dense.linear_bwd_weight_multi([(go, act, want) for go, act, want, _, _ in problems])
@@ -293,7 +312,7 @@ class _SagePoolStack(torch.autograd.Function):
                 grads[slot] = gw
                 if bias_slot is not None:
                     grads[bias_slot] = gb
-        return (None, gx, None, *grads)
+        return gx, grads
 
 
 # GTS_STACK_C=0 keeps the launch-by-launch Python loop of the fused stack (A/B runs; bench.py's instrumented block
@@ -441,10 +460,9 @@ class _SagePoolStackCall(torch.autograd.Function):
         return (None, gx, None, *[flat[s:s + k].view_as(p) for s, k, p in zip(starts, sizes, params)])
 
 
-def sage_pool_stack(graph, features, layers):
-    """Run `layers` (SAGEConv pool modules: ReLU on all but the last, no active dropout, bias on)
-    as one fused autograd node.  Returns None when the stack does not have that shape, so the
-    caller can fall back to the layer-by-layer path."""
+def _pool_stack_params(layers):
+    """The parameters of `layers`, five per layer in the fused stack's order, when they are SAGEConv pool modules with
+    ReLU on all but the last, no active dropout and bias on; None otherwise."""
     for i, layer in enumerate(layers):
         last = i == len(layers) - 1
         if not isinstance(layer, SAGEConv) or layer._aggre_type != "pool" or layer.bias is None \
@@ -456,11 +474,103 @@ def sage_pool_stack(graph, features, layers):
     for layer in layers:
         params += [layer.fc_pool.weight, layer.fc_pool.bias, layer.fc_self.weight,
                    layer.fc_neigh.weight, layer.bias]
+    return params
+
+
+def sage_pool_stack(graph, features, layers):
+    """Run `layers` (SAGEConv pool modules: ReLU on all but the last, no active dropout, bias on)
+    as one fused autograd node.  Returns None when the stack does not have that shape, so the
+    caller can fall back to the layer-by-layer path."""
+    params = _pool_stack_params(layers)
+    if params is None:
+        return None
     need_bwd = torch.is_grad_enabled() and (features.requires_grad or any(p.requires_grad for p in params))
     one_call = STACK_IN_ONE_CALL and not ops.INSTRUMENTED and features.shape[1] % 4 == 0 \
         and all(p.shape[-1] % 4 == 0 and p.shape[0] % 4 == 0 and p.is_contiguous() for p in params) \
         and features.dtype == torch.float32 and features.is_cuda
     return (_SagePoolStackCall if one_call else _SagePoolStack).apply(graph, features, need_bwd, *params)
+
+
+# GTS_TOP_TURN=0: the training step keeps the classifier, the loss and the top layer's weight gradients as launches of
+# their own (A/B runs; tests/test_gpu_top_turn.py switches it to compare the two steps).
+TOP_TURN = os.environ.get("GTS_TOP_TURN", "1") != "0"
+
+
+def sage_pool_stack_train(graph, features, layers, labels, class_w, sink, normalise=True):
+    """Forward and backward of a training step whose whole network is one fused pool stack with a 256 -> 4 top layer,
+    outside autograd: the launches of `sage_pool_stack(...)`, the weighted cross-entropy on its logits and
+    `logits.backward(grad)`, except that ONE pass over the top layer's two 256-wide inputs forms the logits, the loss,
+    the gradient w.r.t. the logits and that layer's narrow weight gradients (gts_sage_top_layer_train_f32: same bits).
+    Every parameter gradient lands in a new buffer of `sink` (a GradSink over exactly the stack's parameters, which it
+    marks as filled); `normalise` False leaves the gradients of the loss's numerator (the data-parallel step divides after its
+    all-reduce).  Returns (logits, [num, den, num / den]), or None when the step does not have that shape — the caller
+    then takes the path through autograd."""
+    params = _pool_stack_params(layers) if TOP_TURN and not ops.INSTRUMENTED and layers else None
+    if params is None:
+        return None
+    top = layers[-1]
+    n = features.shape[0]
+    if n == 0 or (top._in_src_feats, top._out_feats) != (256, 4) or features.dim() != 2 or features.shape[1] % 4 != 0 \
+            or features.dtype != torch.float32 or not features.is_cuda or features.requires_grad \
+            or not all(p.shape[-1] % 4 == 0 and p.shape[0] % 4 == 0 and p.is_contiguous() and p.requires_grad for p in params) \
+            or labels.dtype != torch.int64 or not labels.is_cuda or tuple(labels.shape) != (n,) \
+            or (class_w is not None and (tuple(class_w.shape) != (4,) or class_w.dtype != torch.float32 or not class_w.is_cuda)) \
+            or len(params) != len(sink.params) or not all(id(p) in sink.offsets for p in params):
+        return None
+    labels = labels.contiguous()
+    class_w = class_w.contiguous() if class_w is not None else None
+    n_layers = len(layers)
+    flat = sink.new_buffer()
+    spans = [(sink.offsets[id(p)], p.numel()) for p in params]
+    with torch.no_grad():
+        if not STACK_IN_ONE_CALL:
+            # the launch-by-launch copy of the plan; its gradients are tensors of their own, copied into the flat buffer
+            # fc_self.weight, fc_neigh.weight, bias of the top layer
+            dst = tuple(flat[s:s + k].view_as(p) for (s, k), p in zip(spans[-3:], params[-3:]))
+            logits, saved, turn = _SagePoolStack.launch_forward(graph, features, True, [p.detach() for p in params],
+                                                                top=(labels, class_w, normalise, dst))
+            g_top, stats = turn[0], turn[4]
+            _, grads = _SagePoolStack.launch_backward(graph, saved, [p.detach() for p in params], g_top, False, top_done=True)
+            for (s, k), grad in zip(spans, grads):
+                if grad is not None:
+                    flat[s:s + k].copy_(grad.reshape(-1))
+            sink.filled = True
+            return logits, stats
+        import ctypes
+
+        from . import _lib
+        from ._lib import check, current_stream, ptr
+
+        lib = _lib.load()
+        x = features.contiguous()
+        table, c_widths, widths = _stack_table(params, x.shape[1])
+        relu_bits, ab = 1 if RELU_MASK_BITS else 0, graph.arg_bytes
+        d = graph.dev()
+        offsets = (ctypes.c_int64 * (4 * n_layers + 2))()
+        total = lib.gts_sage_pool_stack_fwd_arena(n, c_widths, n_layers, 1, ab, relu_bits, offsets)
+        if total < 0:
+            raise _lib.GtsError("gts_sage_pool_stack_fwd_arena rejected the stack's shape")
+        arena = torch.empty(max(int(total), 16), dtype=torch.uint8, device=x.device)
+        grads = (ctypes.c_void_p * (5 * n_layers))(*[flat.data_ptr() + 4 * s for s, _ in spans])
+        g_top = torch.empty((n, 4), dtype=torch.float32, device=x.device)
+        stats = torch.empty(3, dtype=torch.float32, device=x.device)
+        top_ws, top_bytes = dense.top_layer_train_workspace(n, x.device)
+        ds = ops._cluster_schedule(graph, "in", n, 256, ab) if 256 in widths[:-1] else None
+        check(lib.gts_sage_pool_stack_train_fwd_f32(
+            ptr(d.indptr), ptr(d.indices), *_DeviceSchedule.launch_args(ds), ptr(x), table, n, c_widths, n_layers, ab,
+            relu_bits, arena.data_ptr(), int(total), ptr(labels), ptr(class_w), 1 if normalise else 0, ptr(g_top), grads,
+            ptr(stats), ptr(top_ws), top_ws.numel() * 4, current_stream()), "gts_sage_pool_stack_train_fwd_f32")
+        at = int(offsets[4 * (n_layers - 1) + 2])
+        logits = arena[at:at + 4 * n * 4].view(torch.float32).view(n, 4)
+        need = lib.gts_sage_pool_stack_bwd_scratch(n, c_widths, n_layers, relu_bits)
+        scratch = torch.empty(max(int(need), 16), dtype=torch.uint8, device=x.device)
+        ds = ops._cluster_schedule(graph, "out", n, 256, ab) if 256 in widths[:-1] else None
+        check(lib.gts_sage_pool_stack_bwd_top_f32(
+            ptr(d.t_indptr), ptr(d.t_indices), ptr(d.t_slot), *_DeviceSchedule.launch_args(ds), ptr(g_top), ptr(x), table, n,
+            c_widths, n_layers, ab, relu_bits, arena.data_ptr(), grads, None, scratch.data_ptr(), int(need), 1,
+            current_stream()), "gts_sage_pool_stack_bwd_top_f32")
+        sink.filled = True
+        return logits, stats
 
 
 class SAGEConv(nn.Module):

@@ -138,6 +138,20 @@ class GNN:
 
     def train_step(self, graph, features, labels):
         """One optimizer step on device-resident inputs; returns the loss as a 0-dim tensor."""
+        # a network that is one fused pool stack with a 256 -> 4 top layer: forward, loss and backward without autograd,
+        # the classifier, the loss and the top layer's narrow gradients in one pass (gts.nn.sage_pool_stack_train: same bits)
+        stack = list(self.net.layers) if getattr(self.net, "fuse_layers", False) else None
+        if stack is not None and self.grad_sync is None:
+            done = gnn.sage_pool_stack_train(graph, features, stack, labels, self.class_weights, self.grad_sink)
+            if done is not None:
+                self.optimizer.zero_grad()
+                self.optimizer.step(flat_grad=self.grad_sink.flat)
+                return done[1][2]
+        elif stack is not None and isinstance(self.optimizer, FlatAdamW) and self.grad_sync.fused_stack_backward(
+                graph, features, stack, labels, self.class_weights):
+            loss = self.grad_sync.all_reduce_and_normalise()
+            self.optimizer.step(flat_grad=self.grad_sync.flat_gradients())
+            return loss
         logits = self.net(graph, features)
         if self.grad_sync is None:
             # loss_fcn(logits, labels).backward() without the autograd node of the loss: the fused pass returns

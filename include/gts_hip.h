@@ -440,6 +440,24 @@ int64_t gts_sage_first_layer_bwd_workspace(int64_t m, int64_t w, int64_t s0, int
 int32_t gts_sage_first_layer_bwd_f32(const float* g, const float* x, const float* m0, const float* w_neigh, float* gm,
                                      float* gw_self, float* g_bias, float* gw_neigh, float* workspace,
                                      int64_t workspace_bytes, int64_t m, int64_t w, int64_t s0, int64_t s1, void* stream);
+/* The 256 -> 4 TOP SAGEConv('pool') layer of a training step in ONE pass over its input h [m, k] and its max-pooled
+ * neighbours mx [m, k] (model/gnn_model.py:41-45: logits, CrossEntropyLoss(weight), backward), plus three small launches:
+ *   logits [m, 4]      = h w_self^T + mx w_neigh^T + bias        exactly gts_linear_fwd_f32 (weights [4, k] as stored)
+ *   out3               = { num, den, num / den }                 exactly gts_weighted_ce_f32 on those logits
+ *   g [m, 4]           = gu / den (normalise = 1: one IEEE division per element) or gu (normalise = 0: the gradient of
+ *                        the numerator, for a step that divides after its all-reduce), gu as gts_weighted_ce_f32 gives it
+ *   gw_self, gw_neigh [4, k], g_bias [4]                         exactly gts_linear_bwd_weight_f32 of (g, h) with its bias
+ *                                                                and of (g, mx)
+ * bit for bit.  labels int64 [m] with gts_weighted_ce_f32's rules (-100 contributes nothing, any other label outside
+ * [0, 4) makes the loss NaN), class_w [4] optional.  Takes k = 256 and n_classes = 4 with 0 < m < 2^31; every other shape
+ * is GTS_ERR_SHAPE and keeps the calls above.  workspace >= gts_sage_top_layer_train_workspace(...) bytes (0 = shape not
+ * taken), caller-owned scratch. */
+int64_t gts_sage_top_layer_train_workspace(int64_t m, int64_t k, int64_t n_classes);
+int32_t gts_sage_top_layer_train_f32(const float* h, const float* mx, const float* w_self, const float* w_neigh,
+                                     const float* bias, const int64_t* labels, const float* class_w, int32_t normalise,
+                                     float* logits, float* g, float* gw_self, float* gw_neigh, float* g_bias, float* out3,
+                                     float* workspace, int64_t workspace_bytes, int64_t m, int64_t k, int64_t n_classes,
+                                     void* stream);
 
 /* ---- a whole stack of SAGEConv('pool') layers in one call each way -------------------------------
  * Replaces the layer loop of GraphSage.forward (model/networks.py:32-36: `for layer in self.layers: h = layer(graph, h)`)
@@ -479,6 +497,27 @@ int32_t gts_sage_pool_stack_bwd_f32(const int32_t* t_indptr, const int32_t* t_in
                                     int32_t n_layers, int32_t arg_bytes, int32_t relu_bits, const void* fwd_arena,
                                     float* const* grads, float* gx, void* scratch, int64_t scratch_bytes,
                                     void* stream);
+/* The training step's forward with the turn to the backward folded in, for a stack whose top layer is 256 -> 4 (any other
+ * is GTS_ERR_SHAPE): gts_sage_pool_stack_fwd_f32 with training = 1, except that the last layer's classifier launch is
+ * gts_sage_top_layer_train_f32, which also leaves out3, g_top [n, 4] (the gradient w.r.t. the logits, see `normalise` there)
+ * and the gradients of the top layer's fc_self.weight, fc_neigh.weight and bias in grads[5 (L - 1) + 2 .. + 4] (the other
+ * entries of `grads` are not touched).  top_workspace >= gts_sage_top_layer_train_workspace(n_rows, 256, 4) bytes.
+ * gts_sage_pool_stack_bwd_top_f32 is gts_sage_pool_stack_bwd_f32 with gout = g_top; with top_done = 1 it leaves those three
+ * gradients as they are (top_done = 0: the same call as gts_sage_pool_stack_bwd_f32).  Same bits as the calls they stand for. */
+int32_t gts_sage_pool_stack_train_fwd_f32(const int32_t* indptr, const int32_t* indices, const int32_t* sched_rec,
+                                          int64_t sched_clusters, int32_t sched_rows, int32_t sched_srcs,
+                                          int32_t sched_loc_words, const float* x, const float* const* params,
+                                          int64_t n_rows, const int64_t* widths, int32_t n_layers, int32_t arg_bytes,
+                                          int32_t relu_bits, void* arena, int64_t arena_bytes, const int64_t* labels,
+                                          const float* class_w, int32_t normalise, float* g_top, float* const* grads,
+                                          float* out3, float* top_workspace, int64_t top_workspace_bytes, void* stream);
+int32_t gts_sage_pool_stack_bwd_top_f32(const int32_t* t_indptr, const int32_t* t_indices, const int32_t* t_slot,
+                                        const int32_t* sched_rec, int64_t sched_clusters, int32_t sched_rows,
+                                        int32_t sched_srcs, int32_t sched_loc_words, const float* gout, const float* x,
+                                        const float* const* params, int64_t n_rows, const int64_t* widths,
+                                        int32_t n_layers, int32_t arg_bytes, int32_t relu_bits, const void* fwd_arena,
+                                        float* const* grads, float* gx, void* scratch, int64_t scratch_bytes,
+                                        int32_t top_done, void* stream);
 
 /* ---- class-weighted cross-entropy ----------------------------------------------------------
  * Replaces torch.nn.CrossEntropyLoss(weight=class_weights)(logits, labels) of the reference
