@@ -1,7 +1,8 @@
 """C1-C5 (csrc/gts_conv3d.hip) against torch CPU fp64: every launch of a refinement-CNN training step
 at volumes whose every voxel is near a boundary, a 48^3 brick and one crop above 2 M voxels, for the
 hyper-parameters' 8->16->4, the shipped checkpoint's 9->16->5 and an odd 3->7->2.  Tolerance as in
-test_gpu_gemm.py: |err| <= 2e-6 * bound, bound = the operation on absolute values."""
+test_gpu_gemm.py: |err| <= 2e-6 * bound, bound = the operation on absolute values.  The matrix of kernel
+instantiations, brick-edge volumes and weight-gradient split plans is in test_gpu_conv3d_edges.py."""
 import pytest
 import torch
 
