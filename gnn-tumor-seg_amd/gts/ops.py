@@ -1348,3 +1348,130 @@ def bias_apply(volume, tables, lattice, mean, want_field=False, out=None, grid_b
     check(_lib.load().gts_bias_apply(ptr(volume), code, *args, float(mean), ptr(out), ptr(field), int(grid_blocks),
                                      current_stream()), "gts_bias_apply")
     return (out, field) if want_field else out
+
+
+# ---------------------------------------------------------------- brain extraction
+BRAIN_BINS = _lib.const("GTS_BRAIN_BINS")
+BRAIN_MAX_R2 = _lib.const("GTS_BRAIN_MAX_R2")
+
+
+def _brain_volume(volume, what):
+    """(dtype code, X, Y, Z) of an intensity volume of three axes, the last contiguous."""
+    code = _moving_volume(volume, what)
+    return (code,) + tuple(int(n) for n in volume.shape)
+
+
+def _brain_mask(mask, what):
+    """(X, Y, Z) of an int16 mask of three axes on the device."""
+    if not isinstance(mask, torch.Tensor) or mask.dim() != 3 or mask.numel() == 0 or mask.dtype != torch.int16:
+        raise _lib.GtsError(f"{what} takes a non-empty int16 mask of three axes")
+    require_device(mask)
+    return tuple(int(n) for n in mask.shape)
+
+
+def _brain_workspace(shape, device, what):
+    size = int(_lib.load().gts_brainmask_workspace(*shape))
+    if size <= 0:
+        raise _lib.GtsError(f"{what}: volume {shape} is outside the kernels' limits (fewer than 2^31 voxels)")
+    return scratch(size, device, torch.uint8), size
+
+
+def brain_range(volume, grid_blocks=0):
+    """S1.  (n, hi): the number of voxels of the volume (int16 or float32, three axes) that are finite and > 0, and
+    their maximum as a Python float (0.0 when there is none).  One host synchronisation."""
+    import struct
+
+    code, x, y, z = _brain_volume(volume, "brain_range")
+    out = torch.empty(2, dtype=torch.int64, device=volume.device)
+    check(_lib.load().gts_brain_range(ptr(volume), code, x, y, z, ptr(out), int(grid_blocks), current_stream()),
+          "gts_brain_range")
+    n, bits = out.tolist()
+    return int(n), float(struct.unpack("<f", struct.pack("<I", bits))[0])
+
+
+def brain_histogram(volume, hi, grid_blocks=0):
+    """S2.  int64 [BRAIN_BINS] on the device: the finite voxels > 0 by min(BINS - 1, floor(float64(v) / hi * BINS)).
+    The counts do not depend on grid_blocks."""
+    code, x, y, z = _brain_volume(volume, "brain_histogram")
+    counts = torch.empty(BRAIN_BINS, dtype=torch.int64, device=volume.device)
+    check(_lib.load().gts_brain_histogram(ptr(volume), code, x, y, z, float(hi), ptr(counts), int(grid_blocks),
+                                          current_stream()), "gts_brain_histogram")
+    return counts
+
+
+def brain_threshold(volume, t, grid_blocks=0):
+    """S2.  (mask int16 0/1 of the volume's shape, count int64 device tensor [1]): finite, > 0 and float64(v) >= t."""
+    code, x, y, z = _brain_volume(volume, "brain_threshold")
+    mask = torch.empty(volume.shape, dtype=torch.int16, device=volume.device)
+    count = torch.empty(1, dtype=torch.int64, device=volume.device)
+    check(_lib.load().gts_brain_threshold(ptr(volume), code, x, y, z, float(t), ptr(mask), ptr(count), int(grid_blocks),
+                                          current_stream()), "gts_brain_threshold")
+    return mask, count
+
+
+def ball_morph(mask, r2, target, outside, invert, grid_blocks=0):
+    """S3.  int16 0/1: ((squared distance to the nearest voxel whose value (!= 0) equals `target` <= r2) != invert),
+    positions outside the volume counting as `target` iff `outside` (include/gts_hip.h)."""
+    shape = _brain_mask(mask, "ball_morph")
+    if int(r2) != r2 or not 0 <= int(r2) <= BRAIN_MAX_R2:
+        raise _lib.GtsError(f"ball_morph: squared radius {r2!r} is outside 0..{BRAIN_MAX_R2}")
+    ws, size = _brain_workspace(shape, mask.device, "ball_morph")
+    out = torch.empty_like(mask)
+    check(_lib.load().gts_ball_morph_i16(ptr(mask), *shape, int(r2), int(bool(target)), int(bool(outside)), ptr(out),
+                                         ptr(ws), size, int(bool(invert)), int(grid_blocks), current_stream()),
+          "gts_ball_morph_i16")
+    return out
+
+
+def ball_erode(mask, r2, border_value=0, grid_blocks=0):
+    """scipy.ndimage.binary_erosion(mask, ball(r2), border_value=border_value) as int16 0/1."""
+    return ball_morph(mask, r2, 0, not border_value, True, grid_blocks)
+
+
+def ball_dilate(mask, r2, grid_blocks=0):
+    """scipy.ndimage.binary_dilation(mask, ball(r2)) as int16 0/1."""
+    return ball_morph(mask, r2, 1, False, False, grid_blocks)
+
+
+def largest_component(mask, connectivity=6, grid_blocks=0):
+    """S4.  (keep int16 0/1, stats int64 device tensor [5] = components, voxels of the largest, of the second largest,
+    the winner's root, voxels of the mask): the component of mask != 0 with the most voxels, a tie going to the smaller root.  An empty
+    mask gives an empty keep and zeros; gts.brainmask.largest_component raises for it."""
+    shape = _brain_mask(mask, "largest_component")
+    if connectivity not in (6, 26):
+        raise _lib.GtsError(f"largest_component: connectivity {connectivity!r} (6 or 26)")
+    ws, size = _brain_workspace(shape, mask.device, "largest_component")
+    keep = torch.empty_like(mask)
+    stats = torch.empty(5, dtype=torch.int64, device=mask.device)
+    check(_lib.load().gts_largest_component_i16(ptr(mask), *shape, int(connectivity), ptr(keep), ptr(stats), ptr(ws),
+                                                size, int(grid_blocks), current_stream()), "gts_largest_component_i16")
+    return keep, stats
+
+
+def fill_holes(mask, grid_blocks=0):
+    """S5.  (filled int16 0/1, stats int64 device tensor [2] = voxels of the result, voxels filled):
+    scipy.ndimage.binary_fill_holes."""
+    shape = _brain_mask(mask, "fill_holes")
+    ws, size = _brain_workspace(shape, mask.device, "fill_holes")
+    out = torch.empty_like(mask)
+    stats = torch.empty(2, dtype=torch.int64, device=mask.device)
+    check(_lib.load().gts_fill_holes_i16(ptr(mask), *shape, ptr(out), ptr(stats), ptr(ws), size, int(grid_blocks),
+                                         current_stream()), "gts_fill_holes_i16")
+    return out, stats
+
+
+def apply_mask(scan, mask, grid_blocks=0):
+    """S6.  (masked scan of scan's dtype, count int64 device tensor [1]): scan ([C, *mask.shape] or mask's shape, int16
+    or float32) where mask != 0, 0 elsewhere (NaN and Inf included)."""
+    shape = _brain_mask(mask, "apply_mask")
+    if not isinstance(scan, torch.Tensor) or scan.dtype not in _VOLUME_CODES:
+        raise _lib.GtsError("apply_mask takes an int16 or float32 tensor")
+    if tuple(scan.shape[-3:]) != shape or scan.dim() not in (3, 4) or scan.numel() == 0:
+        raise _lib.GtsError(f"apply_mask: scan {tuple(scan.shape)} does not lie over the mask {shape}")
+    require_device(scan, mask)
+    channels = int(scan.shape[0]) if scan.dim() == 4 else 1
+    out = torch.empty_like(scan)
+    count = torch.empty(1, dtype=torch.int64, device=mask.device)
+    check(_lib.load().gts_apply_mask(ptr(scan), _VOLUME_CODES[scan.dtype], channels, *shape, ptr(mask), ptr(out),
+                                     ptr(count), int(grid_blocks), current_stream()), "gts_apply_mask")
+    return out, count

@@ -64,3 +64,64 @@ def make_prediction(seed, shape=BRATS_SHAPE, n_blobs=3, salt=0.001):
     noise = rng.random(shape, dtype=np.float32) < salt
     labels[noise] = rng.choice(np.array([1, 2, 4], dtype=np.int16), size=int(noise.sum()))
     return labels
+
+
+HEAD_SCALE = 0.8                                   # the head phantom's brain radii against make_sample's: room for the scalp
+HEAD_SHELLS = (1.08, 1.23, 1.45)                   # outer radius of CSF, skull and scalp in units of the brain's
+HEAD_CSF, HEAD_SKULL, HEAD_SCALP, HEAD_POCKET = 130.0, 18.0, 760.0, 35.0
+
+
+def make_head_sample(seed, shape=BRATS_SHAPE):
+    """(intensities float32 [X, Y, Z, 4], labels int16 [X, Y, Z] in {0, 1, 2, 4}, intracranial bool [X, Y, Z]): a scan
+    with its skull on, for gts.brainmask.  The brain and tumour are make_sample's recipe with the radii scaled by
+    HEAD_SCALE, inside a CSF shell, a dark skull shell and a bright scalp shell (HEAD_SHELLS: their thicknesses scale
+    with the shape), two tissue bridges two voxels wide through CSF and skull (emissary-vessel style: what makes a plain
+    threshold-and-largest-component keep the scalp), a dark CSF pocket inside the brain and positive noise in the air.
+    intracranial = brain + CSF shell: what a brain mask should be."""
+    rng = np.random.default_rng(seed)
+    axes = [np.linspace(-1.0, 1.0, n, dtype=np.float32) for n in shape]
+    x, y, z = np.meshgrid(*axes, indexing="ij")
+    r = rng.uniform(0.6, 0.75, 3).astype(np.float32) * np.float32(HEAD_SCALE)
+    q = (x / r[0]) ** 2 + (y / r[1]) ** 2 + (z / r[2]) ** 2
+    brain = q < 1.0
+    csf, skull, scalp = (q < np.float32(s * s) for s in HEAD_SHELLS)
+    c = rng.uniform(-0.25, 0.25, 3).astype(np.float32) * np.float32(HEAD_SCALE)
+    d2 = (x - c[0]) ** 2 + (y - c[1]) ** 2 + (z - c[2]) ** 2
+    core, tumour, edema = d2 < 0.006, d2 < 0.02, d2 < 0.045
+    pocket = ((x + c[0]) ** 2 + (y + c[1]) ** 2 + (z - np.float32(0.5) * c[2]) ** 2 < 0.004) & brain & ~edema
+    ix, iy, iz = np.meshgrid(*[np.arange(n) for n in shape], indexing="ij")
+    mid = [n // 2 for n in shape]
+    two = lambda i, m: (i == m) | (i == m + 1)      # noqa: E731
+    bridge = ((two(iy, mid[1]) & two(iz, mid[2]) & (ix > mid[0])) | (two(ix, mid[0]) & two(iz, mid[2]) & (iy < mid[1])))
+    bridge &= skull & ~brain
+    img = np.zeros(shape + (4,), dtype=np.float32)
+    for m in range(4):
+        base = 300.0 + 80.0 * m + 60.0 * np.sin(4.0 * x + m) * np.cos(3.0 * y)
+        noise = rng.standard_normal(shape, dtype=np.float32)
+        v = base + 25.0 * noise + 250.0 * edema + 200.0 * tumour
+        air = np.rint(np.abs(6.0 * noise))
+        head = np.where(brain | bridge, v, np.where(csf, HEAD_CSF + 10.0 * noise, np.where(
+            skull, HEAD_SKULL + 4.0 * noise, HEAD_SCALP + 40.0 * m + 30.0 * noise)))
+        head = np.where(pocket, HEAD_POCKET + 5.0 * noise, head)
+        img[..., m] = np.where(scalp, np.rint(np.maximum(head, 1.0)), air)
+    labels = np.zeros(shape, dtype=np.int16)
+    labels[brain & edema] = 2
+    labels[brain & tumour] = 4
+    labels[brain & core] = 1
+    return img, labels, np.ascontiguousarray(csf)
+
+
+def write_head_sample(root, sample_id, seed, shape=BRATS_SHAPE, label_ext="_seg.nii.gz", mask_ext=None):
+    """Write one head phantom as BraTS NIfTI files (int16) under root/sample_id/, with mask_ext also the true
+    intracranial mask; returns (the folder, the intracranial mask)."""
+    from data_processing.nifti_io import save_as_nifti
+
+    img, labels, intracranial = make_head_sample(seed, shape)
+    folder = os.path.join(root, sample_id)
+    os.makedirs(folder, exist_ok=True)
+    for m, ext in enumerate(MODALITY_EXTS):
+        save_as_nifti(img[..., m].astype(np.int16), os.path.join(folder, sample_id + ext))
+    save_as_nifti(labels, os.path.join(folder, sample_id + label_ext))
+    if mask_ext:
+        save_as_nifti(intracranial.astype(np.int16), os.path.join(folder, sample_id + mask_ext))
+    return folder, intracranial

@@ -5,7 +5,7 @@ For every scan under SCANS (found as scripts.segment_scans finds them) each moda
 stored (int16 or float32), corrected on the device on its own grid and written as float32 to OUT/{id}/ under its own
 file name with the input's own affine.  --save_field also writes the estimated field as a ratio (the factor the
 volume was divided by), {name}_biasfield.nii.gz.  The mask the field is estimated from is every voxel above
---bias_threshold (default 0): meant for skull-stripped scans.  A scan that raises is reported and skipped; the exit
+--bias_threshold (default 0): strip the skull first (scripts.skull_strip).  A scan that raises is reported and skipped; the exit
 status is 1 when any scan was skipped.
 
     python -m scripts.bias_correct -d SCANS -o OUT [--save_field] [--bias_levels L --bias_spans S --bias_iterations N

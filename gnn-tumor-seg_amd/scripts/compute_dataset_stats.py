@@ -17,7 +17,8 @@ the exit status is 1 when any scan was left out.
 
 --bias_correct (and the --bias_* settings, as scripts.segment_scans documents them) removes each modality's bias field
 on the device (gts.bias) before the statistics are taken, for datasets that are preprocessed and
-segmented with the same flag.
+segmented with the same flag.  --skull_strip [MODALITY] (and the --strip_* settings) sets every modality to 0 outside a
+brain mask found on the device (gts.brainmask) before that, for scans that still hold their skull.
 """
 import argparse
 import os
@@ -48,9 +49,9 @@ def build_parser():
                         help="file suffix of the label volume (required: the statistics are taken over healthy tissue)")
     parser.add_argument("-p", "--data_prefix", default="", help="common prefix of the scan folders, e.g. BraTS2021")
     parser.add_argument("-o", "--output", default=None, type=str, help="the statistics file to write (JSON)")
-    from gts import bias
+    from gts import bias, brainmask
 
-    return bias.add_flags(parser)
+    return brainmask.add_flags(bias.add_flags(parser))
 
 
 def check_request(modality_extensions, label_extension):
@@ -72,11 +73,13 @@ def load_scan(folder, modality_extensions, label_extension):
     return staged, dataset_stats.stage_labels(nifti_io.read_in_labels(folder, label_extension))
 
 
-def compute(scans, modality_extensions, label_extension, q=QUANTILE, bias_settings=None, bias_report=None):
+def compute(scans, modality_extensions, label_extension, q=QUANTILE, bias_settings=None, bias_report=None,
+            strip_settings=None, strip_report=None):
     """Per-scan statistics of {id: folder}: ({id: ScanStats}, ids left out).  bias_settings: gts.bias.correct_volume's
     settings, to correct every modality on the device first (None: the values as stored); bias_report, a dict,
-    receives the correction's per-modality reports by scan id."""
-    from gts import bias, dataset_stats, intake
+    receives the correction's per-modality reports by scan id.  strip_settings: gts.brainmask.settings_from_args' pair,
+    to strip the skull on the device before that; strip_report receives the masks' reports."""
+    from gts import bias, brainmask, dataset_stats, intake
 
     check_request(modality_extensions, label_extension)
     ids = sorted(scans)
@@ -91,6 +94,11 @@ def compute(scans, modality_extensions, label_extension, q=QUANTILE, bias_settin
                 pending[i + READ_AHEAD] = submit(i + READ_AHEAD)
             try:
                 staged, labels = pending.pop(i).result()
+                if strip_settings is not None:
+                    staged, _, found = brainmask.strip_scan(staged.to(intake._device(), non_blocking=True),
+                                                            strip_settings[0], **strip_settings[1])
+                    if strip_report is not None:
+                        strip_report[scan_id] = found
                 if bias_settings is not None:
                     staged, reports = bias.correct_scan(staged.to(intake._device(), non_blocking=True), **bias_settings)
                     if bias_report is not None:
@@ -103,12 +111,13 @@ def compute(scans, modality_extensions, label_extension, q=QUANTILE, bias_settin
 
 
 def compute_and_save(scans, modality_extensions, label_extension, path, q=QUANTILE, bias_settings=None,
-                     bias_report=None):
+                     bias_report=None, strip_settings=None, strip_report=None):
     """compute, then the medians into the file at path: (mean, std, ids left out).  StatsError when no
     scan gave statistics (nothing is written then)."""
     from gts import dataset_stats
 
-    per_scan, failed = compute(scans, modality_extensions, label_extension, q, bias_settings, bias_report)
+    per_scan, failed = compute(scans, modality_extensions, label_extension, q, bias_settings, bias_report,
+                               strip_settings, strip_report)
     if not per_scan:
         raise standardization.StatsError(f"none of the {len(scans)} scan(s) gave statistics")
     mean, std = dataset_stats.dataset_stats([per_scan[s] for s in sorted(per_scan)])
@@ -126,24 +135,29 @@ def main(argv=None):
         check_request(args.modality_extensions, args.label_extension)
     except standardization.StatsError as exc:
         parser.error(str(exc))
-    from gts import bias
+    from gts import bias, brainmask
 
     try:
         settings = bias.settings_from_args(args)
+        strip = brainmask.settings_from_args(args)
     except ValueError as exc:
         parser.error(str(exc))
-    report = {}
+    report, strip_report = {}, {}
     scans = prep.find_scans(args.data_dir or Filepaths.INPUT_MRI_DIR, args.data_prefix)
     print(f"{len(scans)} scan folders found; statistics go to {args.output}")
     try:
         mean, std, failed = compute_and_save(scans, args.modality_extensions, args.label_extension,
                                              os.path.expanduser(args.output), bias_settings=settings,
-                                             bias_report=report)
+                                             bias_report=report, strip_settings=strip, strip_report=strip_report)
     except standardization.StatsError as exc:
         print(f"no statistics written: {exc}")
         return 1
     if args.bias_report:
         bias.save_report(args.bias_report, args.modality_extensions, settings, report)
+    if args.strip_report:
+        brainmask.save_report(args.strip_report, args.modality_extensions, strip[0], strip[1], strip_report)
+    for scan_id in sorted(strip_report):
+        print(f"{scan_id}: {brainmask.describe(strip_report[scan_id])}")
     print(f"mean {mean.tolist()}, standard deviation {std.tolist()} over {len(scans) - len(failed)} scan(s), "
           f"{len(failed)} left out")
     return 1 if failed else 0

@@ -22,6 +22,10 @@ OUT_DIR/standardization.json.
 scripts.segment_scans documents them) removes each modality's bias field on the device (gts.bias)
 before the crop, the normalization and, with --stats compute, the statistics: the graphs a model is trained on then
 see the correction that `segment_scans --bias_correct` applies to the scans it segments.
+
+--skull_strip [MODALITY] (with --strip_radius, --strip_close, --strip_fraction, --strip_connectivity, --strip_report, as
+scripts.segment_scans documents them) sets every modality to 0 outside a brain mask found on the device (gts.brainmask,
+DESIGN.md 4x) before all of that, --bias_correct included, for scans that still hold their skull.
 """
 import argparse
 import glob
@@ -70,9 +74,9 @@ def build_parser():
     parser.add_argument("--stats", default=None, metavar="STATS.json|compute",
                         help="standardization statistics: a file of scripts.compute_dataset_stats, or 'compute' to take "
                              "them over the input folder first (default: the BraTS-2021 constants)")
-    from gts import bias
+    from gts import bias, brainmask
 
-    return bias.add_flags(parser)
+    return brainmask.add_flags(bias.add_flags(parser))
 
 
 def default_output_dir(args):
@@ -96,10 +100,12 @@ class DataPreprocessor:
         self.scans = find_scans(args.data_dir or Filepaths.INPUT_MRI_DIR, args.data_prefix)
         self.all_ids = sorted(self.scans)
         self.stats_failed = []
-        from gts import bias
+        from gts import bias, brainmask
 
         self.bias = bias.settings_from_args(args)       # None without --bias_correct
         self.bias_report = {}
+        self.strip = brainmask.settings_from_args(args)  # None without --skull_strip
+        self.strip_report = {}
         self.mean, self.std = self.standardization_stats(getattr(args, "stats", None))
         print(f"{len(self.all_ids)} scan folders found; graphs go to {self.output_dir}")
 
@@ -113,7 +119,8 @@ class DataPreprocessor:
 
         path = os.path.join(self.output_dir, standardization.FILE_NAME)
         mean, std, self.stats_failed = compute_dataset_stats.compute_and_save(
-            self.scans, self.args.modality_extensions, self.args.label_extension, path, bias_settings=self.bias)
+            self.scans, self.args.modality_extensions, self.args.label_extension, path, bias_settings=self.bias,
+            strip_settings=self.strip)
         print(f"standardization statistics over {len(self.scans) - len(self.stats_failed)} scan(s) written to {path}")
         return standardization.load_stats(path, self.args.modality_extensions)
 
@@ -121,7 +128,8 @@ class DataPreprocessor:
         """Host stage: decode, crop, relabel, normalize, standardize."""
         folder = self.scans[scan_id]
         image = nifti_io.read_in_patient_sample(folder, self.args.modality_extensions)
-        if self.bias is not None:       # corrected on the device first: run() calls finish() for the rest of this stage
+        if self.bias is not None or self.strip is not None:     # stripped / corrected on the device first: run() calls
+            # finish() for the rest of this stage
             labels = nifti_io.read_in_labels(folder, self.args.label_extension) if self.args.label_extension else None
             return image, labels, None
         crop = determine_brain_crop(image)
@@ -132,10 +140,14 @@ class DataPreprocessor:
         return image, labels, crop
 
     def finish(self, scan_id, image, labels):
-        """With --bias_correct: the correction on the device, then what load() does to an uncorrected scan."""
-        from gts import bias
+        """With --skull_strip or --bias_correct: the strip, then the correction, on the device, then what load() does to
+        a scan taken as stored."""
+        from gts import bias, brainmask
 
-        image, self.bias_report[scan_id] = bias.correct_image(image, **self.bias)
+        if self.strip is not None:
+            image, _, self.strip_report[scan_id] = brainmask.strip_image(image, self.strip[0], **self.strip[1])
+        if self.bias is not None:
+            image, self.bias_report[scan_id] = bias.correct_image(image, **self.bias)
         crop = determine_brain_crop(image)
         if labels is not None:
             labels = swap_labels_from_brats(labels[crop])
@@ -154,7 +166,7 @@ class DataPreprocessor:
 
     def run(self):
         """Process every scan; returns the ids that failed."""
-        from gts import bias
+        from gts import bias, brainmask
         from mri2graph.graphgen import img2graph
 
         failed, writes = [], []
@@ -177,13 +189,17 @@ class DataPreprocessor:
             for scan_id, job in writes:
                 try:
                     job.result()
-                    note = f" ({bias.describe(self.bias_report[scan_id])})" if scan_id in self.bias_report else ""
+                    note = f" ({brainmask.describe(self.strip_report[scan_id])})" if scan_id in self.strip_report else ""
+                    note += f" ({bias.describe(self.bias_report[scan_id])})" if scan_id in self.bias_report else ""
                     print(f"{scan_id}: done{note}")
                 except Exception as exc:
                     print(f"{scan_id}: writing failed ({exc!r})")
                     failed.append(scan_id)
         if getattr(self.args, "bias_report", None):
             bias.save_report(self.args.bias_report, self.args.modality_extensions, self.bias, self.bias_report)
+        if getattr(self.args, "strip_report", None):
+            brainmask.save_report(self.args.strip_report, self.args.modality_extensions, self.strip[0], self.strip[1],
+                                  self.strip_report)
         return failed
 
 
@@ -191,7 +207,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     try:
         gen = DataPreprocessor(args)
-    except ValueError as exc:                   # --bias_* settings that cannot run
+    except ValueError as exc:                   # --bias_* or --strip_* settings that cannot run
         print(f"preprocess_dataset: {exc}", file=sys.stderr)
         return 2
     except standardization.StatsError as exc:   # a statistics file that does not fit this run, or none could be computed

@@ -22,6 +22,8 @@ A scan that raises is reported and skipped; the exit status is 1 when any scan w
                                     [--uncertainty_dir DIR]
                                     [--bias_correct [--bias_levels L --bias_spans S --bias_iterations N --bias_tol T
                                      --bias_threshold V --bias_report FILE.json]]
+                                    [--skull_strip [MODALITY] [--strip_radius R --strip_close R --strip_fraction F
+                                     --strip_connectivity {6,26} --strip_report FILE.json --strip_mask_dir DIR]]
 
 --also_gnn_weights / --also_cnn_weights name further members (the other folds' weight files, paired in order) and
 --tta_mirror AXES (a non-empty subset of xyz) adds the CNN's mirrored views: class probabilities are averaged over
@@ -67,13 +69,27 @@ translation and rotation.
 --bias_correct removes each modality's bias field, the slow multiplicative intensity inhomogeneity of a scan as the
 scanner writes it, on the device (gts.bias, DESIGN.md 4w: N4's scheme of histogram sharpening and multilevel B-spline
 fitting) after --conform / --coregister or the plain upload and before the intake, once per modality.  The mask the
-field is estimated from is every voxel above --bias_threshold (default 0): meant for skull-stripped scans, whose
-background is 0.  --bias_levels lattices, the coarsest with --bias_spans cells per axis and each finer one with twice
+field is estimated from is every voxel above --bias_threshold (default 0): for a scan with its skull on, give
+--skull_strip too, which runs first and leaves 0 outside the brain.  --bias_levels lattices, the coarsest with --bias_spans cells per axis and each finer one with twice
 as many (at most 32), are fitted for at most --bias_iterations rounds each, a level ending early when no control point
 moves by --bias_tol.  --bias_report FILE.json writes the rounds run, the last change and the field's range per scan
 and modality; the scan's line of output names the field's range.  scripts.preprocess_dataset and
 scripts.compute_dataset_stats take the same flags: the graphs and the statistics a model is trained on should see the
 correction its scans will see here.  Without the flag nothing changes.
+
+--skull_strip [MODALITY] sets every modality to 0 outside a brain mask found on the device (gts.brainmask, DESIGN.md 4x:
+a threshold from the robust range of the positive voxels, an erosion by a ball, the largest connected component, a
+dilation by the same ball, a closing and a hole fill), after --conform / --coregister or the plain upload and before
+--bias_correct and the intake, which take their masks, crops and quantiles from the voxels that are not 0.  MODALITY is
+the extension of the modality the mask is found from (default: _t1.nii.gz when it is among the extensions, else the
+first).  --strip_radius and --strip_close are the radii of the two balls in voxels of the grid the step sees
+(millimetres after --conform), --strip_fraction places the threshold between the 2nd and the 98th percentile,
+--strip_connectivity is that of the component kept.  --strip_report FILE.json writes the threshold and the voxel counts
+of every step per scan; the scan's line of output names the mask's volume, and says "check this scan" when a second
+component has at least half the voxels of the one kept.  --strip_mask_dir DIR writes DIR/{id}_brainmask.nii.gz (int16
+0/1) on the grid and with the affine of the label file.  scripts.preprocess_dataset and scripts.compute_dataset_stats
+take the same flags; scripts.skull_strip does only this step.  The scheme is this project's own definition: it has not
+been run on real anatomy, and agreement with BET, HD-BET or ROBEX is unknown.  Without the flag nothing changes.
 """
 import argparse
 import os
@@ -91,7 +107,7 @@ from data_processing import nifti_io, standardization  # noqa: E402
 from data_processing.image_processing import (uncrop_maps_to_brats_size, uncrop_to_brats_size,  # noqa: E402
                                               uncrop_to_shape)
 from data_processing.labels import INTERNAL_TO_BRATS  # noqa: E402
-from gts import bias, conform, graphgen, intake, ops, register  # noqa: E402
+from gts import bias, brainmask, conform, graphgen, intake, ops, register  # noqa: E402
 from scripts import cleanup as cleanup_flags  # noqa: E402
 from scripts import ensemble_flags  # noqa: E402
 from scripts import preprocess_dataset as prep  # noqa: E402
@@ -137,15 +153,20 @@ def build_parser():
                         help="bound on each rotation angle of the search")
     parser.add_argument("--coregister_report", default=None, metavar="FILE.json",
                         help="write the parameters, scores and launch counts found per scan and modality")
+    brainmask.add_flags(parser)
+    parser.add_argument("--strip_mask_dir", default=None, metavar="DIR",
+                        help="with --skull_strip: write {id}_brainmask.nii.gz (int16 0/1) on the label file's grid")
     return bias.add_flags(ensemble_flags.add_flags(cleanup_flags.add_flags(parser)))
 
 
 def parse_args(argv=None):
     """The parsed flags, --coregister resolved: it turns --conform on and names the reference modality's index
     (args.coregister_ref; None without the flag), and the --bias_* flags as args.bias (None without --bias_correct,
-    else gts.bias.correct_volume's settings).  Raises ValueError for flags that do not go together or cannot run."""
+    else gts.bias.correct_volume's settings), the --strip_* flags as args.strip (None without --skull_strip, else the
+    index of the modality the mask is found from and gts.brainmask.brain_mask's settings).  Raises ValueError for flags that do not go together or cannot run."""
     args = build_parser().parse_args(argv)
     args.bias = bias.settings_from_args(args)
+    args.strip = brainmask.settings_from_args(args)
     args.coregister_ref = None
     if args.coregister is None:
         if args.coregister_header_only or args.coregister_report:
@@ -196,6 +217,10 @@ class Segmenter:
         self.coregister_report = {}                                     # scan id -> per-modality findings
         self.bias = getattr(args, "bias", None)                         # None: intensities are taken as stored
         self.bias_report = {}                                           # scan id -> per-modality reports
+        self.strip = getattr(args, "strip", None)                       # None: the scans are taken as skull-stripped
+        self.strip_report = {}                                          # scan id -> the mask's report
+        self.strip_mask_dir = getattr(args, "strip_mask_dir", None)
+        self.last_mask = None                   # the brain mask of the scan segment() saw last, on the label file's grid
         if getattr(args, "stats", None):
             self.mean, self.std = standardization.load_stats(os.path.expanduser(args.stats), args.modality_extensions)
         else:
@@ -265,6 +290,12 @@ class Segmenter:
             staged, plan, _ = staged
             staged = conform.conform_scan(staged.to(self.device, non_blocking=True), plan)
             tick("conform")
+        if self.strip is not None:
+            staged, mask, self.last_strip = brainmask.strip_scan(staged.to(self.device, non_blocking=True), self.strip[0],
+                                                                 **self.strip[1])
+            tick("strip")
+            if self.strip_mask_dir:
+                self.last_mask = self.mask_on_scan_grid(mask, plan)
         if self.bias is not None:
             staged, self.last_bias = bias.correct_scan(staged.to(self.device, non_blocking=True), **self.bias)
             tick("bias")
@@ -309,9 +340,19 @@ class Segmenter:
         tick("unconform")
         return back.cpu().numpy().T          # [X, Y, Z], x fastest: the order the file stores
 
-    def store(self, scan_id, volume, affine=nifti_io.BRATS_AFFINE, maps=None):
+    def mask_on_scan_grid(self, mask, plan):
+        """The brain mask [Z, Y, X] of the frame the step saw -> int16 [X, Y, Z] on the grid the labels are written on."""
+        if plan is None or plan.is_identity:
+            return mask.cpu().numpy().T
+        return conform.unconform_labels(mask, plan).cpu().numpy().T
+
+    def store(self, scan_id, volume, affine=nifti_io.BRATS_AFFINE, maps=None, mask=None):
         """Host stage: gzip NIfTI encode."""
         nifti_io.save_as_nifti(volume, os.path.join(self.output_dir, scan_id + ".nii.gz"), affine)
+        if mask is not None:
+            os.makedirs(os.path.expanduser(self.strip_mask_dir), exist_ok=True)
+            nifti_io.save_as_nifti(mask, os.path.join(os.path.expanduser(self.strip_mask_dir),
+                                                      scan_id + brainmask.MASK_SUFFIX), affine)
         if maps is not None:
             ensemble_flags.save_uncertainty_maps(self.uncertainty_dir, scan_id, maps, affine)
 
@@ -330,12 +371,16 @@ class Segmenter:
                     staged = pending.pop(i).result()
                     volume = self.segment(staged)
                     maps = self.last_uncertainty if self.uncertainty_dir else None
+                    mask = self.last_mask if self.strip_mask_dir else None
                     note = f" ({self.cleanup.report()})" if self.cleanup is not None else ""
                     if self.coregister_ref is not None:
                         self.coregister_report[scan_id] = self.last_registration
                         note += f" ({self.last_plan.describe()}) ({self.registration_note()})"
                     elif self.conform:
                         note += f" ({staged[1].describe()})"
+                    if self.strip is not None:
+                        self.strip_report[scan_id] = self.last_strip
+                        note += f" ({brainmask.describe(self.last_strip)})"
                     if self.bias is not None:
                         self.bias_report[scan_id] = self.last_bias
                         note += f" ({bias.describe(self.last_bias)})"
@@ -347,7 +392,7 @@ class Segmenter:
                     affine = staged[2][self.coregister_ref]
                 else:
                     affine = staged[2] if self.conform else nifti_io.BRATS_AFFINE
-                writes.append((scan_id, note, pool.submit(self.store, scan_id, volume, affine, maps)))
+                writes.append((scan_id, note, pool.submit(self.store, scan_id, volume, affine, maps, mask)))
             for scan_id, note, job in writes:
                 try:
                     job.result()
@@ -365,6 +410,9 @@ class Segmenter:
                 f.write("\n")
         if getattr(self.args, "bias_report", None):
             bias.save_report(self.args.bias_report, self.args.modality_extensions, self.bias, self.bias_report)
+        if getattr(self.args, "strip_report", None):
+            brainmask.save_report(self.args.strip_report, self.args.modality_extensions, self.strip[0], self.strip[1],
+                                  self.strip_report)
         return failed
 
     def registration_note(self):

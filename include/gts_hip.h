@@ -1161,6 +1161,53 @@ int32_t gts_bias_apply(const void* src, int32_t dtype, int64_t X, int64_t Y, int
                        const int32_t* cells, const double* lattice, int64_t spans0, int64_t levels, double mean,
                        float* out, float* field_out, int64_t grid_blocks, void* stream);
 
+/* ---- S1-S6: morphological brain extraction of one MRI volume (no counterpart in the reference) -----
+ * A volume of three axes [X][Y][Z], Z contiguous; the scheme is symmetric in the axes, so a tensor's shape is handed
+ * over as it is.  Intensities by their NIfTI code 4 (int16) or 16 (float32), else GTS_ERR_ARGKIND; masks are int16,
+ * read as != 0 and written as 0 / 1.  Every extent >= 1 and X * Y * Z < 2^31, else GTS_ERR_SHAPE.  grid_blocks:
+ * workgroups of the passes over the voxels (0: the library's choice, else 1 .. 2^31 - 1, else GTS_ERR_SHAPE); every
+ * result is an integer or a copied value and depends neither on it nor on scheduling.  workspace:
+ * gts_brainmask_workspace(X, Y, Z) bytes (0 for a rejected shape), one size for S3-S5; a smaller one: GTS_ERR_SHAPE.
+ * Nothing is launched for a rejected argument.  P = the voxels that are finite and > 0.
+ * gts_brain_range (S1): out (device uint64 [2]) = { |P|, the bits of float32(max over P) (0 for an empty P) }.
+ * gts_brain_histogram (S2): counts (device int64 [GTS_BRAIN_BINS], zeroed by the call): one count per voxel of P at
+ *   min(BINS - 1, floor(float64(v) / hi * BINS)).  hi finite and > 0, else GTS_ERR_ARGKIND.  LDS integer tables,
+ *   one integer global atomic per non-empty bin and workgroup.
+ * gts_brain_threshold (S2): mask = (v in P and float64(v) >= t), *count (device) = its voxels.  t finite and >= 0,
+ *   else GTS_ERR_ARGKIND.
+ * gts_ball_morph_i16 (S3): mask_out (may be mask_in) = ((the squared distance, in voxels, from the voxel to the
+ *   nearest position whose mask value (!= 0) equals `target` is <= R2) != invert); positions outside the volume count
+ *   as `target` iff `outside`.  Dilation by the ball |o|^2 <= R2: (target 1, outside 0, invert 0); erosion with the
+ *   outside as background: (0, 1, 1), as foreground: (0, 0, 1).  0 <= R2 <= GTS_BRAIN_MAX_R2 and target, outside,
+ *   invert in {0, 1}, else GTS_ERR_ARGKIND.  Three exact passes with a window of floor(sqrt(R2)) voxels.
+ * gts_largest_component_i16 (S4): keep_out (may be mask) = the component of mask != 0 with the most voxels, a tie
+ *   going to the smaller root of gts_components_roots_i16; connectivity 6 or 26, else GTS_ERR_SHAPE.
+ *   stats (device int64 [5]) = { components, voxels of the largest, of the second largest (0 if none), the winner's
+ *   root (0 for an empty mask, keep_out then all 0), voxels of the mask }.
+ * gts_fill_holes_i16 (S5): mask_out (another buffer) = mask or every voxel of a connectivity-6 component of mask == 0
+ *   that has no voxel on a face of the volume.  stats (device int64 [2]) = { voxels of mask_out, voxels filled }.
+ * gts_apply_mask (S6): src and dst [C][X][Y][Z] of one dtype (two buffers), 1 <= C <= 64 else GTS_ERR_SHAPE:
+ *   dst = src where mask != 0, 0 (also for NaN / Inf) elsewhere; *count (device) = the voxels of the mask. */
+#define GTS_BRAIN_BINS 4096
+#define GTS_BRAIN_MAX_R2 255
+int64_t gts_brainmask_workspace(int64_t X, int64_t Y, int64_t Z);
+int32_t gts_brain_range(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, uint64_t* out,
+                        int64_t grid_blocks, void* stream);
+int32_t gts_brain_histogram(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, double hi, int64_t* counts,
+                            int64_t grid_blocks, void* stream);
+int32_t gts_brain_threshold(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, double t, int16_t* mask,
+                            uint64_t* count, int64_t grid_blocks, void* stream);
+int32_t gts_ball_morph_i16(const int16_t* mask_in, int64_t X, int64_t Y, int64_t Z, int32_t R2, int32_t target,
+                           int32_t outside, int16_t* mask_out, void* workspace, int64_t workspace_bytes, int32_t invert,
+                           int64_t grid_blocks, void* stream);
+int32_t gts_largest_component_i16(const int16_t* mask, int64_t X, int64_t Y, int64_t Z, int32_t connectivity,
+                                  int16_t* keep_out, int64_t* stats, void* workspace, int64_t workspace_bytes,
+                                  int64_t grid_blocks, void* stream);
+int32_t gts_fill_holes_i16(const int16_t* mask, int64_t X, int64_t Y, int64_t Z, int16_t* mask_out, int64_t* stats,
+                           void* workspace, int64_t workspace_bytes, int64_t grid_blocks, void* stream);
+int32_t gts_apply_mask(const void* src, int32_t dtype, int64_t C, int64_t X, int64_t Y, int64_t Z, const int16_t* mask,
+                       void* dst, uint64_t* count, int64_t grid_blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
