@@ -39,18 +39,16 @@
 
 #include <algorithm>
 
-#include "gts_volume.h"
+#include "gts_scan.h"
 
 namespace gts {
 namespace {
 
-constexpr int64_t kMaxExtent = 65535;
 constexpr int kMaxSpans = GTS_BIAS_MAX_SPANS;
 constexpr int kMaxLevels = 6;                  // spans0 << (levels - 1) <= 32
 constexpr int kMaxCoefs = 96;                  // sum over the levels of spans + 3 <= 63 + 18
 constexpr int kBins = GTS_BIAS_BINS;
 constexpr int kMaxGrid = 4096;
-constexpr int32_t kI16 = 4, kF32 = 16;         // NIfTI datatype codes
 
 // The first member of every row kernel's argument struct.
 struct Basis {
@@ -131,17 +129,8 @@ __device__ __forceinline__ void for_each_row(const Basis& b, Row&& row) {
   }
 }
 
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
-  return v;
-}
+__device__ __forceinline__ double wave_min(double v) { return wave_reduce(v, [](double a, double b) { return fmin(a, b); }); }
+__device__ __forceinline__ double wave_max(double v) { return wave_reduce(v, [](double a, double b) { return fmax(a, b); }); }
 
 // ------------------------------------------------------------------ Z1
 template <typename T>
@@ -151,7 +140,7 @@ __global__ __launch_bounds__(kBlock) void bias_log_kernel(const T* __restrict__ 
   unsigned mine[1] = {0};
   for (int64_t i = int64_t{blockIdx.x} * kBlock + threadIdx.x; i < vol; i += int64_t{gridDim.x} * kBlock) {
     const double v = static_cast<double>(src[i]);
-    const bool member = (v - v == 0.0) && v > threshold;
+    const bool member = is_finite(v) && v > threshold;
     u[i] = member ? static_cast<float>(log(v)) : __builtin_nanf("");
     mine[0] += member ? 1u : 0u;
   }
@@ -218,8 +207,7 @@ struct HistArgs {
 
 __global__ __launch_bounds__(kBlock) void bias_histogram_kernel(const HistArgs p) {
   __shared__ unsigned hist[kBins];
-  for (int i = threadIdx.x; i < kBins; i += kBlock) hist[i] = 0;
-  __syncthreads();
+  block_hist_clear(hist, kBins);
   const int lane = threadIdx.x & (kWave - 1);
   for_each_row(p.b, [&](int64_t r, int, int, const double* coef) {
     const float* __restrict__ u = p.u + r * p.b.X;
@@ -232,9 +220,7 @@ __global__ __launch_bounds__(kBlock) void bias_histogram_kernel(const HistArgs p
       }
     }
   });
-  __syncthreads();
-  for (int i = threadIdx.x; i < kBins; i += kBlock)
-    if (hist[i]) atomicAdd(&p.counts[i], static_cast<unsigned long long>(hist[i]));
+  block_hist_flush(hist, kBins, p.counts);
 }
 
 // ------------------------------------------------------------------ Z4
@@ -420,17 +406,9 @@ inline Layout layout(int64_t Y, int64_t Z, int64_t spans) {
   return l;
 }
 
-inline bool extents_ok(int64_t X, int64_t Y, int64_t Z) {
-  int64_t n;
-  return X >= 1 && Y >= 1 && Z >= 1 && X <= kMaxExtent && Y <= kMaxExtent && Z <= kMaxExtent &&
-         volume_voxels(X, Y, Z, false, &n);
-}
-
 inline bool levels_ok(int64_t spans0, int64_t levels) {
   return spans0 >= 1 && levels >= 1 && levels <= kMaxLevels && (spans0 << (levels - 1)) <= kMaxSpans;
 }
-
-inline bool is_finite(double v) { return v - v == 0.0; }
 
 Basis make_basis(const double* weights, const int32_t* cells, const double* lattice, int64_t X, int64_t Y, int64_t Z,
                  int64_t spans0, int64_t levels) {
@@ -457,7 +435,7 @@ inline int row_grid(int64_t rows, int64_t grid_blocks) {
 int check_rows(const void* u, const double* weights, const int32_t* cells, const double* lattice, int64_t X, int64_t Y,
                int64_t Z, int64_t spans0, int64_t levels, int64_t grid_blocks) {
   if (!u || !weights || !cells || !lattice) return GTS_ERR_NULL;
-  if (!extents_ok(X, Y, Z) || !levels_ok(spans0, levels) || grid_blocks < 0 || grid_blocks > INT32_MAX)
+  if (!scan_extents_ok(X, Y, Z) || !levels_ok(spans0, levels) || !grid_blocks_ok(grid_blocks))
     return GTS_ERR_SHAPE;
   return GTS_OK;
 }
@@ -467,27 +445,26 @@ int check_rows(const void* u, const double* weights, const int32_t* cells, const
 
 extern "C" int64_t gts_bias_workspace(int64_t X, int64_t Y, int64_t Z, int64_t spans) {
   using namespace gts;
-  if (!extents_ok(X, Y, Z) || spans < 1 || spans > kMaxSpans) return GTS_ERR_SHAPE;
+  if (!scan_extents_ok(X, Y, Z) || spans < 1 || spans > kMaxSpans) return GTS_ERR_SHAPE;
   return layout(Y, Z, spans).total;
 }
 
 extern "C" int32_t gts_bias_log(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, double threshold,
                                 float* u, uint64_t* count, void* stream) {
   using namespace gts;
-  if (dtype != kI16 && dtype != kF32) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype)) return GTS_ERR_ARGKIND;
   if (!src || !u || !count) return GTS_ERR_NULL;
-  if (!extents_ok(X, Y, Z)) return GTS_ERR_SHAPE;
+  if (!scan_extents_ok(X, Y, Z)) return GTS_ERR_SHAPE;
   if (!is_finite(threshold) || threshold < 0.0) return GTS_ERR_ARGKIND;
   const int64_t vol = X * Y * Z;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(count, 0, 8, st) != hipSuccess) return launch_status();
   auto* cnt = reinterpret_cast<unsigned long long*>(count);
   const int grid = blocks_for(vol, kBlock, kMaxGrid);
-  if (dtype == kI16)
-    bias_log_kernel<int16_t><<<grid, kBlock, 0, st>>>(static_cast<const int16_t*>(src), vol, threshold, u, cnt);
-  else
-    bias_log_kernel<float><<<grid, kBlock, 0, st>>>(static_cast<const float*>(src), vol, threshold, u, cnt);
-  return launch_status();
+  return with_scan_type(dtype, src, [&](auto* s) {
+    bias_log_kernel<<<grid, kBlock, 0, st>>>(s, vol, threshold, u, cnt);
+    return launch_status();
+  });
 }
 
 extern "C" int32_t gts_bias_range(const float* u, int64_t X, int64_t Y, int64_t Z, const double* weights,
@@ -591,7 +568,7 @@ extern "C" int32_t gts_bias_apply(const void* src, int32_t dtype, int64_t X, int
                                   int64_t levels, double mean, float* out, float* field, int64_t grid_blocks,
                                   void* stream) {
   using namespace gts;
-  if (dtype != kI16 && dtype != kF32) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype)) return GTS_ERR_ARGKIND;
   const int status = check_rows(src, weights, cells, lattice, X, Y, Z, spans0, levels, grid_blocks);
   if (status != GTS_OK) return status;
   if (!out) return GTS_ERR_NULL;

@@ -19,7 +19,7 @@
 //   S6  apply: every modality keeps its value where B is set and becomes 0 elsewhere, dtype preserved.
 //
 // Every result is an integer (or a copy of an input value) that does not depend on scheduling or on the grid.
-#include "gts_volume.h"
+#include "gts_scan.h"
 
 namespace gts {
 namespace {
@@ -35,16 +35,11 @@ static_assert(kMaxRadius * kMaxRadius <= kMaxR2 && (kMaxRadius + 1) * (kMaxRadiu
 template <typename T>
 __device__ __forceinline__ bool positive_finite(T v) {
   const float f = static_cast<float>(v);
-  return (f - f == 0.f) && f > 0.f;
+  return is_finite(f) && f > 0.f;
 }
 
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(v, off, kWave);
-    v = o > v ? o : v;
-  }
-  return v;
+  return wave_reduce(v, [](unsigned long long a, unsigned long long b) { return b > a ? b : a; });
 }
 
 // ------------------------------------------------------------------ S1
@@ -77,8 +72,7 @@ template <typename T>
 __global__ __launch_bounds__(kBlock) void brain_histogram_kernel(const T* __restrict__ src, int64_t n, double hi,
                                                                  unsigned long long* __restrict__ counts) {
   __shared__ unsigned hist[kBins];
-  for (int i = threadIdx.x; i < kBins; i += kBlock) hist[i] = 0;
-  __syncthreads();
+  block_hist_clear(hist, kBins);
   for (int64_t i = int64_t{blockIdx.x} * kBlock + threadIdx.x; i < n; i += int64_t{gridDim.x} * kBlock) {
     const T v = src[i];
     if (positive_finite(v)) {
@@ -86,9 +80,7 @@ __global__ __launch_bounds__(kBlock) void brain_histogram_kernel(const T* __rest
       atomicAdd(&hist[q < static_cast<double>(kBins - 1) ? static_cast<int>(q) : kBins - 1], 1u);
     }
   }
-  __syncthreads();
-  for (int i = threadIdx.x; i < kBins; i += kBlock)
-    if (hist[i]) atomicAdd(&counts[i], static_cast<unsigned long long>(hist[i]));
+  block_hist_flush(hist, kBins, counts);
 }
 
 template <typename T>
@@ -302,8 +294,6 @@ __global__ __launch_bounds__(kBlock) void apply_mask_kernel(const T* __restrict_
 
 // ------------------------------------------------------------------ host
 inline bool brain_voxels(int64_t X, int64_t Y, int64_t Z, int64_t* n) { return volume_voxels(X, Y, Z, false, n); }
-inline bool grid_ok(int64_t grid_blocks) { return grid_blocks >= 0 && grid_blocks <= INT32_MAX; }
-inline bool is_finite(double v) { return v - v == 0.0; }
 
 // workgroups of a pass over `items` at `per_block` each: the caller's count or the library's, never more than needed
 inline int grid_for(int64_t items, int64_t per_block, int64_t grid_blocks) {
@@ -338,54 +328,51 @@ extern "C" int32_t gts_brain_range(const void* src, int32_t dtype, int64_t X, in
                                    int64_t grid_blocks, void* stream) {
   using namespace gts;
   if (!src || !out) return GTS_ERR_NULL;
-  if (dtype != 4 && dtype != 16) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype)) return GTS_ERR_ARGKIND;
   int64_t n;
-  if (!brain_voxels(X, Y, Z, &n) || !grid_ok(grid_blocks)) return GTS_ERR_SHAPE;
+  if (!brain_voxels(X, Y, Z, &n) || !grid_blocks_ok(grid_blocks)) return GTS_ERR_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(out, 0, 2 * sizeof(uint64_t), st) != hipSuccess) return launch_status();
   unsigned long long* o = reinterpret_cast<unsigned long long*>(out);
   const int grid = grid_for(n, kBlock, grid_blocks);
-  if (dtype == 4)
-    brain_range_kernel<<<grid, kBlock, 0, st>>>(static_cast<const int16_t*>(src), n, o);
-  else
-    brain_range_kernel<<<grid, kBlock, 0, st>>>(static_cast<const float*>(src), n, o);
-  return launch_status();
+  return with_scan_type(dtype, src, [&](auto* s) {
+    brain_range_kernel<<<grid, kBlock, 0, st>>>(s, n, o);
+    return launch_status();
+  });
 }
 
 extern "C" int32_t gts_brain_histogram(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, double hi,
                                        int64_t* counts, int64_t grid_blocks, void* stream) {
   using namespace gts;
   if (!src || !counts) return GTS_ERR_NULL;
-  if ((dtype != 4 && dtype != 16) || !is_finite(hi) || !(hi > 0.0)) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype) || !is_finite(hi) || !(hi > 0.0)) return GTS_ERR_ARGKIND;
   int64_t n;
-  if (!brain_voxels(X, Y, Z, &n) || !grid_ok(grid_blocks)) return GTS_ERR_SHAPE;
+  if (!brain_voxels(X, Y, Z, &n) || !grid_blocks_ok(grid_blocks)) return GTS_ERR_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(counts, 0, kBins * sizeof(int64_t), st) != hipSuccess) return launch_status();
   unsigned long long* c = reinterpret_cast<unsigned long long*>(counts);
   const int grid = grid_for(n, kBlock, grid_blocks);
-  if (dtype == 4)
-    brain_histogram_kernel<<<grid, kBlock, 0, st>>>(static_cast<const int16_t*>(src), n, hi, c);
-  else
-    brain_histogram_kernel<<<grid, kBlock, 0, st>>>(static_cast<const float*>(src), n, hi, c);
-  return launch_status();
+  return with_scan_type(dtype, src, [&](auto* s) {
+    brain_histogram_kernel<<<grid, kBlock, 0, st>>>(s, n, hi, c);
+    return launch_status();
+  });
 }
 
 extern "C" int32_t gts_brain_threshold(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, double t,
                                        int16_t* mask, uint64_t* count, int64_t grid_blocks, void* stream) {
   using namespace gts;
   if (!src || !mask || !count) return GTS_ERR_NULL;
-  if ((dtype != 4 && dtype != 16) || !is_finite(t) || t < 0.0) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype) || !is_finite(t) || t < 0.0) return GTS_ERR_ARGKIND;
   int64_t n;
-  if (!brain_voxels(X, Y, Z, &n) || !grid_ok(grid_blocks)) return GTS_ERR_SHAPE;
+  if (!brain_voxels(X, Y, Z, &n) || !grid_blocks_ok(grid_blocks)) return GTS_ERR_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(count, 0, sizeof(uint64_t), st) != hipSuccess) return launch_status();
   unsigned long long* c = reinterpret_cast<unsigned long long*>(count);
   const int grid = grid_for(n, kBlock, grid_blocks);
-  if (dtype == 4)
-    brain_threshold_kernel<<<grid, kBlock, 0, st>>>(static_cast<const int16_t*>(src), n, t, mask, c);
-  else
-    brain_threshold_kernel<<<grid, kBlock, 0, st>>>(static_cast<const float*>(src), n, t, mask, c);
-  return launch_status();
+  return with_scan_type(dtype, src, [&](auto* s) {
+    brain_threshold_kernel<<<grid, kBlock, 0, st>>>(s, n, t, mask, c);
+    return launch_status();
+  });
 }
 
 extern "C" int32_t gts_ball_morph_i16(const int16_t* mask_in, int64_t X, int64_t Y, int64_t Z, int32_t R2,
@@ -395,7 +382,7 @@ extern "C" int32_t gts_ball_morph_i16(const int16_t* mask_in, int64_t X, int64_t
   if (!mask_in || !mask_out || !workspace) return GTS_ERR_NULL;
   if (R2 < 0 || R2 > kMaxR2 || (target | 1) != 1 || (outside | 1) != 1 || (invert | 1) != 1) return GTS_ERR_ARGKIND;
   int64_t n;
-  if (!brain_voxels(X, Y, Z, &n) || !grid_ok(grid_blocks)) return GTS_ERR_SHAPE;
+  if (!brain_voxels(X, Y, Z, &n) || !grid_blocks_ok(grid_blocks)) return GTS_ERR_SHAPE;
   const Layout l = layout(X, Y, Z, n);
   if (workspace_bytes < l.bytes) return GTS_ERR_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -418,7 +405,7 @@ extern "C" int32_t gts_largest_component_i16(const int16_t* mask, int64_t X, int
   using namespace gts;
   if (!mask || !keep_out || !stats || !workspace) return GTS_ERR_NULL;
   int64_t n;
-  if (!brain_voxels(X, Y, Z, &n) || (connectivity != 6 && connectivity != 26) || !grid_ok(grid_blocks))
+  if (!brain_voxels(X, Y, Z, &n) || (connectivity != 6 && connectivity != 26) || !grid_blocks_ok(grid_blocks))
     return GTS_ERR_SHAPE;
   const Layout l = layout(X, Y, Z, n);
   if (workspace_bytes < l.bytes) return GTS_ERR_SHAPE;
@@ -446,7 +433,7 @@ extern "C" int32_t gts_fill_holes_i16(const int16_t* mask, int64_t X, int64_t Y,
   using namespace gts;
   if (!mask || !mask_out || !stats || !workspace) return GTS_ERR_NULL;
   int64_t n;
-  if (!brain_voxels(X, Y, Z, &n) || !grid_ok(grid_blocks)) return GTS_ERR_SHAPE;
+  if (!brain_voxels(X, Y, Z, &n) || !grid_blocks_ok(grid_blocks)) return GTS_ERR_SHAPE;
   const Layout l = layout(X, Y, Z, n);
   if (workspace_bytes < l.bytes) return GTS_ERR_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -470,18 +457,16 @@ extern "C" int32_t gts_apply_mask(const void* src, int32_t dtype, int64_t C, int
                                   const int16_t* mask, void* dst, uint64_t* count, int64_t grid_blocks, void* stream) {
   using namespace gts;
   if (!src || !mask || !dst || !count) return GTS_ERR_NULL;
-  if (dtype != 4 && dtype != 16) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype)) return GTS_ERR_ARGKIND;
   int64_t n;
-  if (!brain_voxels(X, Y, Z, &n) || C < 1 || C > kMaxChannels || !grid_ok(grid_blocks)) return GTS_ERR_SHAPE;
+  if (!brain_voxels(X, Y, Z, &n) || C < 1 || C > kMaxChannels || !grid_blocks_ok(grid_blocks)) return GTS_ERR_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(count, 0, sizeof(uint64_t), st) != hipSuccess) return launch_status();
   unsigned long long* c = reinterpret_cast<unsigned long long*>(count);
   const int grid = grid_for(n, kBlock, grid_blocks);
-  if (dtype == 4)
-    apply_mask_kernel<<<grid, kBlock, 0, st>>>(static_cast<const int16_t*>(src), mask, static_cast<int>(C), n,
-                                               static_cast<int16_t*>(dst), c);
-  else
-    apply_mask_kernel<<<grid, kBlock, 0, st>>>(static_cast<const float*>(src), mask, static_cast<int>(C), n,
-                                               static_cast<float*>(dst), c);
-  return launch_status();
+  return with_scan_type(dtype, src, [&](auto* s) {
+    using T = std::remove_const_t<std::remove_pointer_t<decltype(s)>>;
+    apply_mask_kernel<<<grid, kBlock, 0, st>>>(s, mask, static_cast<int>(C), n, static_cast<T*>(dst), c);
+    return launch_status();
+  });
 }

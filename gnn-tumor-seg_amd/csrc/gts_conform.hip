@@ -7,9 +7,8 @@
 // float64 weight of the second.  The kernel divides nothing and rounds nothing but the final float32.
 //
 //   exact      out = in[idx0 ...], the stored dtype, bit for bit (pure reorientation, and the inverse map);
-//   trilinear  the eight neighbours (idx0 | idx1 per axis), lerped along input x, then y, then z, each lerp
-//              a + (b - a) * t in float64 (the library is built without contraction; t == 0 gives a itself),
-//              one rounding to float32;
+//   trilinear  the eight neighbours (idx0 | idx1 per axis) through gts_scan.h's trilinear8 (float64, along input
+//              x, then y, then z; t == 0 gives the voxel itself), one rounding to float32;
 //   nearest    t < 0.5 ? idx0 : idx1 per axis, int16.
 //
 // Memory access.  Whatever the mode, the eight (or one) reads of an output voxel lie on input rows, so the
@@ -19,19 +18,15 @@
 //          16-byte groups moves 16 bytes per lane, reversed in registers when x is flipped;
 //   tiled  the output's x reads the input's y or z (4 of the 6 permutations): a 64 x 64 tile over (output x,
 //          the output axis that reads input x).  Loading, a wave's lanes run along input x; the finished values
-//          go through LDS; storing, the lanes run along output x.  LDS holds one 32-bit word per value with a
-//          pitch of 65 words: the row writes and the column reads (ds_write_b32 / ds_read_b32, 32 banks per
-//          32-lane group) both touch 32 distinct banks.
+//          go through LDS; storing, the lanes run along output x (gts_scan.h's cross_tile64: one 32-bit word per
+//          value, an int16 widened to int32, and the bank arithmetic of its pitch).
 // Table entries are clamped to the input extent before use, so no table can make a read leave the volume.
-#include "gts_volume.h"
+#include "gts_scan.h"
 
 namespace gts {
 namespace {
 
 constexpr int kModeExact = 0, kModeTrilinear = 1, kModeNearest = 2;
-constexpr int kTile = 64;
-constexpr int kPitch = kTile + 1;
-constexpr int64_t kMaxExtent = 65535;
 
 // Tables and extents ordered by INPUT axis j (0 = x, fastest): which output axis drives it, and that axis'
 // tables.  t is unused (may be NULL) in exact mode, idx1 likewise.
@@ -48,23 +43,6 @@ struct ConformArgs {
 __device__ __forceinline__ int pick(int axis, int o0, int o1, int o2) { return axis == 0 ? o0 : (axis == 1 ? o1 : o2); }
 __device__ __forceinline__ int clamp_index(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 
-template <typename T>
-struct Lds;  // the 32-bit word a value travels through LDS as
-template <>
-struct Lds<int16_t> {
-  __device__ static uint32_t pack(int16_t v) { return static_cast<uint16_t>(v); }
-  __device__ static int16_t unpack(uint32_t w) { return static_cast<int16_t>(static_cast<uint16_t>(w)); }
-};
-template <>
-struct Lds<float> {
-  __device__ static uint32_t pack(float v) { return __float_as_uint(v); }
-  __device__ static float unpack(uint32_t w) { return __uint_as_float(w); }
-};
-
-// A sample that lies on a voxel (t == 0) IS that voxel: the sign of a -0.0 survives and a non-finite neighbour
-// that carries no weight does not turn the result into a NaN.  For finite values a + (b - a) * 0 is a anyway.
-__device__ __forceinline__ double lerp64(double a, double b, double t) { return t == 0.0 ? a : a + (b - a) * t; }
-
 // The value of output voxel (o0, o1, o2) of channel c.
 template <typename In, typename Out, int kMode>
 __device__ __forceinline__ Out fetch(const In* __restrict__ src, const ConformArgs& p, int c, int o0, int o1, int o2) {
@@ -76,15 +54,7 @@ __device__ __forceinline__ Out fetch(const In* __restrict__ src, const ConformAr
     const int y0 = clamp_index(p.idx0[1][iy], Y), y1 = clamp_index(p.idx1[1][iy], Y);
     const int z0 = clamp_index(p.idx0[2][iz], Z), z1 = clamp_index(p.idx1[2][iz], Z);
     const double tx = p.t[0][ix], ty = p.t[1][iy], tz = p.t[2][iz];
-    const In* r00 = vol + (static_cast<int64_t>(z0) * Y + y0) * X;
-    const In* r01 = vol + (static_cast<int64_t>(z0) * Y + y1) * X;
-    const In* r10 = vol + (static_cast<int64_t>(z1) * Y + y0) * X;
-    const In* r11 = vol + (static_cast<int64_t>(z1) * Y + y1) * X;
-    const double v00 = lerp64(static_cast<double>(r00[x0]), static_cast<double>(r00[x1]), tx);
-    const double v01 = lerp64(static_cast<double>(r01[x0]), static_cast<double>(r01[x1]), tx);
-    const double v10 = lerp64(static_cast<double>(r10[x0]), static_cast<double>(r10[x1]), tx);
-    const double v11 = lerp64(static_cast<double>(r11[x0]), static_cast<double>(r11[x1]), tx);
-    return static_cast<Out>(static_cast<float>(lerp64(lerp64(v00, v01, ty), lerp64(v10, v11, ty), tz)));
+    return static_cast<Out>(static_cast<float>(trilinear8(vol, X, Y, x0, x1, y0, y1, z0, z1, tx, ty, tz)));
   }
   int x, y, z;
   if (kMode == kModeNearest) {
@@ -162,7 +132,6 @@ __global__ __launch_bounds__(kBlock) void conform_rows_wide_kernel(const T* __re
 template <typename In, typename Out, int kMode>
 __global__ __launch_bounds__(kBlock) void conform_tiled_kernel(const In* __restrict__ src, Out* __restrict__ dst,
                                                                const ConformArgs p, int ka, int tiles_x, int tiles_a) {
-  __shared__ uint32_t tile[kTile * kPitch];
   int64_t b = blockIdx.x;
   const int tx0 = static_cast<int>(b % tiles_x) * kTile;
   b /= tiles_x;
@@ -171,31 +140,14 @@ __global__ __launch_bounds__(kBlock) void conform_tiled_kernel(const In* __restr
   const int OX = p.out[0], OA = ka == 1 ? p.out[1] : p.out[2], OB = ka == 1 ? p.out[2] : p.out[1];
   const int ob = static_cast<int>(b % OB);
   const int c = static_cast<int>(b / OB);
-  const int lane = threadIdx.x & (kTile - 1), wave_row = threadIdx.x / kTile;
-  // load: lanes along output axis ka (= input x), rows along output x
-  {
-    const int oa = ta0 + lane;
-    for (int r = wave_row; r < kTile; r += kBlock / kTile) {
-      const int ox = tx0 + r;
-      if (oa < OA && ox < OX) {
+  using Word = decltype(Out{} + 0);  // float, or the int an int16 widens to
+  cross_tile64<Word>(
+      tx0, ta0, OX, OA,
+      [&](int ox, int oa) { return fetch<In, Out, kMode>(src, p, c, ox, ka == 1 ? oa : ob, ka == 1 ? ob : oa); },
+      [&](int ox, int oa, Word w) {
         const int o1 = ka == 1 ? oa : ob, o2 = ka == 1 ? ob : oa;
-        tile[r * kPitch + lane] = Lds<Out>::pack(fetch<In, Out, kMode>(src, p, c, ox, o1, o2));
-      }
-    }
-  }
-  __syncthreads();
-  // store: lanes along output x, rows along output axis ka
-  {
-    const int ox = tx0 + lane;
-    for (int r = wave_row; r < kTile; r += kBlock / kTile) {
-      const int oa = ta0 + r;
-      if (oa < OA && ox < OX) {
-        const int o1 = ka == 1 ? oa : ob, o2 = ka == 1 ? ob : oa;
-        const int64_t at = ((static_cast<int64_t>(c) * p.out[2] + o2) * p.out[1] + o1) * OX + ox;
-        dst[at] = Lds<Out>::unpack(tile[lane * kPitch + r]);
-      }
-    }
-  }
+        dst[((static_cast<int64_t>(c) * p.out[2] + o2) * p.out[1] + o1) * OX + ox] = static_cast<Out>(w);
+      });
 }
 
 template <typename In, typename Out, int kMode>
@@ -233,14 +185,14 @@ extern "C" int32_t gts_conform_gather(const void* src, int32_t dtype, int64_t C,
                                       void* stream) {
   using namespace gts;
   if (mode != kModeExact && mode != kModeTrilinear && mode != kModeNearest) return GTS_ERR_ARGKIND;
-  if (dtype != 4 && dtype != 16) return GTS_ERR_ARGKIND;
-  if (mode == kModeNearest && dtype != 4) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype)) return GTS_ERR_ARGKIND;
+  if (mode == kModeNearest && dtype != kI16) return GTS_ERR_ARGKIND;
   if (!src || !dst || !idx0) return GTS_ERR_NULL;
   if (mode != kModeExact && (!idx1 || !t)) return GTS_ERR_NULL;
   if (C < 0) return GTS_ERR_SHAPE;
   const int64_t in_dims[3] = {X, Y, Z}, out_dims[3] = {OX, OY, OZ};
   for (int k = 0; k < 3; ++k)
-    if (in_dims[k] <= 0 || out_dims[k] <= 0 || in_dims[k] > kMaxExtent || out_dims[k] > kMaxExtent) return GTS_ERR_SHAPE;
+    if (!scan_extent_ok(in_dims[k]) || !scan_extent_ok(out_dims[k])) return GTS_ERR_SHAPE;
   const int32_t axes[3] = {axis0, axis1, axis2};
   int seen = 0;
   for (int k = 0; k < 3; ++k) {
@@ -249,9 +201,9 @@ extern "C" int32_t gts_conform_gather(const void* src, int32_t dtype, int64_t C,
   }
   if (seen != 7) return GTS_ERR_ARGKIND;
   if (C == 0) return GTS_OK;
-  int64_t n_in, n_out, all;  // a lane's linear index covers every channel: C volumes are one volume of C planes
-  if (!volume_voxels(X, Y, Z, false, &n_in) || !volume_voxels(OX, OY, OZ, false, &n_out)) return GTS_ERR_SHAPE;
-  if (!volume_voxels(n_in, C, 1, false, &all) || !volume_voxels(n_out, C, 1, false, &all)) return GTS_ERR_SHAPE;
+  if (!scan_extents_ok(X, Y, Z) || !scan_extents_ok(OX, OY, OZ)) return GTS_ERR_SHAPE;
+  int64_t all;  // a lane's linear index covers every channel: C volumes are one volume of C planes
+  if (!volume_voxels(X * Y * Z, C, 1, false, &all) || !volume_voxels(OX * OY * OZ, C, 1, false, &all)) return GTS_ERR_SHAPE;
   ConformArgs p;
   int64_t at = 0;
   for (int k = 0; k < 3; ++k) {  // output axis k reads input axis axes[k]; its tables start at `at`
@@ -268,8 +220,8 @@ extern "C" int32_t gts_conform_gather(const void* src, int32_t dtype, int64_t C,
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (mode == kModeNearest) return launch<int16_t, int16_t, kModeNearest>(src, dst, p, st);
   if (mode == kModeTrilinear)
-    return dtype == 4 ? launch<int16_t, float, kModeTrilinear>(src, dst, p, st)
+    return dtype == kI16 ? launch<int16_t, float, kModeTrilinear>(src, dst, p, st)
                       : launch<float, float, kModeTrilinear>(src, dst, p, st);
-  return dtype == 4 ? launch<int16_t, int16_t, kModeExact>(src, dst, p, st)
+  return dtype == kI16 ? launch<int16_t, int16_t, kModeExact>(src, dst, p, st)
                     : launch<float, float, kModeExact>(src, dst, p, st);
 }

@@ -162,19 +162,16 @@ extern "C" int32_t gts_dataset_stats_mask(const void* src, int32_t dtype, const 
   const int64_t vol = X * Y * Z;
   const StatsLayout l = stats_layout(vol);
   if (workspace_bytes < l.total) return GTS_ERR_SHAPE;
-  if (dtype != kI16 && dtype != kF32) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype)) return GTS_ERR_ARGKIND;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(counts, 0, 16, st) != hipSuccess) return launch_status();
   auto* bits = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + l.mask);
   auto* cnt = reinterpret_cast<unsigned long long*>(counts);
   const int grid = blocks_for(vol, kBlock, kMaxBlocks);
-  if (dtype == kI16)
-    dstats_mask_kernel<int16_t><<<grid, kBlock, 0, st>>>(static_cast<const int16_t*>(src), labels,
-                                                         static_cast<unsigned>(vol), bits, cnt);
-  else
-    dstats_mask_kernel<float><<<grid, kBlock, 0, st>>>(static_cast<const float*>(src), labels,
-                                                       static_cast<unsigned>(vol), bits, cnt);
-  return launch_status();
+  return with_scan_type(dtype, src, [&](auto* s) {
+    dstats_mask_kernel<<<grid, kBlock, 0, st>>>(s, labels, static_cast<unsigned>(vol), bits, cnt);
+    return launch_status();
+  });
 }
 
 extern "C" int32_t gts_dataset_stats_order_stats(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z,
@@ -187,16 +184,13 @@ extern "C" int32_t gts_dataset_stats_order_stats(const void* src, int32_t dtype,
   const StatsLayout l = stats_layout(vol);
   if (workspace_bytes < l.total || n < 1 || n > vol) return GTS_ERR_SHAPE;
   if (rank_lo < 0 || rank_hi < rank_lo || rank_hi >= n) return GTS_ERR_SHAPE;
-  if (dtype != kI16 && dtype != kF32) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype)) return GTS_ERR_ARGKIND;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const MaskSource source{reinterpret_cast<const unsigned long long*>(static_cast<char*>(workspace) + l.mask)};
-  if (dtype == kI16)
-    run_select(static_cast<const int16_t*>(src), static_cast<size_t>(vol), source, vol, rank_lo, rank_hi, out,
-               workspace, st);
-  else
-    run_select(static_cast<const float*>(src), static_cast<size_t>(vol), source, vol, rank_lo, rank_hi, out,
-               workspace, st);
-  return launch_status();
+  return with_scan_type(dtype, src, [&](auto* s) {
+    run_select(s, static_cast<size_t>(vol), source, vol, rank_lo, rank_hi, out, workspace, st);
+    return launch_status();
+  });
 }
 
 extern "C" int32_t gts_dataset_stats_moments(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z,
@@ -208,7 +202,7 @@ extern "C" int32_t gts_dataset_stats_moments(const void* src, int32_t dtype, int
   const int64_t vol = X * Y * Z;
   const StatsLayout l = stats_layout(vol);
   if (workspace_bytes < l.total || n < 1 || n > vol) return GTS_ERR_SHAPE;
-  if (dtype != kI16 && dtype != kF32) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype)) return GTS_ERR_ARGKIND;
   Tops p;
   for (int c = 0; c < kChannels; ++c) p.top[c] = top[c];
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -216,12 +210,10 @@ extern "C" int32_t gts_dataset_stats_moments(const void* src, int32_t dtype, int
   const auto* bits = reinterpret_cast<const unsigned long long*>(ws + l.mask);
   double* partial = reinterpret_cast<double*>(ws + l.partial);
   const unsigned units = static_cast<unsigned>(l.units), words = static_cast<unsigned>(l.words);
-  if (dtype == kI16)
-    dstats_moments_kernel<int16_t><<<blocks_for(l.units, 1, kMaxBlocks), kBlock, 0, st>>>(
-        static_cast<const int16_t*>(src), static_cast<unsigned>(vol), bits, words, p, units, partial);
-  else
-    dstats_moments_kernel<float><<<blocks_for(l.units, 1, kMaxBlocks), kBlock, 0, st>>>(
-        static_cast<const float*>(src), static_cast<unsigned>(vol), bits, words, p, units, partial);
-  dstats_final_kernel<<<1, kBlock, 0, st>>>(partial, units, static_cast<unsigned long long>(n), out);
-  return launch_status();
+  return with_scan_type(dtype, src, [&](auto* s) {
+    dstats_moments_kernel<<<blocks_for(l.units, 1, kMaxBlocks), kBlock, 0, st>>>(s, static_cast<unsigned>(vol), bits, words,
+                                                                                 p, units, partial);
+    dstats_final_kernel<<<1, kBlock, 0, st>>>(partial, units, static_cast<unsigned long long>(n), out);
+    return launch_status();
+  });
 }

@@ -127,7 +127,7 @@ extern "C" int32_t gts_intake_occupancy(const void* src, int32_t dtype, int64_t 
   using namespace gts;
   if (!src || !flag_x || !flag_y || !flag_z || !nonfinite) return GTS_ERR_NULL;
   if (!volume_ok(X, Y, Z)) return GTS_ERR_SHAPE;
-  if (dtype != kI16 && dtype != kF32) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype)) return GTS_ERR_ARGKIND;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(flag_x, 0, X * 4, st) != hipSuccess || hipMemsetAsync(flag_y, 0, Y * 4, st) != hipSuccess ||
       hipMemsetAsync(flag_z, 0, Z * 4, st) != hipSuccess || hipMemsetAsync(nonfinite, 0, 8, st) != hipSuccess)
@@ -135,13 +135,10 @@ extern "C" int32_t gts_intake_occupancy(const void* src, int32_t dtype, int64_t 
   const int x = static_cast<int>(X), y = static_cast<int>(Y), z = static_cast<int>(Z);
   auto* bad = reinterpret_cast<unsigned long long*>(nonfinite);
   const int grid = blocks_for(X * Y * Z, kBlock, kMaxBlocks);
-  if (dtype == kI16)
-    intake_occupancy_kernel<int16_t><<<grid, kBlock, 0, st>>>(static_cast<const int16_t*>(src), x, y, z, flag_x,
-                                                              flag_y, flag_z, bad);
-  else
-    intake_occupancy_kernel<float><<<grid, kBlock, 0, st>>>(static_cast<const float*>(src), x, y, z, flag_x, flag_y,
-                                                            flag_z, bad);
-  return launch_status();
+  return with_scan_type(dtype, src, [&](auto* s) {
+    intake_occupancy_kernel<<<grid, kBlock, 0, st>>>(s, x, y, z, flag_x, flag_y, flag_z, bad);
+    return launch_status();
+  });
 }
 
 extern "C" int64_t gts_intake_select_workspace(void) { return gts::kLayout.total; }
@@ -155,16 +152,15 @@ extern "C" int32_t gts_intake_order_stats(const void* src, int32_t dtype, int64_
   if (!volume_ok(X, Y, Z) || !crop_ok(X, Y, Z, cx, cy, cz) || workspace_bytes < kLayout.total) return GTS_ERR_SHAPE;
   const int64_t n = cx * cy * cz;
   if (rank_lo < 0 || rank_hi < rank_lo || rank_hi >= n) return GTS_ERR_SHAPE;
-  if (dtype != kI16 && dtype != kF32) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype)) return GTS_ERR_ARGKIND;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const CropSource source{xs, ys, zs, static_cast<int>(cx), static_cast<int>(cy), static_cast<int>(X),
                           static_cast<int>(Y), static_cast<int>(Z)};
   const size_t vol = static_cast<size_t>(X * Y * Z);
-  if (dtype == kI16)
-    run_select(static_cast<const int16_t*>(src), vol, source, n, rank_lo, rank_hi, out, workspace, st);
-  else
-    run_select(static_cast<const float*>(src), vol, source, n, rank_lo, rank_hi, out, workspace, st);
-  return launch_status();
+  return with_scan_type(dtype, src, [&](auto* s) {
+    run_select(s, vol, source, n, rank_lo, rank_hi, out, workspace, st);
+    return launch_status();
+  });
 }
 
 extern "C" int32_t gts_intake_standardize(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z,
@@ -174,7 +170,7 @@ extern "C" int32_t gts_intake_standardize(const void* src, int32_t dtype, int64_
   using namespace gts;
   if (!src || !xs || !ys || !zs || !params || !out) return GTS_ERR_NULL;
   if (!volume_ok(X, Y, Z) || !crop_ok(X, Y, Z, cx, cy, cz)) return GTS_ERR_SHAPE;
-  if (dtype != kI16 && dtype != kF32) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype)) return GTS_ERR_ARGKIND;
   StandardizeParams p;
   for (int c = 0; c < kChannels; ++c) {
     p.top[c] = params[c];
@@ -185,13 +181,9 @@ extern "C" int32_t gts_intake_standardize(const void* src, int32_t dtype, int64_
   const dim3 grid(static_cast<unsigned>((cx + kTileX - 1) / kTileX), static_cast<unsigned>(cy),
                   static_cast<unsigned>((cz + kTileZ - 1) / kTileZ));
   const int x = static_cast<int>(X), y = static_cast<int>(Y), z = static_cast<int>(Z);
-  if (dtype == kI16)
-    intake_standardize_kernel<int16_t><<<grid, kBlock, 0, st>>>(static_cast<const int16_t*>(src), x, y, z, xs,
-                                                                static_cast<int>(cx), ys, static_cast<int>(cy), zs,
-                                                                static_cast<int>(cz), p, out);
-  else
-    intake_standardize_kernel<float><<<grid, kBlock, 0, st>>>(static_cast<const float*>(src), x, y, z, xs,
-                                                              static_cast<int>(cx), ys, static_cast<int>(cy), zs,
-                                                              static_cast<int>(cz), p, out);
-  return launch_status();
+  return with_scan_type(dtype, src, [&](auto* s) {
+    intake_standardize_kernel<<<grid, kBlock, 0, st>>>(s, x, y, z, xs, static_cast<int>(cx), ys, static_cast<int>(cy), zs,
+                                                       static_cast<int>(cz), p, out);
+    return launch_status();
+  });
 }

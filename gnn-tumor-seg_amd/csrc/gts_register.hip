@@ -5,8 +5,8 @@
 // 3 x 4 float64 matrix T sends the voxel indices (x, y, z) of another grid to:
 //   u = ((T00 x + T01 y) + T02 z) + T03, v and w likewise from rows 1 and 2: float64, nothing contracted;
 //   inside  <=>  0 <= u <= X-1 && 0 <= v <= Y-1 && 0 <= w <= Z-1 (a NaN coordinate fails every comparison: outside);
-//   i0 = min(floor(u), X-1), i1 = min(i0 + 1, X-1), t = u - i0 per axis; the eight neighbours as float64,
-//   lerp64 (gts_conform.hip's: t == 0 returns a) along x, then y, then z.
+//   i0 = min(floor(u), X-1), i1 = min(i0 + 1, X-1), t = u - i0 per axis; the eight neighbours through
+//   gts_scan.h's trilinear8 (float64, along x, then y, then z; t == 0 returns the voxel itself).
 //
 //   R1 gts_affine_resample   out[z][y][x] = float32(that value), 0.0f outside.  One value per lane, and two maps
 //        of lanes to voxels that compute the same bits:
@@ -16,11 +16,11 @@
 //          tiled  |T10| or |T20| dominant: the output's x runs along the input's y or z, and the output axis
 //                 ka with the larger |T0ka| runs along the input's x.  A 64 x 64 tile over (output x, output ka):
 //                 computing, a wave's lanes run along ka (input rows); the values cross a padded LDS tile;
-//                 storing, the lanes run along output x.  conform_tiled_kernel's shape, same bank arithmetic.
+//                 storing, the lanes run along output x (gts_scan.h's cross_tile64).
 //   R2 gts_joint_histogram   for every voxel of a FIXED float32 volume with x, y, z all multiples of `stride`
 //        and each of K matrices: the moving value m (float64, not rounded), then one count in row k of an int64
 //        table [K][B*B + 1]: entry B*B when the sample is outside, entry bin(f) * B + bin(m) otherwise.
-//        bin(v) = 0 when v is not finite (v - v == 0.0 is false for NaN and +-Inf), else q = floor((v - lo) *
+//        bin(v) = 0 when v is not finite (NaN and +-Inf), else q = floor((v - lo) *
 //        scale), q >= 1 ? (q < B-1 ? int(q) : B-1) : 0 (a NaN q fails q >= 1: bin 0).
 //        Counts are integers, summed in LDS (uint32, one B*B table per matrix) and flushed with one 64-bit
 //        integer global atomic per non-zero cell and workgroup: no float atomics, no dependence on the grid or
@@ -34,21 +34,16 @@
 
 #include <algorithm>
 
-#include "gts_volume.h"
+#include "gts_scan.h"
 
 namespace gts {
 namespace {
 
-constexpr int kTile = 64;
-constexpr int kPitch = kTile + 1;
-constexpr int64_t kMaxExtent = 65535;
 constexpr int kMaxMatrices = 16;
 constexpr int kPassCells = 16384;                                            // uint32 cells of one pass's tables
 constexpr int kHistLdsBytes = (kPassCells + kMaxMatrices) * 4;               // + one outside counter per matrix
 constexpr int kMaxLdsPerCu = 160 * 1024;
 constexpr int kPathAuto = 0, kPathPlain = 1, kPathTiled = 2;
-
-__device__ __forceinline__ double lerp64(double a, double b, double t) { return t == 0.0 ? a : a + (b - a) * t; }
 
 struct Coord {
   double u, v, w;
@@ -73,15 +68,7 @@ __device__ __forceinline__ double sample(const In* __restrict__ vol, int X, int 
   const int y0 = min(static_cast<int>(c.v), Y - 1), y1 = min(y0 + 1, Y - 1);
   const int z0 = min(static_cast<int>(c.w), Z - 1), z1 = min(z0 + 1, Z - 1);
   const double tx = c.u - static_cast<double>(x0), ty = c.v - static_cast<double>(y0), tz = c.w - static_cast<double>(z0);
-  const In* r00 = vol + (static_cast<int64_t>(z0) * Y + y0) * X;
-  const In* r01 = vol + (static_cast<int64_t>(z0) * Y + y1) * X;
-  const In* r10 = vol + (static_cast<int64_t>(z1) * Y + y0) * X;
-  const In* r11 = vol + (static_cast<int64_t>(z1) * Y + y1) * X;
-  const double v00 = lerp64(static_cast<double>(r00[x0]), static_cast<double>(r00[x1]), tx);
-  const double v01 = lerp64(static_cast<double>(r01[x0]), static_cast<double>(r01[x1]), tx);
-  const double v10 = lerp64(static_cast<double>(r10[x0]), static_cast<double>(r10[x1]), tx);
-  const double v11 = lerp64(static_cast<double>(r11[x0]), static_cast<double>(r11[x1]), tx);
-  return lerp64(lerp64(v00, v01, ty), lerp64(v10, v11, ty), tz);
+  return trilinear8(vol, X, Y, x0, x1, y0, y1, z0, z1, tx, ty, tz);
 }
 
 // ------------------------------------------------------------------ R1
@@ -112,37 +99,22 @@ __global__ __launch_bounds__(kBlock) void resample_plain_kernel(const In* __rest
 template <typename In>
 __global__ __launch_bounds__(kBlock) void resample_tiled_kernel(const In* __restrict__ src, float* __restrict__ dst,
                                                                 const ResampleArgs p, int ka, int tiles_x, int tiles_a) {
-  __shared__ float tile[kTile * kPitch];
   int64_t b = blockIdx.x;
   const int tx0 = static_cast<int>(b % tiles_x) * kTile;
   b /= tiles_x;
   const int ta0 = static_cast<int>(b % tiles_a) * kTile;
   const int ob = static_cast<int>(b / tiles_a);
-  const int OX = p.out[0], OA = ka == 1 ? p.out[1] : p.out[2];
-  const int lane = threadIdx.x & (kTile - 1), wave_row = threadIdx.x / kTile;
-  {  // compute: lanes along output axis ka (the input's x), rows along output x
-    const int oa = ta0 + lane;
-    for (int r = wave_row; r < kTile; r += kBlock / kTile) {
-      const int ox = tx0 + r;
-      if (oa < OA && ox < OX) tile[r * kPitch + lane] = resampled(src, p, ox, ka == 1 ? oa : ob, ka == 1 ? ob : oa);
-    }
-  }
-  __syncthreads();
-  {  // store: lanes along output x, rows along output axis ka
-    const int ox = tx0 + lane;
-    for (int r = wave_row; r < kTile; r += kBlock / kTile) {
-      const int oa = ta0 + r;
-      if (oa < OA && ox < OX) {
+  cross_tile64<float>(
+      tx0, ta0, p.out[0], ka == 1 ? p.out[1] : p.out[2],
+      [&](int ox, int oa) { return resampled(src, p, ox, ka == 1 ? oa : ob, ka == 1 ? ob : oa); },
+      [&](int ox, int oa, float v) {
         const int oy = ka == 1 ? oa : ob, oz = ka == 1 ? ob : oa;
-        dst[(static_cast<int64_t>(oz) * p.out[1] + oy) * OX + ox] = tile[lane * kPitch + r];
-      }
-    }
-  }
+        dst[(static_cast<int64_t>(oz) * p.out[1] + oy) * p.out[0] + ox] = v;
+      });
 }
 
 template <typename In>
-int launch_resample(const void* src, float* dst, const ResampleArgs& p, int path, hipStream_t st) {
-  const In* s = static_cast<const In*>(src);
+int launch_resample(const In* s, float* dst, const ResampleArgs& p, int path, hipStream_t st) {
   const double ax = fabs(p.T[0]), ay = fabs(p.T[4]), az = fabs(p.T[8]);
   const bool x_leads = ax >= ay && ax >= az;   // neighbouring output voxels along x step along the input's x
   if (path == kPathPlain || (path == kPathAuto && x_leads)) {
@@ -172,7 +144,7 @@ struct HistArgs {
 };
 
 __device__ __forceinline__ int bin_of(double v, double lo, double scale, int bins) {
-  if (!(v - v == 0.0)) return 0;  // NaN, +Inf, -Inf
+  if (!is_finite(v)) return 0;
   const double q = floor((v - lo) * scale);
   return q >= 1.0 ? (q < static_cast<double>(bins - 1) ? static_cast<int>(q) : bins - 1) : 0;
 }
@@ -244,7 +216,8 @@ int device_cus() {
 }
 
 template <typename In>
-int launch_histogram(HistArgs p, const double* matrices, int K, int64_t grid_blocks, hipStream_t st) {
+int launch_histogram(const In* moving, HistArgs p, const double* matrices, int K, int64_t grid_blocks, hipStream_t st) {
+  p.moving = moving;
   static const hipError_t allowed = hipFuncSetAttribute(reinterpret_cast<const void*>(&joint_histogram_kernel<In>),
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, kHistLdsBytes);
   if (allowed != hipSuccess) return static_cast<int>(allowed);
@@ -270,7 +243,7 @@ int launch_histogram(HistArgs p, const double* matrices, int K, int64_t grid_blo
 
 bool finite_all(const double* v, int64_t n) {
   for (int64_t i = 0; i < n; ++i)
-    if (!(v[i] - v[i] == 0.0)) return false;
+    if (!is_finite(v[i])) return false;
   return true;
 }
 
@@ -280,14 +253,11 @@ bool finite_all(const double* v, int64_t n) {
 extern "C" int32_t gts_affine_resample(const void* src, int32_t dtype, int64_t X, int64_t Y, int64_t Z, const double* matrix,
                                        int64_t OX, int64_t OY, int64_t OZ, float* dst, int32_t path, void* stream) {
   using namespace gts;
-  if (dtype != 4 && dtype != 16) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype)) return GTS_ERR_ARGKIND;
   if (path != kPathAuto && path != kPathPlain && path != kPathTiled) return GTS_ERR_ARGKIND;
   if (!src || !dst || !matrix) return GTS_ERR_NULL;
+  if (!scan_extents_ok(X, Y, Z) || !scan_extents_ok(OX, OY, OZ)) return GTS_ERR_SHAPE;
   const int64_t in_dims[3] = {X, Y, Z}, out_dims[3] = {OX, OY, OZ};
-  for (int k = 0; k < 3; ++k)
-    if (in_dims[k] <= 0 || out_dims[k] <= 0 || in_dims[k] > kMaxExtent || out_dims[k] > kMaxExtent) return GTS_ERR_SHAPE;
-  int64_t n_in, n_out;
-  if (!volume_voxels(X, Y, Z, false, &n_in) || !volume_voxels(OX, OY, OZ, false, &n_out)) return GTS_ERR_SHAPE;
   if (!finite_all(matrix, 12)) return GTS_ERR_ARGKIND;
   ResampleArgs p;
   for (int j = 0; j < 12; ++j) p.T[j] = matrix[j];
@@ -296,7 +266,7 @@ extern "C" int32_t gts_affine_resample(const void* src, int32_t dtype, int64_t X
     p.out[k] = static_cast<int>(out_dims[k]);
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return dtype == 4 ? launch_resample<int16_t>(src, dst, p, path, st) : launch_resample<float>(src, dst, p, path, st);
+  return with_scan_type(dtype, src, [&](auto* s) { return launch_resample(s, dst, p, path, st); });
 }
 
 extern "C" int32_t gts_joint_histogram(const float* fixed, int64_t FX, int64_t FY, int64_t FZ, const void* moving,
@@ -304,26 +274,22 @@ extern "C" int32_t gts_joint_histogram(const float* fixed, int64_t FX, int64_t F
                                        int64_t stride, int64_t bins, double lo_f, double scale_f, double lo_m,
                                        double scale_m, int64_t* counts, int64_t grid_blocks, void* stream) {
   using namespace gts;
-  if (dtype != 4 && dtype != 16) return GTS_ERR_ARGKIND;
+  if (!scan_type_ok(dtype)) return GTS_ERR_ARGKIND;
   if (bins != 16 && bins != 32 && bins != 64) return GTS_ERR_ARGKIND;
   if (!fixed || !moving || !matrices || !counts) return GTS_ERR_NULL;
-  if (K < 1 || K > kMaxMatrices || stride < 1 || grid_blocks < 0 || grid_blocks > INT32_MAX) return GTS_ERR_SHAPE;
+  if (K < 1 || K > kMaxMatrices || stride < 1 || !grid_blocks_ok(grid_blocks)) return GTS_ERR_SHAPE;
+  if (!scan_extents_ok(X, Y, Z) || !scan_extents_ok(FX, FY, FZ)) return GTS_ERR_SHAPE;
   const int64_t in_dims[3] = {X, Y, Z}, fix_dims[3] = {FX, FY, FZ};
-  for (int k = 0; k < 3; ++k)
-    if (in_dims[k] <= 0 || fix_dims[k] <= 0 || in_dims[k] > kMaxExtent || fix_dims[k] > kMaxExtent) return GTS_ERR_SHAPE;
-  int64_t n_in, n_fix;
-  if (!volume_voxels(X, Y, Z, false, &n_in) || !volume_voxels(FX, FY, FZ, false, &n_fix)) return GTS_ERR_SHAPE;
   const double ranges[4] = {lo_f, scale_f, lo_m, scale_m};
   if (!finite_all(matrices, K * 12) || !finite_all(ranges, 4)) return GTS_ERR_ARGKIND;
   HistArgs p;
   p.fixed = fixed;
-  p.moving = moving;
   p.counts = reinterpret_cast<unsigned long long*>(counts);
   for (int k = 0; k < 3; ++k) {
     p.in[k] = static_cast<int>(in_dims[k]);
     p.fix[k] = static_cast<int>(fix_dims[k]);
   }
-  const int64_t s = stride < kMaxExtent ? stride : kMaxExtent;  // a stride beyond every extent samples index 0 only
+  const int64_t s = stride < kScanMaxExtent ? stride : kScanMaxExtent;  // a stride beyond every extent samples index 0 only
   p.stride = static_cast<int>(s);
   p.nsx = static_cast<int>((FX + s - 1) / s);
   p.nsy = static_cast<int>((FY + s - 1) / s);
@@ -334,6 +300,7 @@ extern "C" int32_t gts_joint_histogram(const float* fixed, int64_t FX, int64_t F
   hipStream_t st = static_cast<hipStream_t>(stream);
   const hipError_t cleared = hipMemsetAsync(counts, 0, static_cast<size_t>(K) * (bins * bins + 1) * sizeof(int64_t), st);
   if (cleared != hipSuccess) return static_cast<int>(cleared);
-  return dtype == 4 ? launch_histogram<int16_t>(p, matrices, static_cast<int>(K), grid_blocks, st)
-                    : launch_histogram<float>(p, matrices, static_cast<int>(K), grid_blocks, st);
+  return with_scan_type(dtype, moving, [&](auto* m) {
+    return launch_histogram(m, p, matrices, static_cast<int>(K), grid_blocks, st);
+  });
 }

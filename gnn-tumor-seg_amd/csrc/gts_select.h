@@ -3,7 +3,7 @@
 // by a voxel bit mask) share.  The element source is a template parameter of the histogram kernel; the
 // select state, the step kernel and the workspace layout are the same for both.
 #pragma once
-#include "gts_volume.h"
+#include "gts_scan.h"
 
 namespace gts {
 namespace {
@@ -13,7 +13,6 @@ constexpr int kMaxExtent = 4096;   // LDS flag arrays of I1
 constexpr int kMaxBlocks = 2048;
 constexpr int kBins = 256;
 constexpr int kHist = kChannels * 2 * kBins;   // [channel][rank][bin]
-constexpr int32_t kI16 = 4, kF32 = 16;       // NIfTI datatype codes
 
 struct SelectState {
   unsigned prefix[kChannels][2];

@@ -1,6 +1,7 @@
-// What the kernels over an int16 label volume [X, Y, Z] (Z contiguous) share: the workspace arithmetic and the
-// volume limit of their entry points, the BraTS region rule, and the wave and workgroup idioms of their
-// counting passes.  One copy of each; a new volume feature includes this instead of copying a neighbour.
+// What the kernels over a volume of three axes share, int16 labels and scan intensities alike: the workspace
+// arithmetic and the volume limit of their entry points, the BraTS region rule, and the wave and workgroup idioms
+// of their counting passes.  One copy of each; a new volume feature includes this instead of copying a
+// neighbour.  What only the scan (intensity) kernels share is in gts_scan.h, which includes this.
 #pragma once
 #include "gts_common.h"
 
@@ -57,11 +58,17 @@ __device__ __forceinline__ Xyz<I> split_xyz(I i, int Y, int Z) {
   return {row / static_cast<I>(Y), row % static_cast<I>(Y), z};
 }
 
+// the xor tree over the wave's lanes: v = op(v, the partner's v) at distances 32, 16, ... 1
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, kWave));
+  return v;  // in every lane
+}
+
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;  // in every lane
+  return wave_reduce(v, [](T a, T b) { return a + b; });
 }
 
 // body(k, same, mine) once per distinct key k among the lanes that are `on`: same is the lane mask of the

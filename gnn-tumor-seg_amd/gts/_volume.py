@@ -1,11 +1,15 @@
-"""What the wrappers of the label-volume kernels (csrc/gts_volume.h's includers) share: the shape rule, the
-checks on an int16 label tensor and the workspace of an entry point.  `what` is the caller's public name and
+"""What the wrappers of the volume kernels (the includers of csrc/gts_volume.h and gts_scan.h) share: the shape
+rule, the checks on an int16 label or mask tensor and on a scan (intensity) volume, the NIfTI dtype codes, the
+float32 output of a resampling call and the workspace of an entry point.  `what` is the caller's public name and
 leads every message."""
 import torch
 
 from . import _lib
 from ._lib import require_device
-from ._operands import scratch
+from ._operands import expect, f32, scratch
+
+I16, F32 = 4, 16                                        # NIfTI datatype codes, csrc/gts_scan.h's kI16 and kF32
+SCAN_CODES = {torch.int16: I16, torch.float32: F32}     # what a scan volume may hold
 
 
 def lift_shape(shape, what):
@@ -21,15 +25,15 @@ def lift_shape(shape, what):
     return x, y, z, any(s == 1 for s in shape)
 
 
-def label_volume(t, what, three_d=False):
+def label_volume(t, what, three_d=False, noun="labels"):
     """t, contiguous, after the checks every kernel needs: an int16 CUDA tensor with at least one element
-    ([X, Y, Z] where three_d)."""
+    ([X, Y, Z] where three_d).  noun: what the message calls the values ("masks" for a 0/1 volume)."""
     if not isinstance(t, torch.Tensor):
         raise _lib.GtsError(f"{what} takes a torch tensor")
     if t.dtype != torch.int16:
-        raise _lib.GtsError(f"{what} takes int16 labels")
+        raise _lib.GtsError(f"{what} takes int16 {noun}")
     if three_d and t.dim() != 3:
-        raise _lib.GtsError(f"{what} takes [X, Y, Z] volumes, got shape {tuple(t.shape)}")
+        raise _lib.GtsError(f"{what} takes [X, Y, Z] volumes of three axes, got shape {tuple(t.shape)}")
     if t.numel() == 0:
         raise _lib.GtsError(f"{what}: empty volume")
     if not t.is_cuda:
@@ -46,10 +50,33 @@ def label_pair(pred, truth, what, three_d=False):
     return pred, truth
 
 
-def workspace(size_fn, x, y, z, device, what):
+def scan_volume(t, what):
+    """(dtype code, d0, d1, d2) of a scan volume after the checks every kernel needs: a non-empty int16 or
+    float32 CUDA tensor of three axes, the last one contiguous."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.numel() == 0:
+        raise _lib.GtsError(f"{what} takes a non-empty [Z, Y, X] tensor")
+    if t.dtype not in SCAN_CODES:
+        raise _lib.GtsError(f"{what}: dtype {t.dtype} is not supported (int16 or float32)")
+    require_device(t)
+    return (SCAN_CODES[t.dtype],) + tuple(int(n) for n in t.shape)
+
+
+def float32_out(out, shape, like):
+    """The float32 tensor of `shape` a call writes: `out` when given (float32, that shape, on like's device: a
+    channel slice of a scan), else a new one beside `like`."""
+    if out is None:
+        return torch.empty(tuple(shape), dtype=torch.float32, device=like.device)
+    f32(out)
+    expect(out, shape, "out")
+    require_device(like, out)
+    return out
+
+
+def workspace(size_fn, x, y, z, device, what, limits=None):
     """(uint8 tensor, its size) for a volume, size_fn being the library's gts_*_workspace(X, Y, Z); a size of
-    0 is the library's refusal."""
-    size = size_fn(x, y, z)
+    0 or an error code is the library's refusal.  limits: the family's limits in words, for the message."""
+    size = int(size_fn(x, y, z))
     if size <= 0:
-        raise _lib.GtsError(f"{what}: volume {x}x{y}x{z} is outside the kernels' limits")
+        raise _lib.GtsError(f"{what}: volume {x}x{y}x{z} is outside the kernels' limits" +
+                            (f" ({limits})" if limits else ""))
     return scratch(size, device, torch.uint8), size

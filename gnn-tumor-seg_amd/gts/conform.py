@@ -154,9 +154,6 @@ def conformed_affine(plan, affine):
 
 # ---- device side -------------------------------------------------------------------------------------------------
 
-_DTYPE_CODES = {"torch.int16": 4, "torch.float32": 16}
-
-
 def _require_cuda_tensor(volume, what):
     import torch
 
@@ -182,12 +179,13 @@ def _bind(volume, axes, tables, mode, what):
     import torch
 
     from . import _lib
+    from ._volume import I16, SCAN_CODES
 
     _require_cuda_tensor(volume, what)
     if volume.dim() not in (3, 4) or volume.numel() == 0:
         raise _lib.GtsError(f"{what} takes a non-empty [C, Z, Y, X] or [Z, Y, X] volume, got {tuple(volume.shape)}")
-    code = _DTYPE_CODES.get(str(volume.dtype))
-    if code is None or (mode == MODE_NEAREST and code != 4):
+    code = SCAN_CODES.get(volume.dtype)
+    if code is None or (mode == MODE_NEAREST and code != I16):
         raise _lib.GtsError(f"{what}: dtype {volume.dtype} is not supported")
     volume = volume.contiguous()
     channels = volume.shape[0] if volume.dim() == 4 else 1

@@ -13,12 +13,12 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _volume
 from ._operands import scratch
 
 CHANNELS = 4
 QUANTILE = 0.995
-DTYPE_CODES = {np.dtype(np.int16): 4, np.dtype(np.float32): 16}   # NIfTI datatype codes
+DTYPE_CODES = {np.dtype(np.int16): _volume.I16, np.dtype(np.float32): _volume.F32}   # NIfTI datatype codes
 _TORCH = {np.dtype(np.int16): torch.int16, np.dtype(np.float32): torch.float32}
 
 

@@ -10,6 +10,7 @@ import torch
 from . import _lib
 from ._lib import check, current_stream, ptr, require_device
 from ._operands import StreamBuffers, expect, f32, scratch
+from ._volume import SCAN_CODES, float32_out, label_volume, scan_volume, workspace
 from .graph import _DeviceSchedule
 
 _ARG_DTYPE = {0: torch.uint8, 1: torch.uint8, 4: torch.int32}
@@ -1140,16 +1141,6 @@ def weighted_cross_entropy_stats(logits, labels, class_w=None):
 REGISTER_MAX_MATRICES = _lib.const("GTS_REGISTER_MAX_MATRICES")
 REGISTER_BINS = (16, 32, 64)
 RESAMPLE_AUTO, RESAMPLE_PLAIN, RESAMPLE_TILED = 0, 1, 2
-_VOLUME_CODES = {torch.int16: 4, torch.float32: 16}
-
-
-def _moving_volume(volume, what):
-    if not isinstance(volume, torch.Tensor) or volume.dim() != 3 or volume.numel() == 0:
-        raise _lib.GtsError(f"{what} takes a non-empty [Z, Y, X] tensor")
-    if volume.dtype not in _VOLUME_CODES:
-        raise _lib.GtsError(f"{what}: dtype {volume.dtype} is not supported (int16 or float32)")
-    require_device(volume)
-    return _VOLUME_CODES[volume.dtype]
 
 
 def _matrices_arg(matrices, what):
@@ -1169,18 +1160,12 @@ def affine_resample(volume, matrix, out_shape, out=None, path=RESAMPLE_AUTO):
     float64 `matrix` sends the output voxel index (x, y, z); 0 outside (include/gts_hip.h).  out_shape = (OX, OY, OZ).
     out: a contiguous float32 tensor of that shape to write (a channel slice of a scan).  path: RESAMPLE_AUTO, or one
     of the two lane maps forced (same bits)."""
-    code = _moving_volume(volume, "affine_resample")
+    code, z, y, x = scan_volume(volume, "affine_resample")
     ox, oy, oz = (int(n) for n in out_shape)
     m = _matrices_arg(matrix, "affine_resample")
     if len(m) != 1:
         raise _lib.GtsError(f"affine_resample takes one matrix, got {len(m)}")
-    if out is None:
-        out = torch.empty((oz, oy, ox), dtype=torch.float32, device=volume.device)
-    else:
-        f32(out)
-        expect(out, (oz, oy, ox), "out")
-        require_device(volume, out)
-    z, y, x = (int(n) for n in volume.shape)
+    out = float32_out(out, (oz, oy, ox), volume)
     check(_lib.load().gts_affine_resample(ptr(volume), code, x, y, z, m.ctypes.data, ox, oy, oz, ptr(out), int(path),
                                           current_stream()), "gts_affine_resample")
     return out
@@ -1193,7 +1178,7 @@ def joint_histogram(fixed, moving, matrices, stride, bins, ranges, grid_blocks=0
     of a row counts the samples outside the moving volume.  ranges = (lo_f, scale_f, lo_m, scale_m): bin = clamp(floor(
     (v - lo) * scale), 0, bins - 1), a non-finite value goes to bin 0.  grid_blocks: workgroups (0: the library's
     choice); the counts do not depend on it."""
-    code = _moving_volume(moving, "joint_histogram")
+    code, z, y, x = scan_volume(moving, "joint_histogram")
     if not isinstance(fixed, torch.Tensor) or fixed.dim() != 3 or fixed.numel() == 0:
         raise _lib.GtsError("joint_histogram takes a non-empty fixed volume [FZ, FY, FX]")
     f32(fixed)
@@ -1207,7 +1192,6 @@ def joint_histogram(fixed, moving, matrices, stride, bins, ranges, grid_blocks=0
     lo_f, scale_f, lo_m, scale_m = (float(v) for v in ranges)
     counts = torch.empty((k, int(bins) ** 2 + 1), dtype=torch.int64, device=fixed.device)
     fz, fy, fx = (int(n) for n in fixed.shape)
-    z, y, x = (int(n) for n in moving.shape)
     check(_lib.load().gts_joint_histogram(ptr(fixed), fx, fy, fz, ptr(moving), code, x, y, z, m.ctypes.data, k,
                                           int(stride), int(bins), lo_f, scale_f, lo_m, scale_m, ptr(counts),
                                           int(grid_blocks), current_stream()), "gts_joint_histogram")
@@ -1237,9 +1221,8 @@ class BiasTables:
         cells = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1)
         if weights.size != self.levels * 4 * total or cells.size != self.levels * total or len(fit) != self.levels:
             raise _lib.GtsError("bias tables do not match the shape and the number of levels")
-        nbytes = int(_lib.load().gts_bias_workspace(*self.shape, self.spans0 << (self.levels - 1)))
-        if nbytes < 0:
-            raise _lib.GtsError(f"volume {self.shape} is outside the kernels' limits (extent <= 65535, < 2^31 voxels)")
+        self.ws, _ = workspace(lambda *extents: _lib.load().gts_bias_workspace(*extents, self.spans0 << (self.levels - 1)),
+                               *self.shape, device, "bias tables", "extent <= 65535, < 2^31 voxels")
         self.weights = torch.from_numpy(weights).to(device)
         self.cells = torch.from_numpy(cells).to(device)
         self.fit = []
@@ -1248,7 +1231,6 @@ class BiasTables:
             if f.size != 8 * total:
                 raise _lib.GtsError("bias fit weights do not match the shape")
             self.fit.append(torch.from_numpy(f).to(device))
-        self.ws = scratch(nbytes, device, torch.uint8)
         self.device = self.weights.device
 
     def points(self, level):
@@ -1277,10 +1259,9 @@ def _bias_operands(u, tables, lattice, what, dtype=torch.float32):
 def bias_log(volume, threshold=0.0):
     """Z1.  (u, n): u float32 [Z, Y, X] = float32(log(float64(v))) where the volume ([Z, Y, X] int16 or float32) is
     finite and above `threshold` (>= 0), NaN elsewhere; n, an int64 device tensor [1], counts the mask voxels."""
-    code = _moving_volume(volume, "bias_log")
+    code, z, y, x = scan_volume(volume, "bias_log")
     u = torch.empty(volume.shape, dtype=torch.float32, device=volume.device)
     count = torch.empty(1, dtype=torch.int64, device=volume.device)
-    z, y, x = (int(n) for n in volume.shape)
     check(_lib.load().gts_bias_log(ptr(volume), code, x, y, z, float(threshold), ptr(u), ptr(count), current_stream()),
           "gts_bias_log")
     return u, count
@@ -1336,14 +1317,9 @@ def bias_mean(u, tables, lattice, grid_blocks=0):
 def bias_apply(volume, tables, lattice, mean, want_field=False, out=None, grid_blocks=0):
     """Z5.  float32 [Z, Y, X] = float32(float64(v) / exp(field - mean)) at every voxel of the volume (int16 or float32);
     with want_field also float32(field - mean).  out: a contiguous float32 tensor to write (a channel of a scan)."""
-    code = _moving_volume(volume, "bias_apply")
+    code = scan_volume(volume, "bias_apply")[0]
     args = _bias_operands(volume, tables, lattice, "bias_apply", dtype=None)
-    if out is None:
-        out = torch.empty(volume.shape, dtype=torch.float32, device=volume.device)
-    else:
-        f32(out)
-        expect(out, volume.shape, "out")
-        require_device(volume, out)
+    out = float32_out(out, volume.shape, volume)
     field = torch.empty(volume.shape, dtype=torch.float32, device=volume.device) if want_field else None
     check(_lib.load().gts_bias_apply(ptr(volume), code, *args, float(mean), ptr(out), ptr(field), int(grid_blocks),
                                      current_stream()), "gts_bias_apply")
@@ -1355,25 +1331,11 @@ BRAIN_BINS = _lib.const("GTS_BRAIN_BINS")
 BRAIN_MAX_R2 = _lib.const("GTS_BRAIN_MAX_R2")
 
 
-def _brain_volume(volume, what):
-    """(dtype code, X, Y, Z) of an intensity volume of three axes, the last contiguous."""
-    code = _moving_volume(volume, what)
-    return (code,) + tuple(int(n) for n in volume.shape)
-
-
 def _brain_mask(mask, what):
-    """(X, Y, Z) of an int16 mask of three axes on the device."""
-    if not isinstance(mask, torch.Tensor) or mask.dim() != 3 or mask.numel() == 0 or mask.dtype != torch.int16:
-        raise _lib.GtsError(f"{what} takes a non-empty int16 mask of three axes")
-    require_device(mask)
-    return tuple(int(n) for n in mask.shape)
-
-
-def _brain_workspace(shape, device, what):
-    size = int(_lib.load().gts_brainmask_workspace(*shape))
-    if size <= 0:
-        raise _lib.GtsError(f"{what}: volume {shape} is outside the kernels' limits (fewer than 2^31 voxels)")
-    return scratch(size, device, torch.uint8), size
+    """(the int16 mask of three axes on the device, contiguous, its kernels' workspace, the workspace's size)."""
+    mask = label_volume(mask, what, three_d=True, noun="masks")
+    return (mask,) + workspace(_lib.load().gts_brainmask_workspace, *mask.shape, mask.device, what,
+                               "fewer than 2^31 voxels")
 
 
 def brain_range(volume, grid_blocks=0):
@@ -1381,7 +1343,7 @@ def brain_range(volume, grid_blocks=0):
     their maximum as a Python float (0.0 when there is none).  One host synchronisation."""
     import struct
 
-    code, x, y, z = _brain_volume(volume, "brain_range")
+    code, x, y, z = scan_volume(volume, "brain_range")
     out = torch.empty(2, dtype=torch.int64, device=volume.device)
     check(_lib.load().gts_brain_range(ptr(volume), code, x, y, z, ptr(out), int(grid_blocks), current_stream()),
           "gts_brain_range")
@@ -1392,7 +1354,7 @@ def brain_range(volume, grid_blocks=0):
 def brain_histogram(volume, hi, grid_blocks=0):
     """S2.  int64 [BRAIN_BINS] on the device: the finite voxels > 0 by min(BINS - 1, floor(float64(v) / hi * BINS)).
     The counts do not depend on grid_blocks."""
-    code, x, y, z = _brain_volume(volume, "brain_histogram")
+    code, x, y, z = scan_volume(volume, "brain_histogram")
     counts = torch.empty(BRAIN_BINS, dtype=torch.int64, device=volume.device)
     check(_lib.load().gts_brain_histogram(ptr(volume), code, x, y, z, float(hi), ptr(counts), int(grid_blocks),
                                           current_stream()), "gts_brain_histogram")
@@ -1401,7 +1363,7 @@ def brain_histogram(volume, hi, grid_blocks=0):
 
 def brain_threshold(volume, t, grid_blocks=0):
     """S2.  (mask int16 0/1 of the volume's shape, count int64 device tensor [1]): finite, > 0 and float64(v) >= t."""
-    code, x, y, z = _brain_volume(volume, "brain_threshold")
+    code, x, y, z = scan_volume(volume, "brain_threshold")
     mask = torch.empty(volume.shape, dtype=torch.int16, device=volume.device)
     count = torch.empty(1, dtype=torch.int64, device=volume.device)
     check(_lib.load().gts_brain_threshold(ptr(volume), code, x, y, z, float(t), ptr(mask), ptr(count), int(grid_blocks),
@@ -1412,12 +1374,11 @@ def brain_threshold(volume, t, grid_blocks=0):
 def ball_morph(mask, r2, target, outside, invert, grid_blocks=0):
     """S3.  int16 0/1: ((squared distance to the nearest voxel whose value (!= 0) equals `target` <= r2) != invert),
     positions outside the volume counting as `target` iff `outside` (include/gts_hip.h)."""
-    shape = _brain_mask(mask, "ball_morph")
+    mask, ws, size = _brain_mask(mask, "ball_morph")
     if int(r2) != r2 or not 0 <= int(r2) <= BRAIN_MAX_R2:
         raise _lib.GtsError(f"ball_morph: squared radius {r2!r} is outside 0..{BRAIN_MAX_R2}")
-    ws, size = _brain_workspace(shape, mask.device, "ball_morph")
     out = torch.empty_like(mask)
-    check(_lib.load().gts_ball_morph_i16(ptr(mask), *shape, int(r2), int(bool(target)), int(bool(outside)), ptr(out),
+    check(_lib.load().gts_ball_morph_i16(ptr(mask), *mask.shape, int(r2), int(bool(target)), int(bool(outside)), ptr(out),
                                          ptr(ws), size, int(bool(invert)), int(grid_blocks), current_stream()),
           "gts_ball_morph_i16")
     return out
@@ -1437,13 +1398,12 @@ def largest_component(mask, connectivity=6, grid_blocks=0):
     """S4.  (keep int16 0/1, stats int64 device tensor [5] = components, voxels of the largest, of the second largest,
     the winner's root, voxels of the mask): the component of mask != 0 with the most voxels, a tie going to the smaller root.  An empty
     mask gives an empty keep and zeros; gts.brainmask.largest_component raises for it."""
-    shape = _brain_mask(mask, "largest_component")
+    mask, ws, size = _brain_mask(mask, "largest_component")
     if connectivity not in (6, 26):
         raise _lib.GtsError(f"largest_component: connectivity {connectivity!r} (6 or 26)")
-    ws, size = _brain_workspace(shape, mask.device, "largest_component")
     keep = torch.empty_like(mask)
     stats = torch.empty(5, dtype=torch.int64, device=mask.device)
-    check(_lib.load().gts_largest_component_i16(ptr(mask), *shape, int(connectivity), ptr(keep), ptr(stats), ptr(ws),
+    check(_lib.load().gts_largest_component_i16(ptr(mask), *mask.shape, int(connectivity), ptr(keep), ptr(stats), ptr(ws),
                                                 size, int(grid_blocks), current_stream()), "gts_largest_component_i16")
     return keep, stats
 
@@ -1451,11 +1411,10 @@ def largest_component(mask, connectivity=6, grid_blocks=0):
 def fill_holes(mask, grid_blocks=0):
     """S5.  (filled int16 0/1, stats int64 device tensor [2] = voxels of the result, voxels filled):
     scipy.ndimage.binary_fill_holes."""
-    shape = _brain_mask(mask, "fill_holes")
-    ws, size = _brain_workspace(shape, mask.device, "fill_holes")
+    mask, ws, size = _brain_mask(mask, "fill_holes")
     out = torch.empty_like(mask)
     stats = torch.empty(2, dtype=torch.int64, device=mask.device)
-    check(_lib.load().gts_fill_holes_i16(ptr(mask), *shape, ptr(out), ptr(stats), ptr(ws), size, int(grid_blocks),
+    check(_lib.load().gts_fill_holes_i16(ptr(mask), *mask.shape, ptr(out), ptr(stats), ptr(ws), size, int(grid_blocks),
                                          current_stream()), "gts_fill_holes_i16")
     return out, stats
 
@@ -1463,8 +1422,9 @@ def fill_holes(mask, grid_blocks=0):
 def apply_mask(scan, mask, grid_blocks=0):
     """S6.  (masked scan of scan's dtype, count int64 device tensor [1]): scan ([C, *mask.shape] or mask's shape, int16
     or float32) where mask != 0, 0 elsewhere (NaN and Inf included)."""
-    shape = _brain_mask(mask, "apply_mask")
-    if not isinstance(scan, torch.Tensor) or scan.dtype not in _VOLUME_CODES:
+    mask = label_volume(mask, "apply_mask", three_d=True, noun="masks")
+    shape = tuple(mask.shape)
+    if not isinstance(scan, torch.Tensor) or scan.dtype not in SCAN_CODES:
         raise _lib.GtsError("apply_mask takes an int16 or float32 tensor")
     if tuple(scan.shape[-3:]) != shape or scan.dim() not in (3, 4) or scan.numel() == 0:
         raise _lib.GtsError(f"apply_mask: scan {tuple(scan.shape)} does not lie over the mask {shape}")
@@ -1472,6 +1432,6 @@ def apply_mask(scan, mask, grid_blocks=0):
     channels = int(scan.shape[0]) if scan.dim() == 4 else 1
     out = torch.empty_like(scan)
     count = torch.empty(1, dtype=torch.int64, device=mask.device)
-    check(_lib.load().gts_apply_mask(ptr(scan), _VOLUME_CODES[scan.dtype], channels, *shape, ptr(mask), ptr(out),
+    check(_lib.load().gts_apply_mask(ptr(scan), SCAN_CODES[scan.dtype], channels, *shape, ptr(mask), ptr(out),
                                      ptr(count), int(grid_blocks), current_stream()), "gts_apply_mask")
     return out, count

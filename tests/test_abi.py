@@ -142,6 +142,98 @@ def test_argument_errors_do_not_need_a_gpu(hip_lib):
     assert hip_lib.gts_spmm_max_fwd_f32(one, one, one, one, None, 0, 1, 0, 4, None) == 0
 
 
+def _scan_refusals():
+    """(label, entry point, arguments, expected code) of calls that the scan-volume entry points (conform,
+    co-registration, bias correction, brain extraction) refuse before they touch memory or the device.  Per entry
+    point: arguments that pass every check (the pointers are never followed), where its dtype code, its extents,
+    its grid_blocks and its float64 scalars stand, and the code each kind of refusal gives (recorded from the
+    library as it was when each entry point still spelt its own guards, not from csrc/gts_scan.h's)."""
+    one, nan, big = ctypes.c_void_p(16), float("nan"), 1 << 40
+    eye = (ctypes.c_double * 12)(1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0)
+    nans = (ctypes.c_double * 12)(*[nan] * 12)
+    rows = [one, 5, 6, 7, one, one, one, 2, 1]            # u, X, Y, Z, weights, cells, lattice, spans0, levels
+    # name: (arguments, dtype at, extents at, every extent below 65536 on its own, grid_blocks at, {NaN at: value},
+    #        codes for dtype 8, extent 0, extent 65536, grid_blocks -1, NaN)
+    entries = {
+        "gts_conform_gather": ([one, 4, 1, 5, 6, 7, 0, 1, 2, 5, 6, 7, one, one, one, 1, one, None],
+                               1, (3, 4, 5, 9, 10, 11), True, None, {}, (-3, -2, -2, None, None)),
+        "gts_affine_resample": ([one, 4, 5, 6, 7, eye, 5, 6, 7, one, 0, None],
+                                1, (2, 3, 4, 6, 7, 8), True, None, {5: nans}, (-3, -2, -2, None, -3)),
+        "gts_joint_histogram": ([one, 5, 6, 7, one, 4, 5, 6, 7, eye, 1, 1, 16, 0.0, 1.0, 0.0, 1.0, one, 0, None],
+                                5, (1, 2, 3, 6, 7, 8), True, 18, {9: nans, 13: nan, 14: nan, 15: nan, 16: nan},
+                                (-3, -2, -2, -2, -3)),
+        "gts_bias_workspace": ([5, 6, 7, 2], None, (0, 1, 2), True, None, {}, (None, -2, -2, None, None)),
+        "gts_bias_log": ([one, 4, 5, 6, 7, 0.0, one, one, None], 1, (2, 3, 4), True, None, {5: nan},
+                         (-3, -2, -2, None, -3)),
+        "gts_bias_range": (rows + [one, one, big, 0, None], None, (1, 2, 3), True, 12, {}, (None, -2, -2, -2, None)),
+        "gts_bias_histogram": (rows + [0.0, 1.0, one, 0, None], None, (1, 2, 3), True, 12, {9: nan, 10: nan},
+                               (None, -2, -2, -2, -3)),
+        "gts_bias_fit": (rows + [0, one, 0.0, 1.0, one, one, one, big, 0, None], None, (1, 2, 3), True, 17,
+                         {11: nan, 12: nan}, (None, -2, -2, -2, -3)),
+        "gts_bias_mean": (rows + [one, one, big, 0, None], None, (1, 2, 3), True, 12, {}, (None, -2, -2, -2, None)),
+        "gts_bias_apply": ([one, 4] + rows[1:] + [0.0, one, None, 0, None], 1, (2, 3, 4), True, 13, {10: nan},
+                           (-3, -2, -2, -2, -3)),
+        "gts_brain_range": ([one, 4, 5, 6, 7, one, 0, None], 1, (2, 3, 4), False, 6, {}, (-3, -2, -2, -2, None)),
+        "gts_brain_histogram": ([one, 4, 5, 6, 7, 1.0, one, 0, None], 1, (2, 3, 4), False, 7, {5: nan},
+                                (-3, -2, -2, -2, -3)),
+        "gts_brain_threshold": ([one, 4, 5, 6, 7, 1.0, one, one, 0, None], 1, (2, 3, 4), False, 8, {5: nan},
+                                (-3, -2, -2, -2, -3)),
+        "gts_ball_morph_i16": ([one, 5, 6, 7, 4, 1, 0, one, one, big, 0, 0, None], None, (1, 2, 3), False, 11, {},
+                               (None, -2, -2, -2, None)),
+        "gts_largest_component_i16": ([one, 5, 6, 7, 6, one, one, one, big, 0, None], None, (1, 2, 3), False, 9, {},
+                                      (None, -2, -2, -2, None)),
+        "gts_fill_holes_i16": ([one, 5, 6, 7, one, one, one, big, 0, None], None, (1, 2, 3), False, 8, {},
+                               (None, -2, -2, -2, None)),
+        "gts_apply_mask": ([one, 4, 2, 5, 6, 7, one, one, one, 0, None], 1, (3, 4, 5), False, 9, {},
+                           (-3, -2, -2, -2, None)),
+    }
+
+    def changed(args, changes):
+        return [changes.get(at, value) for at, value in enumerate(args)]
+
+    for name, (good, dtype_at, extents_at, each, grid_at, nan_at, codes) in entries.items():
+        if dtype_at is not None:
+            yield f"{name} dtype 8", name, changed(good, {dtype_at: 8}), codes[0]
+        for at in extents_at:
+            yield f"{name} extent 0 at {at}", name, changed(good, {at: 0}), codes[1]
+            if each:
+                yield f"{name} extent 65536 at {at}", name, changed(good, {at: 65536}), codes[2]
+        if not each:   # brain extraction has no limit per extent: 65536 along every axis is past its 2^31 voxels
+            yield f"{name} every extent 65536", name, changed(good, {at: 65536 for at in extents_at}), codes[2]
+        if grid_at is not None:
+            yield f"{name} grid_blocks -1", name, changed(good, {grid_at: -1}), codes[3]
+        for at, value in nan_at.items():
+            yield f"{name} NaN at {at}", name, changed(good, {at: value}), codes[4]
+
+
+def test_scan_entry_points_refuse_bad_arguments_with_their_own_codes(hip_lib):
+    """A bad dtype code, extent, grid_blocks or NaN scalar gives its own code, and of two bad arguments the one an
+    entry point checks first answers: the order of its checks is part of an entry point's contract, and the guards
+    that csrc/gts_scan.h shares must not change it."""
+    cases = list(_scan_refusals())
+    assert len(cases) == 142
+    for label, name, args, want in cases:
+        assert want in (-2, -3), label
+        assert getattr(hip_lib, name)(*args) == want, label
+    # two things wrong at once: the check that comes first in an entry point still answers
+    one, top = ctypes.c_void_p(16), 65535
+
+    def conform(c, x, axes):
+        return hip_lib.gts_conform_gather(one, 4, c, x, x, x, *axes, 5, 6, 7, one, one, one, 1, one, None)
+    assert conform(1, top, (0, 0, 2)) == -3             # the axes are looked at before the number of voxels
+    assert conform(1, 0, (0, 0, 2)) == -2               # and after the extents
+    assert conform(1, top, (0, 1, 2)) == -2
+    assert conform(0, top, (0, 1, 2)) == 0              # no channel: nothing to index, nothing launched
+    assert conform(-1, 5, (0, 1, 2)) == -2
+    assert hip_lib.gts_brain_range(None, 8, 5, 6, 7, one, 0, None) == -1                     # NULL, then the dtype
+    assert hip_lib.gts_brain_range(one, 8, 0, 6, 7, one, 0, None) == -3                      # the dtype, then the shape
+    assert hip_lib.gts_bias_apply(one, 8, 0, 6, 7, one, one, one, 2, 1, 0.0, one, None, 0, None) == -3
+    assert hip_lib.gts_intake_occupancy(one, 8, 0, 6, 7, one, one, one, one, None) == -2     # the shape, then the dtype
+    assert hip_lib.gts_intake_occupancy(one, 8, 5, 6, 7, one, one, one, one, None) == -3
+    assert hip_lib.gts_dataset_stats_mask(one, 8, one, 5, 6, 7, one, one, 0, None) == -2     # the workspace's size first
+    assert hip_lib.gts_dataset_stats_mask(one, 8, one, 5, 6, 7, one, one, 1 << 40, None) == -3
+
+
 def test_cluster_schedule_rejects_a_malformed_csr(hip_lib):
     """gts_cluster_schedule is a HOST entry point of the C ABI: ids outside [0, n), extents that go down or that do not
     match the transpose must come back as GTS_ERR_SHAPE, not index the builder's tables."""

@@ -147,6 +147,78 @@ def test_resample_modalities_writes_channel_slices_and_refuses_bad_operands(hip_
         ops.joint_histogram(got[0], src, np.stack([mats[0]] * 17), 1, 32, (0.0, 1.0, 0.0, 1.0))
 
 
+# ---- R1 against conform: the two features share one sampler (csrc/gts_scan.h) ------------------------------------------
+
+# (perm, signs, offsets of the shape): output axis perm[j] runs along input axis j, u_j = signs[j] * i + offsets[j].
+# Offsets are an integer shift plus 0, 0.25 or 0.5, so u, floor(u) and u - floor(u) are exact in float64 whether T @ (x,
+# y, z, 1) forms them on the device or numpy does for conform's tables: both features must then give the same bits.
+# The first map keeps x on x (conform's row kernel, R1's plain lane map), the others move it (the tiled kernels).
+DYADIC_MAPS = [((0, 1, 2), (1, 1, 1), lambda n: (0.25, 0.5, 1.0)),
+               ((1, 0, 2), (1, -1, 1), lambda n: (1.5, n[1] - 1.25, 0.0)),
+               ((2, 0, 1), (-1, 1, -1), lambda n: (n[0] - 1.5, 0.25, n[2] - 2.0)),
+               ((2, 1, 0), (1, 1, -1), lambda n: (2.25, 0.0, n[2] - 1.5))]
+
+
+def _dyadic_map(shape, perm, signs, offsets):
+    """(T, out_shape, axes, tables, inside [OX, OY, OZ]) of one map: R1's matrix, and conform's input axis and
+    AxisTables per output axis built from the same numbers by R1's rule (i0 = min(floor(u), n - 1), i1 = min(i0 + 1,
+    n - 1), t = u - i0).  An index R1 leaves outside gets the table entry (0, 0, 0.0) and is not compared."""
+    from gts.conform import AxisTables
+
+    T, out, axes, tables, inside = np.zeros((3, 4)), [0] * 3, [0] * 3, [None] * 3, [None] * 3
+    for j in range(3):
+        w, n = perm[j], shape[j]
+        T[j, w], T[j, 3], out[w], axes[w] = signs[j], offsets[j], n, j
+        u = signs[j] * np.arange(n, dtype=np.float64) + offsets[j]
+        inside[w] = (u >= 0) & (u <= n - 1)
+        i0 = np.where(inside[w], np.minimum(np.floor(u), n - 1), 0.0)
+        i1 = np.where(inside[w], np.minimum(i0 + 1, n - 1), 0.0)
+        tables[w] = AxisTables(i0.astype(np.int32), i1.astype(np.int32), np.where(inside[w], u - i0, 0.0))
+    return T, tuple(out), tuple(axes), tuple(tables), inside[0][:, None, None] & inside[1][None, :, None] & inside[2]
+
+
+def _check_against_conform(a, perm, signs, offsets):
+    from gts import conform, ops
+
+    T, out_shape, axes, tables, inside = _dyadic_map(a.shape, perm, signs, offsets)
+    assert inside.any() and not inside.all()
+    src = _dev(a)
+    want = _host(conform._gather(src, axes, tables, conform.MODE_TRILINEAR, "test"))
+    assert want.dtype == np.float32 and want.shape == out_shape
+    assert want[inside].tobytes() == R.affine_resample(a, T, out_shape)[inside].tobytes(), (a.shape, a.dtype, perm)
+    for path in (ops.RESAMPLE_AUTO, ops.RESAMPLE_PLAIN, ops.RESAMPLE_TILED):
+        got = _host(ops.affine_resample(src, T, out_shape, path=path))
+        assert got[inside].tobytes() == want[inside].tobytes(), (a.shape, a.dtype, perm, path)
+        assert not got[~inside].any()
+    return want, inside
+
+
+@pytest.mark.parametrize("shape", [(5, 6, 7), (65, 3, 18)])
+def test_resample_and_conform_give_the_same_bits_on_dyadic_maps(hip_lib, shape):
+    for dtype in (np.int16, np.float32):
+        a = _values(shape, dtype, 16)
+        for perm, signs, offsets in DYADIC_MAPS:
+            _check_against_conform(a, perm, signs, offsets(shape))
+
+
+def test_resample_and_conform_agree_on_a_nan_neighbour_without_weight(hip_lib):
+    """Whole offsets along the input's x: every sample lies on a voxel along x, and its other x neighbour, NaN or not,
+    carries no weight.  The voxel before the NaN stays finite in both features, the NaN itself is sampled by both."""
+    shape = (5, 6, 7)
+    a = _values(shape, np.float32, 17)
+    a[3, 2, 4] = np.nan
+    for perm, signs, offsets in DYADIC_MAPS:
+        off = offsets(shape)
+        off = (float(np.floor(off[0])),) + tuple(off[1:])
+        want, inside = _check_against_conform(a, perm, signs, off)
+        reads_x = (signs[0] * np.arange(shape[0]) + off[0]).astype(int)          # input x of output index i along perm[0]
+        by_x = np.moveaxis(want, perm[0], 0)
+        ok = np.moveaxis(inside, perm[0], 0)
+        for i, x in enumerate(reads_x):
+            if ok[i].any():
+                assert np.isnan(by_x[i][ok[i]]).any() == (x == 3), (perm, i, x)
+
+
 # ---- R2 --------------------------------------------------------------------------------------------------------------
 
 def _fixed(shape, seed):
