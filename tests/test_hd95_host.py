@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 from scipy.ndimage import binary_erosion, generate_binary_structure
 
+from tests.hd95_ref import border_lifted as _border_lifted
+
 
 def _order_stats(d2):
     from gts.metrics import percentile95_from_order_stats
@@ -34,21 +36,6 @@ def test_percentile_finish_rejects_an_empty_multiset():
 
     with pytest.raises(ValueError):
         percentile95_from_order_stats(0, 0, 0)
-
-
-def _border_lifted(mask, x, y, z, all_border):
-    """The kernels' border rule, restated in numpy on the lifted [X, Y, Z] volume."""
-    m = mask.reshape(x, y, z).astype(bool)
-    if all_border:
-        return m
-    inner = m.copy()
-    for axis in range(3):
-        if m.shape[axis] == 1:
-            continue
-        padded = np.pad(m, [(1, 1) if a == axis else (0, 0) for a in range(3)], constant_values=False)
-        n = m.shape[axis]
-        inner &= np.take(padded, range(0, n), axis=axis) & np.take(padded, range(2, n + 2), axis=axis)
-    return m & ~inner
 
 
 @pytest.mark.parametrize("shape", [(9, 7, 6), (1, 9, 7, 6), (11, 8), (9, 1, 6), (1, 1, 13), (13,), (1, 5, 1, 4)])
