@@ -1,0 +1,144 @@
+"""Written predictions -> how much tumour there is, where, and how big each lesion is, on the MI355X.
+
+Every {id}.nii.gz in PRED_DIR, as segment_scans and the two generate_* scripts write it, is decoded, mapped to the
+internal labels and measured per region (WT, CT, ET) by gts.measure.tumour_report (definitions: DESIGN.md 4y): per
+lesion the volume in ml, the centroid and extent in mm, the face-count area, the largest 3-D diameter and, on the
+planes of constant last axis, the major diameter, the caliper width perpendicular to it and their product (in the
+spirit of RANO's bidimensional product; not a reader's protocol).  Files may hold {0, 1, 2, 4} or the 2023
+convention {0, 1, 2, 3}; a file with both 3 and 4, or any other value, is refused.  The voxel spacing is read from
+each file's own affine (its column norms).
+
+One CSV row per (scan, region, lesion), the lesions of a region by descending size, and one `total` row per (scan,
+region); --json writes the whole report as well.  The GPU takes one scan at a time while a small thread pool decodes
+the next ones.  A file that cannot be measured is reported and left out; the exit status is then 1.
+
+    python -m scripts.measure_tumours -s PRED_DIR -o report.csv --json report.json --min_lesion_voxels 10
+"""
+import argparse
+import json
+import os
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+_PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _PKG not in sys.path:
+    sys.path.insert(0, _PKG)
+
+import numpy as np  # noqa: E402
+
+from data_processing import labels as label_maps  # noqa: E402
+from data_processing import nifti_io  # noqa: E402
+from scripts.score_predictions import IO_WORKERS, READ_AHEAD, spacing_of  # noqa: E402
+
+REGIONS = ("WT", "CT", "ET")
+SUFFIX = ".nii.gz"
+HEADER = ["id", "region", "lesion", "n_lesions", "root", "voxels", "volume_ml", "ml_label1", "ml_label2", "ml_label3",
+          "centroid_x_mm", "centroid_y_mm", "centroid_z_mm", "extent_x_mm", "extent_y_mm", "extent_z_mm",
+          "face_area_mm2", "diameter_mm", "plane_z", "plane_major_mm", "plane_minor_mm", "plane_product_mm2"]
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description="Per-lesion volumes, extents and diameters of written predictions on "
+                                                 "MI355X")
+    parser.add_argument("-s", "--pred_dir", required=True, help="folder holding the predictions, {id}.nii.gz")
+    parser.add_argument("-o", "--output", required=True, help="the CSV file to write")
+    parser.add_argument("--json", default=None, metavar="FILE", help="also write the whole report as JSON")
+    parser.add_argument("--connectivity", type=int, default=26, choices=(6, 26),
+                        help="voxels of one lesion are connected through faces (6) or faces, edges and corners (26)")
+    parser.add_argument("--min_lesion_voxels", type=int, default=1,
+                        help="a smaller lesion is counted in the totals but gets no row")
+    parser.add_argument("--regions", nargs="+", default=list(REGIONS), choices=REGIONS, help="the regions to report")
+    return parser
+
+
+def find_predictions(pred_dir):
+    """{id: path} of every {id}.nii.gz directly in pred_dir."""
+    return {f[:-len(SUFFIX)]: os.path.join(pred_dir, f) for f in sorted(os.listdir(pred_dir)) if f.endswith(SUFFIX)}
+
+
+def load_prediction(path):
+    """Host stage: (internal int16 labels, C-contiguous; spacing in mm)."""
+    labels = label_maps.swap_labels_from_brats_any(nifti_io.read_nifti(path, np.int16))
+    if labels.ndim != 3:
+        raise ValueError(f"the label volume has {labels.ndim} axes, expected 3")
+    return np.ascontiguousarray(labels), spacing_of(path)
+
+
+def _cell(value):
+    return repr(value) if isinstance(value, float) else str(value)
+
+
+def rows_of(scan_id, report, regions=REGIONS):
+    """The CSV rows (lists of strings, HEADER's order) of one scan's tumour_report: per region its lesions in the
+    report's order, numbered from 1, then the `total` row."""
+    rows = []
+    for region in regions:
+        record = report[region]
+        for rank, m in enumerate(record["lesions"], 1):
+            rows.append([scan_id, region, rank, "", m["root"], m["n"], m["volume_ml"]] + m["class_ml"] +
+                        m["centroid_mm"] + m["extent_mm"] +
+                        [m["face_area_mm2"], m["diameter_mm"], m["plane_z"], m["plane_major_mm"], m["plane_minor_mm"],
+                         m["plane_product_mm2"]])
+        rows.append([scan_id, region, "total", record["n_lesions"], "", record["voxels"], record["ml"]] +
+                    record["class_ml"] + [""] * 12)
+    return [[_cell(v) for v in row] for row in rows]
+
+
+def write_csv(path, rows):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        f.write(",".join(HEADER) + "\n")
+        for row in rows:
+            f.write(",".join(row) + "\n")
+
+
+def measure(paths, connectivity=26, min_lesion_voxels=1):
+    """({id: {"spacing_mm", "regions": tumour_report}}, ids left out) of {id: path}."""
+    import torch
+
+    from gts import measure as gts_measure
+
+    ids = sorted(paths)
+    reports, failed = {}, []
+    with ThreadPoolExecutor(max_workers=IO_WORKERS) as pool:
+        pending = {i: pool.submit(load_prediction, paths[ids[i]]) for i in range(min(READ_AHEAD, len(ids)))}
+        for i, scan_id in enumerate(ids):
+            if i + READ_AHEAD < len(ids):
+                pending[i + READ_AHEAD] = pool.submit(load_prediction, paths[ids[i + READ_AHEAD]])
+            try:
+                labels, spacing = pending.pop(i).result()
+                report = gts_measure.tumour_report(torch.from_numpy(labels).cuda(), spacing, connectivity,
+                                                   min_lesion_voxels)
+                reports[scan_id] = dict(spacing_mm=list(spacing), regions=report)
+            except Exception as exc:
+                print(f"{scan_id}: left out ({exc!r})")
+                failed.append(scan_id)
+    return reports, failed
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    paths = find_predictions(os.path.expanduser(args.pred_dir))
+    print(f"{len(paths)} predictions found; the report goes to {args.output}")
+    reports, failed = measure(paths, args.connectivity, args.min_lesion_voxels)
+    rows = [row for scan_id in sorted(reports) for row in rows_of(scan_id, reports[scan_id]["regions"], args.regions)]
+    write_csv(os.path.expanduser(args.output), rows)
+    if args.json:
+        path = os.path.expanduser(args.json)
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(reports, f, indent=1, sort_keys=True)
+    for scan_id in sorted(reports):
+        for region in args.regions:
+            record = reports[scan_id]["regions"][region]
+            largest = record["lesions"][0] if record["lesions"] else None
+            print(f"{scan_id} {region}: {record['ml']:.2f} ml in {record['n_lesions']} lesion(s)" +
+                  (f", the largest {largest['volume_ml']:.2f} ml, {largest['diameter_mm']:.1f} mm across, "
+                   f"{largest['plane_major_mm']:.1f} x {largest['plane_minor_mm']:.1f} mm in slice {largest['plane_z']}"
+                   if largest else ""))
+    print(f"{len(reports)} prediction(s) measured, {len(failed)} left out")
+    return 1 if failed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

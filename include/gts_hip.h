@@ -1208,6 +1208,55 @@ int32_t gts_fill_holes_i16(const int16_t* mask, int64_t X, int64_t Y, int64_t Z,
 int32_t gts_apply_mask(const void* src, int32_t dtype, int64_t C, int64_t X, int64_t Y, int64_t Z, const int16_t* mask,
                        void* dst, uint64_t* count, int64_t grid_blocks, void* stream);
 
+/* ---- M1-M4: per-lesion measurements of one label volume (no counterpart in the reference) ----------
+ * labels int16 [X][Y][Z] (Z contiguous, internal labels 0..3); region 0 WT, 1 CT, 2 ET; roots int32 [X][Y][Z] from
+ * gts_components_roots_i16 on the region's 0 / 1 mask (gts_lesionwise_dilate_i16 with dilation 0 writes it) at
+ * `connectivity` 6 or 26.  A lesion is a component of that mask.  units (HOST int64 [3], read at the call): the voxel
+ * spacing as integers in [1, 10^6] (gts.metrics.spacing_units).  Every result is an exact int64 that depends neither
+ * on grid_blocks (0: the library's choice, else 1 .. 2^31 - 1) nor on any order of arrival.
+ * Refusals, nothing being launched: a NULL pointer GTS_ERR_NULL; then an extent outside [1, 4097], X * Y * Z >= 2^31,
+ * a bad grid_blocks, a workspace below gts_measure_workspace(X, Y, Z) bytes or a table below
+ * gts_measure_table_i64s(X, Y, Z, connectivity) entries (both 0 for a refused shape) GTS_ERR_SHAPE; then a region,
+ * connectivity or unit out of range GTS_ERR_ARGKIND; then, with B = sum_a u_a^2 (N_a - 1)^2, 2 B >= 2^62
+ * GTS_ERR_SHAPE (it needs the units to be valid).  gts_measure_check makes these checks on a shape and units alone.
+ * table (device int64): a header of GTS_MEASURE_HEAD_I64 entries { lesions, slice rows, 3-D candidates, in-plane
+ * candidates, 0 .. } and one row of GTS_MEASURE_ROW_I64 entries per lesion in arrival order (sort by root):
+ *    0 root (1 + the smallest linear index)   1 n   2..4 voxels of label 1, 2, 3
+ *    5..10 the box as max(x + 1), max(X - x), max(y + 1), max(Y - y), max(z + 1), max(Z - z)
+ *   11..13 sum of x, y, z   14..16 faces F_x, F_y, F_z: (voxel, direction +-a) pairs whose neighbour is outside the mask
+ *       or the volume   17 3-D candidates   18 end of its 3-D candidate list (start before M2)   19 its first slice row
+ *   20 D3 = max over voxel pairs of sum_a u_a^2 d_a^2   21..23 plane z*, D2, W (see csrc/gts_measure.hip)
+ * gts_measure_tables_i16 (M1): clears the header and the rows it uses and fills fields 0..19.  One row per 2 x 2 x 2 cell suffices at
+ *   connectivity 26, one per two voxels at 6.
+ * gts_measure_candidates (M2): the lists of hull-vertex candidates in the workspace, per lesion (3-D: a voxel that
+ *   lacks one of its two neighbours along each of x, y, z) and per lesion and slice of constant z (along x and y).
+ * gts_measure_diameters (M3): field 20.  work (device int32 [n_work][3]): (row, tile i, tile j >= i) over a row's
+ *   3-D candidates in tiles of GTS_MEASURE_PAIR_TILE; a unit outside the table or the list is skipped.  n_work 0:
+ *   nothing is launched.
+ * gts_measure_planes (M4): fields 21..23.  work (device int32 [n_work][2]): (row, z - the box's first z); slices
+ *   (device int64 [n_slices][2], n_slices = header entry 1, cleared by the call) receives (D2_z, W_z) per slice row,
+ *   pairs taken in tiles of GTS_MEASURE_PLANE_TILE; z* is the smallest z with the largest W_z.  n_work 0: nothing is
+ *   launched. */
+#define GTS_MEASURE_HEAD_I64 8
+#define GTS_MEASURE_ROW_I64 24
+#define GTS_MEASURE_PAIR_TILE 256
+#define GTS_MEASURE_PLANE_TILE 256
+int64_t gts_measure_workspace(int64_t X, int64_t Y, int64_t Z);
+int64_t gts_measure_table_i64s(int64_t X, int64_t Y, int64_t Z, int32_t connectivity);
+int32_t gts_measure_check(int64_t X, int64_t Y, int64_t Z, const int64_t* units);
+int32_t gts_measure_tables_i16(const int16_t* labels, const int32_t* roots, int64_t X, int64_t Y, int64_t Z,
+                               int32_t region, int32_t connectivity, int64_t* table, int64_t table_i64s,
+                               void* workspace, int64_t workspace_bytes, int64_t grid_blocks, void* stream);
+int32_t gts_measure_candidates(const int32_t* roots, int64_t X, int64_t Y, int64_t Z, int64_t* table,
+                               int64_t table_i64s, void* workspace, int64_t workspace_bytes, int64_t grid_blocks,
+                               void* stream);
+int32_t gts_measure_diameters(int64_t X, int64_t Y, int64_t Z, const int64_t* units, const int32_t* work,
+                              int64_t n_work, int64_t* table, int64_t table_i64s, const void* workspace,
+                              int64_t workspace_bytes, int64_t grid_blocks, void* stream);
+int32_t gts_measure_planes(int64_t X, int64_t Y, int64_t Z, const int64_t* units, const int32_t* work, int64_t n_work,
+                           int64_t* slices, int64_t n_slices, int64_t* table, int64_t table_i64s,
+                           const void* workspace, int64_t workspace_bytes, int64_t grid_blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
