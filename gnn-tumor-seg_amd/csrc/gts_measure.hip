@@ -89,29 +89,6 @@ __device__ __forceinline__ bool is_candidate(unsigned m, int axes) {
   return c;
 }
 
-// the exclusive prefix of v over the workgroup's threads and, in *total, the sum; every thread calls it
-__device__ __forceinline__ int64_t block_scan_exclusive(int64_t v, int64_t* total) {
-  __shared__ int64_t wave_total[kWavesPerBlock];
-  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-  int64_t inc = v;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const int64_t t = __shfl_up(inc, off, kWave);
-    if (lane >= off) inc += t;
-  }
-  if (lane == kWave - 1) wave_total[w] = inc;
-  __syncthreads();
-  int64_t before = 0, all = 0;
-#pragma unroll
-  for (int k = 0; k < kWavesPerBlock; ++k) {
-    if (k < w) before += wave_total[k];
-    all += wave_total[k];
-  }
-  __syncthreads();
-  *total = all;
-  return before + inc - v;
-}
-
 // the maximum of v over the workgroup, in every thread; every thread calls it
 __device__ __forceinline__ int64_t block_max(int64_t v) {
   __shared__ int64_t wave_top[kWavesPerBlock];

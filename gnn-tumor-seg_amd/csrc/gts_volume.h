@@ -103,4 +103,27 @@ __device__ __forceinline__ void block_add_counters(const unsigned (&mine)[N], Gl
     atomicAdd(&global[threadIdx.x], static_cast<Global>(block_counts[threadIdx.x]));
 }
 
+// the exclusive prefix of v over the workgroup's threads and, in *total, the sum; every thread calls it
+__device__ __forceinline__ int64_t block_scan_exclusive(int64_t v, int64_t* total) {
+  __shared__ int64_t wave_total[kWavesPerBlock];
+  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+  int64_t inc = v;
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) {
+    const int64_t t = __shfl_up(inc, off, kWave);
+    if (lane >= off) inc += t;
+  }
+  if (lane == kWave - 1) wave_total[w] = inc;
+  __syncthreads();
+  int64_t before = 0, all = 0;
+#pragma unroll
+  for (int k = 0; k < kWavesPerBlock; ++k) {
+    if (k < w) before += wave_total[k];
+    all += wave_total[k];
+  }
+  __syncthreads();
+  *total = all;
+  return before + inc - v;
+}
+
 }  // namespace gts

@@ -186,20 +186,39 @@ def lesion_measurements(labels, region, spacing_mm=(1, 1, 1), connectivity=26, *
     return [derive(table, k) for k in range(len(table["root"]))]
 
 
-def report_from_table(table, min_lesion_voxels=1):
-    """One region's part of tumour_report from its lesion_table."""
+def report_from_table(table, min_lesion_voxels=1, features=None):
+    """One region's part of tumour_report from its lesion_table.  features: gts.mesh.shape_features of the same
+    region in lesion order; each listed lesion then carries its keys too."""
     u, s = table["units"], table["scale_mm"]
     voxels = int(table["n"].sum())
     classes = [int(v) for v in table["n_class"].sum(axis=0)] if len(table["n"]) else [0, 0, 0]
     order = sorted(range(len(table["n"])), key=lambda k: (-int(table["n"][k]), int(table["root"][k])))
     return dict(voxels=voxels, ml=volume_ml(voxels, u, s), class_ml=[volume_ml(c, u, s) for c in classes],
                 n_lesions=len(order),
-                lesions=[derive(table, k) for k in order if int(table["n"][k]) >= min_lesion_voxels])
+                lesions=[dict(derive(table, k), **(features[k] if features is not None else {}))
+                         for k in order if int(table["n"][k]) >= min_lesion_voxels])
 
 
-def tumour_report(labels, spacing_mm=(1, 1, 1), connectivity=26, min_lesion_voxels=1):
+def tumour_report(labels, spacing_mm=(1, 1, 1), connectivity=26, min_lesion_voxels=1, *, mesh=False,
+                  smooth_iterations=20, meshes=None):
     """{"WT" | "CT" | "ET": record}: voxels and ml of the region, class_ml (the region's voxels of label 1, 2, 3 in
     ml), n_lesions, and `lesions`, the dicts of `derive` sorted by descending n, then root.  A lesion of fewer than
-    min_lesion_voxels voxels is counted in the totals and in n_lesions but not listed."""
-    return {name: report_from_table(lesion_table(labels, name, spacing_mm, connectivity), min_lesion_voxels)
-            for name in REGIONS}
+    min_lesion_voxels voxels is counted in the totals and in n_lesions but not listed.
+
+    mesh=True: each listed lesion also carries gts.mesh.shape_features' keys (the triangle surface of DESIGN.md 4z
+    after smooth_iterations Taubin iterations); meshes, a dict, then receives every region's gts.mesh.region_mesh."""
+    report = {}
+    for name in REGIONS:
+        table = lesion_table(labels, name, spacing_mm, connectivity)
+        features = None
+        if mesh:
+            from . import mesh as gts_mesh
+
+            surface = gts_mesh.region_mesh(labels, name, spacing_mm, connectivity, smooth_iterations=smooth_iterations)
+            if not np.array_equal(surface["root"], table["root"]):
+                raise _lib.GtsError(f"tumour_report: the mesh and the table of {name} list different lesions")
+            features = gts_mesh.shape_features(surface)
+            if meshes is not None:
+                meshes[name] = surface
+        report[name] = report_from_table(table, min_lesion_voxels, features)
+    return report

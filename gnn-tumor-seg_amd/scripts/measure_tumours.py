@@ -12,7 +12,13 @@ One CSV row per (scan, region, lesion), the lesions of a region by descending si
 region); --json writes the whole report as well.  The GPU takes one scan at a time while a small thread pool decodes
 the next ones.  A file that cannot be measured is reported and left out; the exit status is then 1.
 
+--mesh adds the triangle surface of every region (gts.mesh): the columns of MESH_HEADER after the
+existing ones (raw mesh area and volume, the same after --mesh_smooth Taubin iterations, sphericity, surface to
+volume), and with --mesh_dir DIR a binary PLY per (scan, region), DIR/{id}_{region}.ply, in the world coordinates of
+the file's own affine.  Without --mesh the CSV and the JSON are what they were.
+
     python -m scripts.measure_tumours -s PRED_DIR -o report.csv --json report.json --min_lesion_voxels 10
+    python -m scripts.measure_tumours -s PRED_DIR -o report.csv --mesh --mesh_dir meshes
 """
 import argparse
 import json
@@ -35,6 +41,8 @@ SUFFIX = ".nii.gz"
 HEADER = ["id", "region", "lesion", "n_lesions", "root", "voxels", "volume_ml", "ml_label1", "ml_label2", "ml_label3",
           "centroid_x_mm", "centroid_y_mm", "centroid_z_mm", "extent_x_mm", "extent_y_mm", "extent_z_mm",
           "face_area_mm2", "diameter_mm", "plane_z", "plane_major_mm", "plane_minor_mm", "plane_product_mm2"]
+MESH_HEADER = ["mesh_triangles", "mesh_area_mm2", "mesh_volume_ml", "smooth_area_mm2", "smooth_volume_ml", "sphericity",
+               "surface_to_volume_per_mm"]       # gts.mesh.FEATURE_KEYS, appended by --mesh
 
 
 def build_parser():
@@ -48,6 +56,12 @@ def build_parser():
     parser.add_argument("--min_lesion_voxels", type=int, default=1,
                         help="a smaller lesion is counted in the totals but gets no row")
     parser.add_argument("--regions", nargs="+", default=list(REGIONS), choices=REGIONS, help="the regions to report")
+    parser.add_argument("--mesh", action="store_true",
+                        help="also mesh every region (marching tetrahedra) and append the shape columns")
+    parser.add_argument("--mesh_smooth", type=int, default=20, metavar="N",
+                        help="Taubin iterations before the smooth area, volume and sphericity (0: the raw mesh)")
+    parser.add_argument("--mesh_dir", default=None, metavar="DIR",
+                        help="with --mesh: write DIR/{id}_{region}.ply in each file's world coordinates")
     return parser
 
 
@@ -68,9 +82,10 @@ def _cell(value):
     return repr(value) if isinstance(value, float) else str(value)
 
 
-def rows_of(scan_id, report, regions=REGIONS):
+def rows_of(scan_id, report, regions=REGIONS, mesh=False):
     """The CSV rows (lists of strings, HEADER's order) of one scan's tumour_report: per region its lesions in the
-    report's order, numbered from 1, then the `total` row."""
+    report's order, numbered from 1, then the `total` row.  mesh: MESH_HEADER's columns after them (empty in the
+    `total` row), from a report made with mesh=True."""
     rows = []
     for region in regions:
         record = report[region]
@@ -78,25 +93,31 @@ def rows_of(scan_id, report, regions=REGIONS):
             rows.append([scan_id, region, rank, "", m["root"], m["n"], m["volume_ml"]] + m["class_ml"] +
                         m["centroid_mm"] + m["extent_mm"] +
                         [m["face_area_mm2"], m["diameter_mm"], m["plane_z"], m["plane_major_mm"], m["plane_minor_mm"],
-                         m["plane_product_mm2"]])
+                         m["plane_product_mm2"]] + ([m[key] for key in MESH_HEADER] if mesh else []))
         rows.append([scan_id, region, "total", record["n_lesions"], "", record["voxels"], record["ml"]] +
-                    record["class_ml"] + [""] * 12)
+                    record["class_ml"] + [""] * (12 + (len(MESH_HEADER) if mesh else 0)))
     return [[_cell(v) for v in row] for row in rows]
 
 
-def write_csv(path, rows):
+def write_csv(path, rows, mesh=False):
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
-        f.write(",".join(HEADER) + "\n")
+        f.write(",".join(HEADER + (MESH_HEADER if mesh else [])) + "\n")
         for row in rows:
             f.write(",".join(row) + "\n")
 
 
-def measure(paths, connectivity=26, min_lesion_voxels=1):
-    """({id: {"spacing_mm", "regions": tumour_report}}, ids left out) of {id: path}."""
+def measure(paths, connectivity=26, min_lesion_voxels=1, mesh=False, mesh_smooth=20, mesh_dir=None, regions=REGIONS):
+    """({id: {"spacing_mm", "regions": tumour_report}}, ids left out) of {id: path}.  mesh: the report carries the
+    shape features; mesh_dir: the PLY files of `regions` go there."""
     import torch
 
     from gts import measure as gts_measure
+
+    if mesh and mesh_dir:
+        from gts import mesh as gts_mesh
+
+        os.makedirs(mesh_dir, exist_ok=True)
 
     ids = sorted(paths)
     reports, failed = {}, []
@@ -107,8 +128,18 @@ def measure(paths, connectivity=26, min_lesion_voxels=1):
                 pending[i + READ_AHEAD] = pool.submit(load_prediction, paths[ids[i + READ_AHEAD]])
             try:
                 labels, spacing = pending.pop(i).result()
-                report = gts_measure.tumour_report(torch.from_numpy(labels).cuda(), spacing, connectivity,
-                                                   min_lesion_voxels)
+                if not mesh:
+                    report = gts_measure.tumour_report(torch.from_numpy(labels).cuda(), spacing, connectivity,
+                                                       min_lesion_voxels)
+                else:
+                    meshes = {}
+                    report = gts_measure.tumour_report(torch.from_numpy(labels).cuda(), spacing, connectivity,
+                                                       min_lesion_voxels, mesh=True, smooth_iterations=mesh_smooth,
+                                                       meshes=meshes)
+                    if mesh_dir:
+                        affine, _ = nifti_io.read_affine(paths[scan_id])
+                        for region in regions:
+                            gts_mesh.write_ply(os.path.join(mesh_dir, f"{scan_id}_{region}.ply"), meshes[region], affine)
                 reports[scan_id] = dict(spacing_mm=list(spacing), regions=report)
             except Exception as exc:
                 print(f"{scan_id}: left out ({exc!r})")
@@ -120,9 +151,13 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     paths = find_predictions(os.path.expanduser(args.pred_dir))
     print(f"{len(paths)} predictions found; the report goes to {args.output}")
-    reports, failed = measure(paths, args.connectivity, args.min_lesion_voxels)
-    rows = [row for scan_id in sorted(reports) for row in rows_of(scan_id, reports[scan_id]["regions"], args.regions)]
-    write_csv(os.path.expanduser(args.output), rows)
+    if args.mesh_dir and not args.mesh:
+        raise SystemExit("--mesh_dir needs --mesh")
+    reports, failed = measure(paths, args.connectivity, args.min_lesion_voxels, args.mesh, args.mesh_smooth,
+                              os.path.expanduser(args.mesh_dir) if args.mesh_dir else None, args.regions)
+    rows = [row for scan_id in sorted(reports)
+            for row in rows_of(scan_id, reports[scan_id]["regions"], args.regions, args.mesh)]
+    write_csv(os.path.expanduser(args.output), rows, args.mesh)
     if args.json:
         path = os.path.expanduser(args.json)
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)

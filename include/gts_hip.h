@@ -1257,6 +1257,60 @@ int32_t gts_measure_planes(int64_t X, int64_t Y, int64_t Z, const int64_t* units
                            int64_t* slices, int64_t n_slices, int64_t* table, int64_t table_i64s,
                            const void* workspace, int64_t workspace_bytes, int64_t grid_blocks, void* stream);
 
+/* ---- T1-T5: triangle surfaces of one region's lesions (no counterpart in the reference) -------------
+ * Marching tetrahedra on the six Kuhn tetrahedra of every cell of the mask padded by one layer of zeros; definitions,
+ * orders and the 16-case rule: csrc/gts_mesh.hip.  roots int32 [X][Y][Z] from gts_components_roots_i16 on the region's
+ * 0 / 1 mask at `connectivity` 6 or 26.  Coordinates are half-index units (2 x the voxel-centre index).  Every integer
+ * result depends neither on grid_blocks (0: the library's choice, else 1 .. 2^31 - 1) nor on any order of arrival;
+ * every float64 result is a gather in a fixed order, bit for bit the same on every run.
+ * Refusals, nothing being launched: a NULL pointer that is needed GTS_ERR_NULL; then an extent outside [1, 4097],
+ * (X + 1)(Y + 1)(Z + 1) >= 2^31, a bad grid_blocks, more than 2^31 - 1 vertices or (2^31 - 1) / 3 triangles, a
+ * workspace below gts_mesh_workspace(X, Y, Z) (gts_mesh_adjacency_workspace(n_vertices)) bytes or a table below
+ * gts_mesh_table_i64s(X, Y, Z, connectivity) entries (0 for a refused shape) GTS_ERR_SHAPE; then a connectivity, unit
+ * (outside [1, 10^6]), scale (outside (0, 10^6]) or factor (not finite) out of range GTS_ERR_ARGKIND.
+ * table (device int64): a header of GTS_MESH_HEAD_I64 entries { lesions, vertices, triangles, 0 .. } and one row of
+ * GTS_MESH_ROW_I64 entries per lesion in arrival order (sort by root):
+ *    0 root   1 triangles   2..9 triangles per normal class: entry 1 + k for |normal| = (k >> 2 & 1, k >> 1 & 1, k & 1),
+ *    k = 1..7, and entry 9 for any other normal (always 0)   10 V6 = sum of p0 . (p1 x p2), 48 x the volume in voxels
+ *    (modulo 2^64: exact for a closed surface, which every lesion's is at connectivity 26)
+ * gts_mesh_classify (T1, T2): the table, and in the workspace every cell's corner mask and the bases of the emit pass.
+ * gts_mesh_emit (T3), after the header came to the host: vertices int32 [n_vertices][3] by ascending (owner cell,
+ *   direction), faces int32 [n_faces][3] by ascending (cell, tetrahedron, index), normals out of the lesion, and
+ *   face_slot int32 [n_faces], the table row of the face's lesion.  n_vertices and n_faces are the header's; 0: nothing
+ *   is launched.
+ * gts_mesh_relabel: face_slot[f] = rank[face_slot[f]] (-1 outside [0, n_rank)): arrival order to the caller's order.
+ * gts_mesh_adjacency (T4): the CSR of { b : (a, b) is a directed edge of a face }, row_start int32 [n_vertices + 1],
+ *   neighbours int32 [3 n_faces], every row ascending.
+ * gts_mesh_positions: positions[v][a] = (double)(vertices[v][a] * units[a]) * scale_mm / 2.0 (units: HOST int64 [3]).
+ * gts_mesh_smooth (T5): `iterations` times P += lambda (mean - P), then P += mu (mean - P), each a Jacobi step between
+ *   positions and scratch (float64 [n_vertices][3]); mean = (the neighbours' sum, left to right in row order) / degree.
+ *   The result is in positions.
+ * gts_mesh_terms (T5): per face area = 0.5 * sqrt((cx cx + cy cy) + cz cz), c = (p1 - p0) x (p2 - p0), and volume =
+ *   ((p0x dx + p0y dy) + p0z dz) / 6.0, d = p1 x p2; no contraction. */
+#define GTS_MESH_HEAD_I64 8
+#define GTS_MESH_ROW_I64 12
+int64_t gts_mesh_workspace(int64_t X, int64_t Y, int64_t Z);
+int64_t gts_mesh_table_i64s(int64_t X, int64_t Y, int64_t Z, int32_t connectivity);
+int64_t gts_mesh_adjacency_workspace(int64_t n_vertices);
+int32_t gts_mesh_classify(const int32_t* roots, int64_t X, int64_t Y, int64_t Z, int32_t connectivity, int64_t* table,
+                          int64_t table_i64s, void* workspace, int64_t workspace_bytes, int64_t grid_blocks,
+                          void* stream);
+int32_t gts_mesh_emit(const int32_t* roots, int64_t X, int64_t Y, int64_t Z, void* workspace, int64_t workspace_bytes,
+                      int32_t* vertices, int64_t n_vertices, int32_t* faces, int32_t* face_slot, int64_t n_faces,
+                      int64_t grid_blocks, void* stream);
+int32_t gts_mesh_relabel(int32_t* face_slot, int64_t n_faces, const int32_t* rank, int64_t n_rank, int64_t grid_blocks,
+                         void* stream);
+int32_t gts_mesh_adjacency(const int32_t* faces, int64_t n_faces, int64_t n_vertices, int32_t* row_start,
+                           int32_t* neighbours, void* workspace, int64_t workspace_bytes, int64_t grid_blocks,
+                           void* stream);
+int32_t gts_mesh_positions(const int32_t* vertices, int64_t n_vertices, const int64_t* units, double scale_mm,
+                           double* positions, int64_t grid_blocks, void* stream);
+int32_t gts_mesh_smooth(const int32_t* row_start, const int32_t* neighbours, int64_t n_vertices, int64_t n_faces,
+                        double* positions, double* scratch, double lambda, double mu, int64_t iterations,
+                        int64_t grid_blocks, void* stream);
+int32_t gts_mesh_terms(const double* positions, const int32_t* faces, int64_t n_vertices, int64_t n_faces,
+                       double* area, double* volume, int64_t grid_blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
