@@ -295,8 +295,6 @@ constexpr int kMaxThresholds = 4;
 constexpr int kOutInts = 4 + 2 * kMaxThresholds;   // one region's row of gts_surface_stats_i16's table
 constexpr int kRadixBins = 256;
 constexpr int kSelectBlocks = 256;                   // H5w: workgroups per region and pass
-constexpr int64_t kMaxUnit = 1000000;                // 100 mm in steps of 1e-4 mm
-constexpr int64_t kMaxExtent = 4097;                 // H2's uint16 distances
 
 struct Thresholds {
   long long t[kMaxThresholds];
@@ -562,17 +560,12 @@ struct SurfaceLayout {
   int top_shift;  // shift of the highest 8-bit digit a D2 of this volume can have
 };
 
-inline bool surface_units_ok(const int64_t* units) {
-  return units[0] >= 1 && units[1] >= 1 && units[2] >= 1 && units[0] <= kMaxUnit && units[1] <= kMaxUnit &&
-         units[2] <= kMaxUnit;
-}
-
 // false for extents outside [1, 4097], X * Y * Z >= 2^31 or B * max(N_a) >= 2^62 with B = sum u_a^2 (N_a - 1)^2:
 // every D2 and every h is then at most B and every product of `hidden` stays inside int64.  units must have
-// passed surface_units_ok (u^2 (N - 1)^2 <= 10^12 * 2^24 then fits the 128-bit sums used here).
+// passed units_ok (u^2 (N - 1)^2 <= 10^12 * 2^24 then fits the 128-bit sums used here).
 inline bool surface_layout(int64_t X, int64_t Y, int64_t Z, const int64_t* units, SurfaceLayout* l) {
   if (!volume_voxels(X, Y, Z, false, &l->n)) return false;
-  if (X > kMaxExtent || Y > kMaxExtent || Z > kMaxExtent) return false;
+  if (X > kMmMaxExtent || Y > kMmMaxExtent || Z > kMmMaxExtent) return false;
   const int64_t extent[3] = {X, Y, Z};
   unsigned __int128 bound = 0;
   int64_t longest = 1;
@@ -600,7 +593,7 @@ inline bool surface_layout(int64_t X, int64_t Y, int64_t Z, const int64_t* units
 
 extern "C" int64_t gts_surface_workspace(int64_t X, int64_t Y, int64_t Z, const int64_t* units) {
   gts::SurfaceLayout l;
-  return units && gts::surface_units_ok(units) && gts::surface_layout(X, Y, Z, units, &l) ? l.total : 0;
+  return units && gts::units_ok(units) && gts::surface_layout(X, Y, Z, units, &l) ? l.total : 0;
 }
 
 extern "C" int32_t gts_surface_stats_i16(const int16_t* pred, const int16_t* truth, int64_t X, int64_t Y, int64_t Z,
@@ -611,7 +604,7 @@ extern "C" int32_t gts_surface_stats_i16(const int16_t* pred, const int16_t* tru
   if (!pred || !truth || !units || !out || !workspace) return GTS_ERR_NULL;
   if (n_thresholds < 0 || n_thresholds > kMaxThresholds) return GTS_ERR_ARGKIND;
   if (n_thresholds > 0 && !thresholds) return GTS_ERR_NULL;
-  if (!surface_units_ok(units) || (all_border != 0 && all_border != 1)) return GTS_ERR_ARGKIND;
+  if (!units_ok(units) || (all_border != 0 && all_border != 1)) return GTS_ERR_ARGKIND;
   Thresholds th = {{0, 0, 0, 0}, n_thresholds};
   for (int t = 0; t < n_thresholds; ++t) {
     if (thresholds[t] < 0) return GTS_ERR_ARGKIND;

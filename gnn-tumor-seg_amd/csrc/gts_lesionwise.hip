@@ -20,8 +20,8 @@
 //       voxels whose D root is the lesion's) as label 3 over a box of the volume, the input pair of H1.
 //
 // Integer arithmetic and integer atomics (add, max) only: identical results on every run.  The region rule
-// (in_region, the one H1 uses), the volume limit and the per-key wave loop of L2 are gts_volume.h's.
-#include "gts_volume.h"
+// (in_region, the one H1 uses), the volume limit, the per-key wave loop of L2 and L2's bound are the shared headers'.
+#include "gts_lesions.h"
 
 namespace gts {
 namespace {
@@ -264,9 +264,6 @@ inline bool lesion_voxels(int64_t X, int64_t Y, int64_t Z, int64_t* n) { return 
 
 inline int64_t lesion_words(int64_t X, int64_t Y, int64_t Z) { return X * Y * ((Z + kWave - 1) / kWave); }
 
-// the most roots, and the most appended pairs, a volume can hold: one per 2 x 2 x 2 cell
-inline int64_t lesion_cells(int64_t X, int64_t Y, int64_t Z) { return ((X + 1) / 2) * ((Y + 1) / 2) * ((Z + 1) / 2); }
-
 // L2: cursors | slot_p int32[n] | slot_d int32[n] | lesion rows | component rows | pairs
 inline int64_t lesion_tables_bytes(int64_t n, int64_t cells) {
   return kHeaderBytes + 2 * round256(4 * n) + 2 * round256(4 * kRowInts * cells) + round256(8 * cells);
@@ -287,14 +284,14 @@ extern "C" int64_t gts_lesionwise_workspace(int64_t X, int64_t Y, int64_t Z) {
   int64_t n;
   if (!gts::lesion_voxels(X, Y, Z, &n)) return 0;
   const int64_t dilate = gts::round256(8 * gts::lesion_words(X, Y, Z));
-  const int64_t tables = gts::lesion_tables_bytes(n, gts::lesion_cells(X, Y, Z));
+  const int64_t tables = gts::lesion_tables_bytes(n, gts::lesion_rows(X, Y, Z, 26));
   return dilate > tables ? dilate : tables;
 }
 
 extern "C" int64_t gts_lesionwise_table_ints(int64_t X, int64_t Y, int64_t Z) {
   int64_t n;
   if (!gts::lesion_voxels(X, Y, Z, &n)) return 0;
-  return 4 + (2 * gts::kRowInts + 2) * gts::lesion_cells(X, Y, Z);
+  return 4 + (2 * gts::kRowInts + 2) * gts::lesion_rows(X, Y, Z, 26);
 }
 
 extern "C" int32_t gts_lesionwise_dilate_i16(const int16_t* labels, int64_t X, int64_t Y, int64_t Z, int32_t region,
@@ -331,7 +328,7 @@ extern "C" int32_t gts_lesionwise_tables_i16(const int16_t* truth, const int32_t
   int64_t n;
   if (!lesion_voxels(X, Y, Z, &n)) return GTS_ERR_SHAPE;
   if (region < 0 || region > 2) return GTS_ERR_ARGKIND;
-  const int64_t cells = lesion_cells(X, Y, Z);
+  const int64_t cells = lesion_rows(X, Y, Z, 26);  // roots, and appended pairs, are pairwise not 26-adjacent
   if (workspace_bytes < lesion_tables_bytes(n, cells) || tables_ints < 4 + (2 * kRowInts + 2) * cells)
     return GTS_ERR_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -18,11 +18,11 @@
 //            The lesion reports (z*, D2_z*, W_z*), z* the smallest z with maximal W_z.  Distances are centre to
 //            centre, so a one-pixel footprint measures 0.
 //
-//   M1  table pass.  Every root voxel takes a row from an atomic cursor and clears it (arrival order; the row carries
-//       its root and the host sorts by it); one pass over labels and roots then adds every voxel's counts, box,
-//       coordinate sums, face counts and whether it is a 3-D candidate to its lesion's row, the lanes of one lesion
-//       summed in the wave first.  A single workgroup then scans the rows: the first slice row of every lesion (one
-//       row per z of its box) and the start of its candidate list.
+//   M1  table pass.  Every root voxel takes a row (gts_lesions.h: lesion_rows_kernel, at most lesion_rows of them);
+//       one pass over labels and roots then adds every voxel's counts, box, coordinate sums, face counts and whether
+//       it is a 3-D candidate to its lesion's row, the lanes of one lesion summed in the wave first.  A single
+//       workgroup then scans the rows: the first slice row of every lesion (one row per z of its box) and the start
+//       of its candidate list.
 //   M2  candidate lists.  A diameter endpoint and a caliper extreme are vertices of the convex hull, and a hull
 //       vertex cannot have lesion voxels on both sides along an axis (it would be their midpoint).  So the 3-D
 //       candidates are the voxels that lack one of their two neighbours along x, along y and along z, the in-plane
@@ -41,7 +41,7 @@
 // every grid_blocks.  Limits: every extent in [1, 4097], X * Y * Z < 2^31, units in [1, 10^6], and with
 // B = sum_a u_a^2 (N_a - 1)^2, 2 B < 2^62: u_a (N_a - 1) then fits an int32, every squared distance is at most B and
 // |p.P_r| <= 2 u_x (N_x - 1) u_y (N_y - 1) <= B, so a projection range is at most 2 B.
-#include "gts_volume.h"
+#include "gts_lesions.h"
 
 namespace gts {
 namespace {
@@ -50,9 +50,6 @@ constexpr int kRow = GTS_MEASURE_ROW_I64;
 constexpr int kHead = GTS_MEASURE_HEAD_I64;
 constexpr int kPairTile = GTS_MEASURE_PAIR_TILE;
 constexpr int kPlaneTile = GTS_MEASURE_PLANE_TILE;
-constexpr int kMaxExtent = 4097;
-constexpr int64_t kMaxUnit = 1000000;
-constexpr int64_t kMaxGrid = 1 << 16;  // the library's choice is at most this many workgroups
 typedef unsigned long long u64;
 
 static_assert(kPairTile == kBlock && kPlaneTile == kBlock, "one thread stages one point of a tile");
@@ -62,6 +59,7 @@ enum { fRoot = 0, fN = 1, fClass = 2, fBox = 5, fSum = 11, fFace = 14, fCand = 1
        fD3 = 20, fPlaneZ = 21, fPlaneD2 = 22, fPlaneW = 23 };
 // header fields
 enum { hLesions = 0, hSlices = 1, hCand3 = 2, hCand2 = 3 };
+static_assert(hLesions == 0 && fRoot == 0, "the table convention of lesion_rows_kernel");
 
 struct Vol {
   int X, Y, Z;
@@ -103,20 +101,6 @@ __device__ __forceinline__ int64_t block_max(int64_t v) {
 }
 
 // ------------------------------------------------------------------ M1
-__global__ __launch_bounds__(kBlock) void measure_slots_kernel(const int* __restrict__ roots, int* __restrict__ slot,
-                                                               int64_t* table, int64_t n, int64_t cap) {
-  for (int64_t i = int64_t{blockIdx.x} * kBlock + threadIdx.x; i < n; i += int64_t{gridDim.x} * kBlock) {
-    if (roots[i] != i + 1) continue;
-    const int64_t s = static_cast<int64_t>(atomicAdd(reinterpret_cast<u64*>(table + hLesions), u64{1}));
-    slot[i] = static_cast<int>(s < cap ? s : cap);  // cap: no row (cannot happen for the roots of C1-C3)
-    if (s >= cap) continue;
-    int64_t* row = table + kHead + s * kRow;  // only the rows in use are cleared, not a table sized for the worst case
-    row[fRoot] = i + 1;
-#pragma unroll
-    for (int f = 1; f < kRow; ++f) row[f] = 0;
-  }
-}
-
 __global__ __launch_bounds__(kBlock) void measure_tables_kernel(const int16_t* __restrict__ labels,
                                                                 const int* __restrict__ roots,
                                                                 const int* __restrict__ slot, int64_t* table, Vol v,
@@ -378,17 +362,11 @@ __global__ __launch_bounds__(kBlock) void measure_resolve_kernel(int64_t* table,
 
 // ------------------------------------------------------------------ host
 inline bool measure_voxels(int64_t X, int64_t Y, int64_t Z, int64_t* n) {
-  return volume_voxels(X, Y, Z, false, n) && X <= kMaxExtent && Y <= kMaxExtent && Z <= kMaxExtent;
-}
-
-// the most lesions a volume can hold: no two roots share a 2 x 2 x 2 cell at connectivity 26; at connectivity 6
-// the lesions' first voxels are pairwise not face-adjacent, an independent set of the grid, at most ceil(n / 2)
-inline int64_t measure_rows(int64_t X, int64_t Y, int64_t Z, int connectivity) {
-  return connectivity == 26 ? ((X + 1) / 2) * ((Y + 1) / 2) * ((Z + 1) / 2) : (X * Y * Z + 1) / 2;
+  return volume_voxels(X, Y, Z, false, n) && X <= kMmMaxExtent && Y <= kMmMaxExtent && Z <= kMmMaxExtent;
 }
 
 inline int64_t measure_table_i64s(int64_t X, int64_t Y, int64_t Z, int connectivity) {
-  return kHead + kRow * measure_rows(X, Y, Z, connectivity);
+  return kHead + kRow * lesion_rows(X, Y, Z, connectivity);
 }
 
 // header | slot int32[n] | slice ends int32[n] | 3-D candidates int32[n] | in-plane candidates int32[n]
@@ -403,19 +381,6 @@ inline MeasureBuffers measure_buffers(void* workspace, int64_t n) {
   const int64_t part = round256(4 * n);
   return {reinterpret_cast<int*>(ws), reinterpret_cast<int*>(ws + part), reinterpret_cast<int*>(ws + 2 * part),
           reinterpret_cast<int*>(ws + 3 * part)};
-}
-
-inline bool grid_ok(int64_t grid_blocks) { return grid_blocks >= 0 && grid_blocks <= INT32_MAX; }
-
-inline int grid_for(int64_t items, int64_t per_block, int64_t grid_blocks) {
-  const int64_t need = items > 0 ? (items + per_block - 1) / per_block : 1;
-  return static_cast<int>(grid_blocks > 0 ? grid_blocks : (need < kMaxGrid ? need : kMaxGrid));
-}
-
-inline bool units_ok(const int64_t* units) {
-  for (int a = 0; a < 3; ++a)
-    if (units[a] < 1 || units[a] > kMaxUnit) return false;
-  return true;
 }
 
 // 2 * sum_a u_a^2 (N_a - 1)^2 < 2^62, for units that passed units_ok and extents that passed measure_voxels
@@ -471,11 +436,11 @@ extern "C" int32_t gts_measure_tables_i16(const int16_t* labels, const int32_t* 
   if (table_i64s < measure_table_i64s(X, Y, Z, connectivity)) return GTS_ERR_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const MeasureBuffers b = measure_buffers(workspace, n);
-  const int64_t cap = measure_rows(X, Y, Z, connectivity);
+  const int64_t cap = lesion_rows(X, Y, Z, connectivity);
   const Vol v = {static_cast<int>(X), static_cast<int>(Y), static_cast<int>(Z), n};
   if (hipMemsetAsync(table, 0, 8 * kHead, st) != hipSuccess) return launch_status();
   const int grid = grid_for(n, kBlock, grid_blocks);
-  measure_slots_kernel<<<grid, kBlock, 0, st>>>(roots, b.slot, table, n, cap);
+  lesion_rows_kernel<kHead, kRow><<<grid, kBlock, 0, st>>>(roots, b.slot, table, n, cap);
   measure_tables_kernel<<<grid, kBlock, 0, st>>>(labels, roots, b.slot, table, v, region, cap);
   measure_scan_rows_kernel<<<1, kBlock, 0, st>>>(table, v.Z, cap);
   return launch_status();

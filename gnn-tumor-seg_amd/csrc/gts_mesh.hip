@@ -41,20 +41,18 @@
 //
 // Integer atomics and plain vector stores only in T1-T4; no float atomics anywhere: identical results on every run and
 // at every grid_blocks.  Limits: every extent in [1, 4097], (X+1)(Y+1)(Z+1) < 2^31, vertices and triangles < 2^31 each.
-#include "gts_volume.h"
+#include "gts_lesions.h"
 
 namespace gts {
 namespace {
 
 constexpr int kRow = GTS_MESH_ROW_I64;
 constexpr int kHead = GTS_MESH_HEAD_I64;
-constexpr int kMaxExtent = 4097;
-constexpr int64_t kMaxUnit = 1000000;
-constexpr int64_t kMaxGrid = 1 << 16;
 typedef unsigned long long u64;
 
 enum { fRoot = 0, fTris = 1, fClass = 2, fV6 = 10 };                 // row fields
 enum { hLesions = 0, hVertices = 1, hTriangles = 2 };                // header fields
+static_assert(hLesions == 0 && fRoot == 0, "the table convention of lesion_rows_kernel");
 
 // ------------------------------------------------------------------ the 16-case rule, at compile time
 struct I3 {
@@ -207,21 +205,7 @@ __device__ __forceinline__ int root_at(const int* __restrict__ roots, const Cell
 }
 
 // ------------------------------------------------------------------ T1
-__global__ __launch_bounds__(kBlock) void mesh_slots_kernel(const int* __restrict__ roots, int* __restrict__ slot,
-                                                            int64_t* table, int64_t n, int64_t cap) {
-  for (int64_t i = int64_t{blockIdx.x} * kBlock + threadIdx.x; i < n; i += int64_t{gridDim.x} * kBlock) {
-    if (roots[i] != i + 1) continue;
-    const int64_t s = static_cast<int64_t>(atomicAdd(reinterpret_cast<u64*>(table + hLesions), u64{1}));
-    slot[i] = static_cast<int>(s < cap ? s : cap);  // cap: no row (cannot happen for the roots of C1-C3)
-    if (s >= cap) continue;
-    int64_t* row = table + kHead + s * kRow;
-    row[fRoot] = i + 1;
-#pragma unroll
-    for (int f = 1; f < kRow; ++f) row[f] = 0;
-  }
-}
-
-// what one tetrahedron adds to its lesion's row
+// what one tetrahedron adds to its lesion's row (every root took one through gts_lesions.h's lesion_rows_kernel)
 struct TetTerms {
   int root;      // the smallest root among the inside corners; 0: no triangle
   int tris;
@@ -589,13 +573,8 @@ __global__ __launch_bounds__(kBlock) void mesh_terms_kernel(const double* __rest
 
 // ------------------------------------------------------------------ host
 inline bool mesh_cells(int64_t X, int64_t Y, int64_t Z, int64_t* voxels, int64_t* cells) {
-  if (!volume_voxels(X, Y, Z, false, voxels) || X > kMaxExtent || Y > kMaxExtent || Z > kMaxExtent) return false;
+  if (!volume_voxels(X, Y, Z, false, voxels) || X > kMmMaxExtent || Y > kMmMaxExtent || Z > kMmMaxExtent) return false;
   return volume_voxels(X + 1, Y + 1, Z + 1, false, cells);
-}
-
-// as M1: no two roots share a 2 x 2 x 2 cell at connectivity 26; at 6 the roots are an independent set of the grid
-inline int64_t mesh_rows(int64_t X, int64_t Y, int64_t Z, int connectivity) {
-  return connectivity == 26 ? ((X + 1) / 2) * ((Y + 1) / 2) * ((Z + 1) / 2) : (X * Y * Z + 1) / 2;
 }
 
 inline int64_t chunks_of(int64_t n) { return (n + kBlock - 1) / kBlock; }
@@ -625,13 +604,6 @@ inline MeshBuffers mesh_buffers(void* workspace, int64_t voxels, int64_t cells) 
 // cursors int32[V] | chunk bases int64[chunks of V] | the total int64
 inline int64_t adjacency_bytes(int64_t V) { return round256(4 * V) + round256(8 * chunks_of(V)) + 256; }
 
-inline bool grid_ok(int64_t grid_blocks) { return grid_blocks >= 0 && grid_blocks <= INT32_MAX; }
-
-inline int grid_for(int64_t items, int64_t grid_blocks) {
-  const int64_t need = items > 0 ? (items + kBlock - 1) / kBlock : 1;
-  return static_cast<int>(grid_blocks > 0 ? grid_blocks : (need < kMaxGrid ? need : kMaxGrid));
-}
-
 inline bool counts_ok(int64_t V, int64_t F) { return V >= 0 && F >= 0 && V <= INT32_MAX && F <= INT32_MAX / 3; }
 
 }  // namespace
@@ -645,7 +617,7 @@ extern "C" int64_t gts_mesh_workspace(int64_t X, int64_t Y, int64_t Z) {
 extern "C" int64_t gts_mesh_table_i64s(int64_t X, int64_t Y, int64_t Z, int32_t connectivity) {
   int64_t voxels, cells;
   if (!gts::mesh_cells(X, Y, Z, &voxels, &cells) || (connectivity != 6 && connectivity != 26)) return 0;
-  return gts::kHead + gts::kRow * gts::mesh_rows(X, Y, Z, connectivity);
+  return gts::kHead + gts::kRow * gts::lesion_rows(X, Y, Z, connectivity);
 }
 
 extern "C" int64_t gts_mesh_adjacency_workspace(int64_t n_vertices) {
@@ -661,16 +633,17 @@ extern "C" int32_t gts_mesh_classify(const int32_t* roots, int64_t X, int64_t Y,
   if (!mesh_cells(X, Y, Z, &voxels, &cells) || !grid_ok(grid_blocks) || workspace_bytes < mesh_bytes(voxels, cells))
     return GTS_ERR_SHAPE;
   if (connectivity != 6 && connectivity != 26) return GTS_ERR_ARGKIND;
-  const int64_t cap = mesh_rows(X, Y, Z, connectivity);
+  const int64_t cap = lesion_rows(X, Y, Z, connectivity);
   if (table_i64s < kHead + kRow * cap) return GTS_ERR_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const MeshBuffers b = mesh_buffers(workspace, voxels, cells);
   const Cells g = {static_cast<int>(X), static_cast<int>(Y), static_cast<int>(Z), static_cast<int>(Y + 1),
                    static_cast<int>(Z + 1), cells, voxels};
   if (hipMemsetAsync(table, 0, 8 * kHead, st) != hipSuccess) return launch_status();
-  mesh_slots_kernel<<<grid_for(voxels, grid_blocks), kBlock, 0, st>>>(roots, b.slot, table, voxels, cap);
-  mesh_classify_kernel<<<grid_for(cells, grid_blocks), kBlock, 0, st>>>(roots, b.slot, table, b.cmask, b.chunk_v,
-                                                                         b.chunk_t, g, cap);
+  lesion_rows_kernel<kHead, kRow><<<grid_for(voxels, kBlock, grid_blocks), kBlock, 0, st>>>(roots, b.slot, table,
+                                                                                            voxels, cap);
+  mesh_classify_kernel<<<grid_for(cells, kBlock, grid_blocks), kBlock, 0, st>>>(roots, b.slot, table, b.cmask,
+                                                                                 b.chunk_v, b.chunk_t, g, cap);
   const ScanJobs jobs = {{b.chunk_v, b.chunk_t}, {table + hVertices, table + hTriangles}};
   mesh_scan_chunks_kernel<<<2, kBlock, 0, st>>>(jobs, chunks_of(cells));
   return launch_status();
@@ -691,7 +664,7 @@ extern "C" int32_t gts_mesh_emit(const int32_t* roots, int64_t X, int64_t Y, int
   const MeshBuffers b = mesh_buffers(workspace, voxels, cells);
   const Cells g = {static_cast<int>(X), static_cast<int>(Y), static_cast<int>(Z), static_cast<int>(Y + 1),
                    static_cast<int>(Z + 1), cells, voxels};
-  const int grid = grid_for(cells, grid_blocks);
+  const int grid = grid_for(cells, kBlock, grid_blocks);
   mesh_vertices_kernel<<<grid, kBlock, 0, st>>>(b.cmask, b.chunk_v, b.vbase, vertices, n_vertices, g);
   mesh_faces_kernel<<<grid, kBlock, 0, st>>>(roots, b.slot, b.cmask, b.chunk_t, b.vbase, faces, face_slot, n_vertices,
                                              n_faces, g);
@@ -704,7 +677,7 @@ extern "C" int32_t gts_mesh_relabel(int32_t* face_slot, int64_t n_faces, const i
   if ((n_faces > 0 && !face_slot) || (n_rank > 0 && !rank)) return GTS_ERR_NULL;
   if (!grid_ok(grid_blocks) || !counts_ok(n_rank, n_faces)) return GTS_ERR_SHAPE;
   if (n_faces == 0) return GTS_OK;
-  mesh_relabel_kernel<<<grid_for(n_faces, grid_blocks), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
+  mesh_relabel_kernel<<<grid_for(n_faces, kBlock, grid_blocks), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
       face_slot, n_faces, rank, n_rank);
   return launch_status();
 }
@@ -723,7 +696,7 @@ extern "C" int32_t gts_mesh_adjacency(const int32_t* faces, int64_t n_faces, int
   int64_t* total = reinterpret_cast<int64_t*>(ws + round256(4 * n_vertices) + round256(8 * chunks_of(n_vertices)));
   if (hipMemsetAsync(row_start, 0, 4 * (n_vertices + 1), st) != hipSuccess) return launch_status();
   if (n_vertices == 0 || n_faces == 0) return launch_status();
-  const int grid_e = grid_for(3 * n_faces, grid_blocks), grid_v = grid_for(n_vertices, grid_blocks);
+  const int grid_e = grid_for(3 * n_faces, kBlock, grid_blocks), grid_v = grid_for(n_vertices, kBlock, grid_blocks);
   int* degree = cursor;  // the degrees are counted where the cursors will stand; the starts are written from them
   if (hipMemsetAsync(degree, 0, 4 * n_vertices, st) != hipSuccess) return launch_status();
   mesh_degree_kernel<<<grid_e, kBlock, 0, st>>>(faces, n_faces, n_vertices, degree);
@@ -741,12 +714,11 @@ extern "C" int32_t gts_mesh_positions(const int32_t* vertices, int64_t n_vertice
   using namespace gts;
   if (!units || (n_vertices > 0 && (!vertices || !positions))) return GTS_ERR_NULL;
   if (!grid_ok(grid_blocks) || !counts_ok(n_vertices, 0)) return GTS_ERR_SHAPE;
-  for (int a = 0; a < 3; ++a)
-    if (units[a] < 1 || units[a] > kMaxUnit) return GTS_ERR_ARGKIND;
-  if (!(scale_mm > 0.0) || !(scale_mm <= 1.0e6)) return GTS_ERR_ARGKIND;
+  if (!units_ok(units) || !(scale_mm > 0.0) || !(scale_mm <= 1.0e6)) return GTS_ERR_ARGKIND;
   if (n_vertices == 0) return GTS_OK;
-  mesh_positions_kernel<<<grid_for(3 * n_vertices, grid_blocks), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
-      vertices, n_vertices, units[0], units[1], units[2], scale_mm, positions);
+  mesh_positions_kernel<<<grid_for(3 * n_vertices, kBlock, grid_blocks), kBlock, 0,
+                          static_cast<hipStream_t>(stream)>>>(vertices, n_vertices, units[0], units[1], units[2],
+                                                              scale_mm, positions);
   return launch_status();
 }
 
@@ -760,7 +732,7 @@ extern "C" int32_t gts_mesh_smooth(const int32_t* row_start, const int32_t* neig
   if (!(lambda == lambda) || !(mu == mu) || lambda - lambda != 0.0 || mu - mu != 0.0) return GTS_ERR_ARGKIND;
   if (n_vertices == 0) return GTS_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int grid = grid_for(n_vertices, grid_blocks);
+  const int grid = grid_for(n_vertices, kBlock, grid_blocks);
   for (int64_t it = 0; it < iterations; ++it) {
     mesh_smooth_kernel<<<grid, kBlock, 0, st>>>(row_start, neighbours, n_vertices, 3 * n_faces, positions, scratch,
                                                 lambda);
@@ -775,7 +747,7 @@ extern "C" int32_t gts_mesh_terms(const double* positions, const int32_t* faces,
   if (n_faces > 0 && (!positions || !faces || !area || !volume)) return GTS_ERR_NULL;
   if (!grid_ok(grid_blocks) || !counts_ok(n_vertices, n_faces)) return GTS_ERR_SHAPE;
   if (n_faces == 0) return GTS_OK;
-  mesh_terms_kernel<<<grid_for(n_faces, grid_blocks), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
+  mesh_terms_kernel<<<grid_for(n_faces, kBlock, grid_blocks), kBlock, 0, static_cast<hipStream_t>(stream)>>>(
       positions, faces, n_vertices, n_faces, area, volume);
   return launch_status();
 }

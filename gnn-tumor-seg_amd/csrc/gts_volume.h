@@ -24,6 +24,17 @@ inline bool volume_voxels(int64_t X, int64_t Y, int64_t Z, bool allow_empty, int
   return true;
 }
 
+// The kernels that work in millimetres (H3w-H5w, M1-M4, T1-T5) take the voxel spacing as integer units, each in
+// [1, kMmMaxUnit] (100 mm in steps of 1e-4 mm), on extents up to kMmMaxExtent (H2's uint16 distances):
+// u_a (N_a - 1) then fits an int32.  (gts_select.h's kMaxExtent and gts_scan.h's kScanMaxExtent have other reasons.)
+constexpr int64_t kMmMaxExtent = 4097;
+constexpr int64_t kMmMaxUnit = 1000000;
+inline bool units_ok(const int64_t* units) {
+  for (int a = 0; a < 3; ++a)
+    if (units[a] < 1 || units[a] > kMmMaxUnit) return false;
+  return true;
+}
+
 // workgroups for `items` at `per_block` each, at most `cap` (the kernel strides over the rest)
 inline int blocks_for(int64_t items, int64_t per_block, int64_t cap = INT32_MAX) {
   const int64_t b = (items + per_block - 1) / per_block;

@@ -8,7 +8,7 @@ give on the host, voxel for voxel, and run on the current stream.
 """
 import torch
 
-from . import _lib, _volume
+from . import _lesions, _lib, _volume   # _lesions imports this module in turn; both use the other at call time only
 from ._lib import check, current_stream, ptr, require_device
 
 
@@ -18,8 +18,7 @@ def lift_shape(shape):
 
 
 def _prepare(labels, connectivity, what):
-    if connectivity not in (6, 26):
-        raise _lib.GtsError(f"{what}: connectivity {connectivity!r} (6 or 26)")
+    _lesions.connectivity_arg(connectivity, what)
     labels = _volume.label_volume(labels, what)
     return labels, lift_shape(labels.shape)
 

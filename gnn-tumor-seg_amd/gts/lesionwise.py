@@ -18,21 +18,12 @@ import numpy as np
 import torch
 
 from . import _lib, _volume, components, metrics
+from ._lesions import REGIONS, region_index, region_mask, table_head
 from ._lib import check, current_stream, ptr
 
-REGIONS = ("WT", "CT", "ET")
 DILATIONS = (0, 1, 2, 3)
 PENALTY_HD95 = 374.0         # HD95 of a missed lesion and of a false-positive component
 ROW_INTS = 9                 # root | count | tp | box (gts_lesionwise_tables_i16)
-FIRST_COPY_INTS = 1 << 14    # the tables of a real prediction fit here; a longer block takes a second copy
-
-
-def _region_index(region):
-    if region in REGIONS:
-        return REGIONS.index(region)
-    if isinstance(region, int) and not isinstance(region, bool) and 0 <= region < 3:
-        return region
-    raise _lib.GtsError(f"lesionwise: region {region!r} (one of {REGIONS} or 0..2)")
 
 
 def _dilation(dilation, what):
@@ -41,23 +32,15 @@ def _dilation(dilation, what):
     return int(dilation)
 
 
-def _dilate(lib, labels, region, dilation, workspace, size):
-    x, y, z = labels.shape
-    out = torch.empty_like(labels)
-    check(lib.gts_lesionwise_dilate_i16(ptr(labels), x, y, z, region, dilation, ptr(out), ptr(workspace), size,
-                                        current_stream()), "gts_lesionwise_dilate_i16")
-    return out
-
-
 def dilate_region(labels, region, dilation=3):
     """int16 0 / 1 tensor of labels' shape: scipy's binary_dilation(region mask of labels,
     generate_binary_structure(3, 2), iterations=dilation), clipped at the volume.  labels: int16 CUDA tensor
     [X, Y, Z] of internal labels; region "WT", "CT" or "ET" (or 0..2); dilation 0..3."""
     labels = _volume.label_volume(labels, "dilate_region", three_d=True)
-    region, dilation = _region_index(region), _dilation(dilation, "dilate_region")
+    region, dilation = region_index(region, "dilate_region"), _dilation(dilation, "dilate_region")
     lib = _lib.load()
     workspace, size = _volume.workspace(lib.gts_lesionwise_workspace, *labels.shape, labels.device, "dilate_region")
-    return _dilate(lib, labels, region, dilation, workspace, size)
+    return region_mask(lib, labels, region, dilation, workspace, size)
 
 
 def _box(row, shape):
@@ -73,7 +56,7 @@ class _RegionState:
         self.lib, self.truth, self.region, self.shape = lib, truth, region, tuple(truth.shape)
         x, y, z = self.shape
         workspace, size = _volume.workspace(lib.gts_lesionwise_workspace, x, y, z, truth.device, what)
-        mask_p, mask_d = (_dilate(lib, v, region, n, workspace, size) for v, n in ((pred, 0), (truth, dilation)))
+        mask_p, mask_d = (region_mask(lib, v, region, n, workspace, size) for v, n in ((pred, 0), (truth, dilation)))
         self.roots_p = components.roots_unchecked(mask_p, self.shape, 26, what)
         self.roots_d = components.roots_unchecked(mask_d, self.shape, 26, what)
         ints = lib.gts_lesionwise_table_ints(x, y, z)
@@ -81,16 +64,13 @@ class _RegionState:
         check(lib.gts_lesionwise_tables_i16(ptr(truth), ptr(self.roots_p), ptr(self.roots_d), x, y, z, region,
                                             ptr(block), ints, ptr(workspace), size, current_stream()),
               "gts_lesionwise_tables_i16")
-        head = block[:min(ints, FIRST_COPY_INTS)].cpu().numpy()
+        head = table_head(block, lambda head: 4 + ROW_INTS * (int(head[0]) + int(head[1])) + 2 * int(head[2]))
         n_l, n_c, n_p = (int(v) for v in head[:3])
-        total = 4 + ROW_INTS * (n_l + n_c) + 2 * n_p
-        if total > head.size:
-            head = np.concatenate([head, block[head.size:total].cpu().numpy()])
         rows = head[4:4 + ROW_INTS * (n_l + n_c)].reshape(n_l + n_c, ROW_INTS).astype(np.int64)
         lesions, comps = rows[:n_l], rows[n_l:]
         self.lesions = lesions[np.argsort(lesions[:, 0])]          # scipy's label order: by smallest index
         self.comps = comps[np.argsort(comps[:, 0])]
-        pairs = head[4 + ROW_INTS * (n_l + n_c):total].reshape(n_p, 2).astype(np.int64)
+        pairs = head[4 + ROW_INTS * (n_l + n_c):].reshape(n_p, 2).astype(np.int64)
         self.pairs = np.unique(pairs, axis=0) if n_p else pairs      # (component root, lesion root), sorted
         self.matched_dev = None
 
@@ -155,7 +135,7 @@ def lesion_tables(pred, truth, region, dilation=3):
     the dilated lesion, scipy's label order): lesion_roots, vol (|G_k|), tp (|P n G_k|), matched_voxels (|M_k|),
     matched_components (indices into comp_roots / comp_sizes, which are in component order), n_fp."""
     pred, truth = _volume.label_pair(pred, truth, "lesion_tables", three_d=True)
-    region, dilation = _region_index(region), _dilation(dilation, "lesion_tables")
+    region, dilation = region_index(region, "lesion_tables"), _dilation(dilation, "lesion_tables")
     return _RegionState(_lib.load(), pred, truth, region, dilation).tables()
 
 

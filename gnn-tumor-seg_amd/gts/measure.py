@@ -19,42 +19,20 @@ an exact int64:
 The float64 quantities are derived on the host, each by one fixed expression (`derive`).  Labels are internal: 0
 healthy, 1 edema, 2 NET, 3 ET.  Everything runs on the current stream.
 """
-import ctypes
 import math
 
 import numpy as np
 import torch
 
-from . import _lib, _volume, components, lesionwise, metrics
+from . import _lib, _volume
+from ._lesions import REGIONS, RegionLesions, grid_arg, table_head
 from ._lib import check, current_stream, ptr
 
-REGIONS = ("WT", "CT", "ET")
 HEAD_I64 = _lib.const("GTS_MEASURE_HEAD_I64")
 ROW_I64 = _lib.const("GTS_MEASURE_ROW_I64")
 PAIR_TILE = _lib.const("GTS_MEASURE_PAIR_TILE")
-FIRST_COPY_I64 = 1 << 13     # the table of a real prediction fits here; a longer one takes a second copy
 LIMITS = "every extent in [1, 4097], fewer than 2^31 voxels, 2 * sum_a u_a^2 (N_a - 1)^2 < 2^62"
 TABLE_KEYS = ("root", "n", "n_class", "box", "coord_sum", "faces", "d3", "plane_z", "plane_d2", "plane_w")
-
-
-def _region_index(region):
-    if region in REGIONS:
-        return REGIONS.index(region)
-    if isinstance(region, int) and not isinstance(region, bool) and 0 <= region < 3:
-        return region
-    raise _lib.GtsError(f"measure: region {region!r} (one of {REGIONS} or 0..2)")
-
-
-def _connectivity(connectivity):
-    if isinstance(connectivity, bool) or connectivity not in (6, 26):
-        raise _lib.GtsError(f"measure: connectivity {connectivity!r} (6 or 26)")
-    return int(connectivity)
-
-
-def _grid(grid_blocks):
-    if isinstance(grid_blocks, bool) or not isinstance(grid_blocks, int) or not 0 <= grid_blocks < 2 ** 31:
-        raise _lib.GtsError(f"measure: grid_blocks {grid_blocks!r} (0 for the library's choice, or 1 .. 2^31 - 1)")
-    return grid_blocks
 
 
 def _work_units(rows, z_extent):
@@ -86,50 +64,40 @@ def lesion_table(labels, region, spacing_mm=(1, 1, 1), connectivity=26, *, grid_
     every pass (0: the library's choice); no value depends on it.  mark: called with a stage's name once the stage
     is enqueued (tools/measure_lesion_shape.py records an event there)."""
     what = "lesion_table"
-    mark = mark or (lambda stage: None)
-    region, connectivity, grid_blocks = _region_index(region), _connectivity(connectivity), _grid(grid_blocks)
-    units, scale_mm = metrics.spacing_units(spacing_mm)
-    labels = _volume.label_volume(labels, what, three_d=True)
-    lib = _lib.load()
-    x, y, z = labels.shape
-    c_units = (ctypes.c_int64 * 3)(*units)
-    if lib.gts_measure_check(x, y, z, c_units) != 0:
-        raise _lib.GtsError(f"{what}: volume {x}x{y}x{z} at units {units} is outside the kernels' limits ({LIMITS})")
-    workspace, size = _volume.workspace(lib.gts_measure_workspace, x, y, z, labels.device, what, LIMITS)
-    scratch, scratch_size = _volume.workspace(lib.gts_lesionwise_workspace, x, y, z, labels.device, what)
-    mask = lesionwise._dilate(lib, labels, region, 0, scratch, scratch_size)
-    mark("region mask")
-    roots = components.roots_unchecked(mask, (x, y, z), connectivity, what)
-    mark("components")
-    ints = lib.gts_measure_table_i64s(x, y, z, connectivity)
+    grid_blocks = grid_arg(grid_blocks, what)
+    return _table(RegionLesions(labels, region, spacing_mm, connectivity, what, LIMITS, mark), grid_blocks)
+
+
+def _table(front, grid_blocks=0):
+    """lesion_table's own stages, M1-M4, on a front end."""
+    lib, labels, roots, c_units, (x, y, z) = front.lib, front.labels, front.roots, front.c_units, front.shape
+    workspace, size = _volume.workspace(lib.gts_measure_workspace, x, y, z, labels.device, "lesion_table", LIMITS)
+    ints = lib.gts_measure_table_i64s(x, y, z, front.connectivity)
     table = torch.empty(ints, dtype=torch.int64, device=labels.device)
     stream = current_stream()
-    check(lib.gts_measure_tables_i16(ptr(labels), ptr(roots), x, y, z, region, connectivity, ptr(table), ints,
-                                     ptr(workspace), size, grid_blocks, stream), "gts_measure_tables_i16")
-    mark("M1 tables")
+    check(lib.gts_measure_tables_i16(ptr(labels), ptr(roots), x, y, z, front.region, front.connectivity, ptr(table),
+                                     ints, ptr(workspace), size, grid_blocks, stream), "gts_measure_tables_i16")
+    front.mark("M1 tables")
     check(lib.gts_measure_candidates(ptr(roots), x, y, z, ptr(table), ints, ptr(workspace), size, grid_blocks, stream),
           "gts_measure_candidates")
-    mark("M2 candidates")
-    head = table[:min(ints, FIRST_COPY_I64)].cpu().numpy()
+    front.mark("M2 candidates")
+    head = table_head(table, lambda head: HEAD_I64 + ROW_I64 * int(head[0]))
     n_lesions, n_slices, plane_candidates = int(head[0]), int(head[1]), int(head[3])
-    total = HEAD_I64 + ROW_I64 * n_lesions
-    if total > head.size:
-        head = np.concatenate([head, table[head.size:total].cpu().numpy()])
-    rows = head[HEAD_I64:total].reshape(n_lesions, ROW_I64)
+    rows = head[HEAD_I64:].reshape(n_lesions, ROW_I64)
     if n_lesions:
         pairs, planes = _work_units(rows, rows[:, 9] + rows[:, 10] - z)
         work = torch.from_numpy(np.concatenate([pairs.ravel(), planes.ravel()])).to(labels.device)
         slices = torch.empty(2 * n_slices, dtype=torch.int64, device=labels.device)
-        mark("plan (copy, host, upload)")
+        front.mark("plan (copy, host, upload)")
         check(lib.gts_measure_diameters(x, y, z, c_units, ptr(work), len(pairs), ptr(table), ints, ptr(workspace),
                                         size, grid_blocks, stream), "gts_measure_diameters")
-        mark("M3 diameters")
+        front.mark("M3 diameters")
         check(lib.gts_measure_planes(x, y, z, c_units, work.data_ptr() + 4 * pairs.size, len(planes), ptr(slices),
                                      n_slices, ptr(table), ints, ptr(workspace), size, grid_blocks, stream),
               "gts_measure_planes")
-        mark("M4 planes")
-        rows = table[HEAD_I64:total].cpu().numpy().reshape(n_lesions, ROW_I64)
-        mark("results (copy)")
+        front.mark("M4 planes")
+        rows = table[HEAD_I64:head.size].cpu().numpy().reshape(n_lesions, ROW_I64)
+        front.mark("results (copy)")
     rows = rows[np.argsort(rows[:, 0])]
     extent = np.array([x, x, y, y, z, z], dtype=np.int64)
     box = rows[:, 5:11].copy()
@@ -138,8 +106,8 @@ def lesion_table(labels, region, spacing_mm=(1, 1, 1), connectivity=26, *, grid_
     return dict(root=rows[:, 0].copy(), n=rows[:, 1].copy(), n_class=rows[:, 2:5].copy(), box=box,
                 coord_sum=rows[:, 11:14].copy(), faces=rows[:, 14:17].copy(), d3=rows[:, 20].copy(),
                 plane_z=rows[:, 21].copy(), plane_d2=rows[:, 22].copy(), plane_w=rows[:, 23].copy(),
-                candidates=rows[:, 17].copy(), plane_candidates=plane_candidates, units=tuple(units),
-                scale_mm=scale_mm)
+                candidates=rows[:, 17].copy(), plane_candidates=plane_candidates, units=tuple(front.units),
+                scale_mm=front.scale_mm)
 
 
 def volume_ml(voxels, units, scale_mm):
@@ -209,12 +177,13 @@ def tumour_report(labels, spacing_mm=(1, 1, 1), connectivity=26, min_lesion_voxe
     after smooth_iterations Taubin iterations); meshes, a dict, then receives every region's gts.mesh.region_mesh."""
     report = {}
     for name in REGIONS:
-        table = lesion_table(labels, name, spacing_mm, connectivity)
+        front = RegionLesions(labels, name, spacing_mm, connectivity, "lesion_table", LIMITS)
+        table = _table(front)
         features = None
-        if mesh:
+        if mesh:       # the same roots under both tables: one region mask and one labelling per region
             from . import mesh as gts_mesh
 
-            surface = gts_mesh.region_mesh(labels, name, spacing_mm, connectivity, smooth_iterations=smooth_iterations)
+            surface = gts_mesh._mesh(front, gts_mesh.iterations_arg(smooth_iterations))
             if not np.array_equal(surface["root"], table["root"]):
                 raise _lib.GtsError(f"tumour_report: the mesh and the table of {name} list different lesions")
             features = gts_mesh.shape_features(surface)

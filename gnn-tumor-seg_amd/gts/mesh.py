@@ -18,26 +18,24 @@ Smoothing is Taubin's lambda | mu scheme on positions in millimetres along the g
 smoothed in millimetres; a gather in a fixed order, every bit the same on every run.  Everything runs on the current
 stream.
 """
-import ctypes
 import math
 
 import numpy as np
 import torch
 
-from . import _lib, _volume, components, lesionwise, metrics
+from . import _lib, _volume
+from ._lesions import REGIONS, RegionLesions, grid_arg, table_head
 from ._lib import check, current_stream, ptr
-from .measure import REGIONS, _connectivity, _grid, _region_index
 
 HEAD_I64 = _lib.const("GTS_MESH_HEAD_I64")
 ROW_I64 = _lib.const("GTS_MESH_ROW_I64")
-FIRST_COPY_I64 = 1 << 13
 TAUBIN_LAMBDA, TAUBIN_MU = 0.5, -0.53
 LIMITS = "every extent in [1, 4097], (X + 1)(Y + 1)(Z + 1) < 2^31, fewer than 2^31 vertices and 2^31 / 3 triangles"
 FEATURE_KEYS = ("mesh_triangles", "mesh_area_mm2", "mesh_volume_ml", "smooth_area_mm2", "smooth_volume_ml",
                 "sphericity", "surface_to_volume_per_mm")
 
 
-def _iterations(n):
+def iterations_arg(n):
     if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= 100000:
         raise _lib.GtsError(f"mesh: smooth_iterations {n!r} (0 .. 100000)")
     return n
@@ -61,38 +59,29 @@ def region_mesh(labels, region, spacing_mm=(1, 1, 1), connectivity=26, *, smooth
     comes to the host once, for the sizes of the arrays.  grid_blocks: workgroups of every pass (0: the library's
     choice); no value depends on it.  mark: called with a stage's name once the stage is enqueued."""
     what = "region_mesh"
-    mark = mark or (lambda stage: None)
-    region, connectivity, grid_blocks = _region_index(region), _connectivity(connectivity), _grid(grid_blocks)
-    smooth_iterations = _iterations(smooth_iterations)
-    units, scale_mm = metrics.spacing_units(spacing_mm)
-    labels = _volume.label_volume(labels, what, three_d=True)
-    lib = _lib.load()
-    x, y, z = labels.shape
-    c_units = (ctypes.c_int64 * 3)(*units)
-    if lib.gts_measure_check(x, y, z, c_units) != 0:
-        raise _lib.GtsError(f"{what}: volume {x}x{y}x{z} at units {units} is outside the kernels' limits ({LIMITS})")
-    dev = labels.device
+    grid_blocks, smooth_iterations = grid_arg(grid_blocks, what), iterations_arg(smooth_iterations)
+    front = RegionLesions(labels, region, spacing_mm, connectivity, what, LIMITS, mark)
+    return _mesh(front, smooth_iterations, grid_blocks)
+
+
+def _mesh(front, smooth_iterations, grid_blocks=0):
+    """region_mesh's own stages, T1-T5, on a front end."""
+    what = "region_mesh"
+    lib, roots, c_units, (x, y, z), mark = front.lib, front.roots, front.c_units, front.shape, front.mark
+    units, scale_mm, dev = front.units, front.scale_mm, roots.device
     workspace, size = _volume.workspace(lib.gts_mesh_workspace, x, y, z, dev, what, LIMITS)
-    scratch, scratch_size = _volume.workspace(lib.gts_lesionwise_workspace, x, y, z, dev, what)
-    mask = lesionwise._dilate(lib, labels, region, 0, scratch, scratch_size)
-    mark("region mask")
-    roots = components.roots_unchecked(mask, (x, y, z), connectivity, what)
-    mark("components")
-    ints = lib.gts_mesh_table_i64s(x, y, z, connectivity)
+    ints = lib.gts_mesh_table_i64s(x, y, z, front.connectivity)
     table = torch.empty(ints, dtype=torch.int64, device=dev)
     stream = current_stream()
-    check(lib.gts_mesh_classify(ptr(roots), x, y, z, connectivity, ptr(table), ints, ptr(workspace), size, grid_blocks,
-                                stream), "gts_mesh_classify")
+    check(lib.gts_mesh_classify(ptr(roots), x, y, z, front.connectivity, ptr(table), ints, ptr(workspace), size,
+                                grid_blocks, stream), "gts_mesh_classify")
     mark("T1-T2 classify, scans")
-    head = table[:min(ints, FIRST_COPY_I64)].cpu().numpy()
+    head = table_head(table, lambda head: HEAD_I64 + ROW_I64 * int(head[0]))
     n_lesions, n_vertices, n_faces = int(head[0]), int(head[1]), int(head[2])
     if n_vertices >= 2 ** 31 or 3 * n_faces >= 2 ** 31:
         raise _lib.GtsError(f"{what}: {n_vertices} vertices and {n_faces} triangles are outside the kernels' limits "
                             f"({LIMITS})")
-    total = HEAD_I64 + ROW_I64 * n_lesions
-    if total > head.size:
-        head = np.concatenate([head, table[head.size:total].cpu().numpy()])
-    rows = head[HEAD_I64:total].reshape(n_lesions, ROW_I64)
+    rows = head[HEAD_I64:].reshape(n_lesions, ROW_I64)
     order = np.argsort(rows[:, 0])
     rank = np.empty(n_lesions, dtype=np.int32)
     rank[order] = np.arange(n_lesions, dtype=np.int32)

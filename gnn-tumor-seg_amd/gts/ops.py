@@ -8,6 +8,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lesions import connectivity_arg
 from ._lib import check, current_stream, ptr, require_device
 from ._operands import StreamBuffers, expect, f32, scratch
 from ._volume import SCAN_CODES, float32_out, label_volume, scan_volume, workspace
@@ -1399,11 +1400,10 @@ def largest_component(mask, connectivity=6, grid_blocks=0):
     the winner's root, voxels of the mask): the component of mask != 0 with the most voxels, a tie going to the smaller root.  An empty
     mask gives an empty keep and zeros; gts.brainmask.largest_component raises for it."""
     mask, ws, size = _brain_mask(mask, "largest_component")
-    if connectivity not in (6, 26):
-        raise _lib.GtsError(f"largest_component: connectivity {connectivity!r} (6 or 26)")
+    connectivity = connectivity_arg(connectivity, "largest_component")
     keep = torch.empty_like(mask)
     stats = torch.empty(5, dtype=torch.int64, device=mask.device)
-    check(_lib.load().gts_largest_component_i16(ptr(mask), *mask.shape, int(connectivity), ptr(keep), ptr(stats), ptr(ws),
+    check(_lib.load().gts_largest_component_i16(ptr(mask), *mask.shape, connectivity, ptr(keep), ptr(stats), ptr(ws),
                                                 size, int(grid_blocks), current_stream()), "gts_largest_component_i16")
     return keep, stats
 

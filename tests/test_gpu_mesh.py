@@ -222,6 +222,37 @@ def test_symmetries_of_the_kuhn_triangulation(hip_lib):
     assert int(ref.region_mesh(np.ascontiguousarray(vol[::-1]), "WT")["v6"].sum()) != v6
 
 
+@pytest.mark.parametrize("connectivity", [26, 6])
+@pytest.mark.parametrize("name", ["lattice", "random-13x17x9-0.31", "zeros-4x4x4", "six-faces"])
+def test_tumour_report_through_one_front_end(hip_lib, monkeypatch, name, connectivity):
+    """tumour_report(mesh=True) labels each region once and hands the roots to both tables: three component passes a
+    scan, and every number and array what lesion_table and region_mesh give when called one by one."""
+    from gts import components, measure, mesh
+
+    dev = _dev(np.zeros((4, 4, 4), dtype=np.int16) if name == "zeros-4x4x4" else ref.volumes()[name])
+    spacing = (0.9375, 0.9375, 5)
+    want, surfaces = {}, {}
+    for region in measure_ref.REGIONS:
+        surfaces[region] = mesh.region_mesh(dev, region, spacing, connectivity, smooth_iterations=3)
+        want[region] = measure.report_from_table(measure.lesion_table(dev, region, spacing, connectivity), 1,
+                                                 mesh.shape_features(surfaces[region]))
+    calls, labelling = [], components.roots_unchecked
+
+    def counting(*args, **kwargs):
+        calls.append(args[2])
+        return labelling(*args, **kwargs)
+
+    monkeypatch.setattr(components, "roots_unchecked", counting)
+    meshes = {}
+    got = measure.tumour_report(dev, spacing, connectivity, mesh=True, smooth_iterations=3, meshes=meshes)
+    assert calls == [connectivity] * 3, calls
+    assert got == want                                   # Python's ==: every float bit for bit (no NaN among them)
+    assert sorted(meshes) == sorted(measure_ref.REGIONS)
+    for region in measure_ref.REGIONS:
+        for key in ("faces", "face_lesion", "vertices_mm"):
+            assert np.array_equal(meshes[region][key].cpu().numpy(), surfaces[region][key].cpu().numpy()), (region, key)
+
+
 def test_cli_with_and_without_mesh(hip_lib, tmp_path):
     from data_processing import labels as label_maps
     from data_processing import nifti_io
