@@ -154,27 +154,38 @@ def lesion_measurements(labels, region, spacing_mm=(1, 1, 1), connectivity=26, *
     return [derive(table, k) for k in range(len(table["root"]))]
 
 
-def report_from_table(table, min_lesion_voxels=1, features=None):
+def report_from_table(table, min_lesion_voxels=1, features=None, texture=None):
     """One region's part of tumour_report from its lesion_table.  features: gts.mesh.shape_features of the same
-    region in lesion order; each listed lesion then carries its keys too."""
+    region in lesion order; each listed lesion then carries its keys too.  texture: {name: {root: the features of
+    gts.texture.derive}} over the listed lesions; each then carries `texture`, {name: features}."""
     u, s = table["units"], table["scale_mm"]
     voxels = int(table["n"].sum())
     classes = [int(v) for v in table["n_class"].sum(axis=0)] if len(table["n"]) else [0, 0, 0]
     order = sorted(range(len(table["n"])), key=lambda k: (-int(table["n"][k]), int(table["root"][k])))
     return dict(voxels=voxels, ml=volume_ml(voxels, u, s), class_ml=[volume_ml(c, u, s) for c in classes],
                 n_lesions=len(order),
-                lesions=[dict(derive(table, k), **(features[k] if features is not None else {}))
+                lesions=[dict(derive(table, k), **(features[k] if features is not None else {}),
+                              **({"texture": {name: by_root[int(table["root"][k])] for name, by_root in texture.items()}}
+                                 if texture is not None else {}))
                          for k in order if int(table["n"][k]) >= min_lesion_voxels])
 
 
 def tumour_report(labels, spacing_mm=(1, 1, 1), connectivity=26, min_lesion_voxels=1, *, mesh=False,
-                  smooth_iterations=20, meshes=None):
+                  smooth_iterations=20, meshes=None, texture=None, texture_bins=32, texture_bin_width=None):
     """{"WT" | "CT" | "ET": record}: voxels and ml of the region, class_ml (the region's voxels of label 1, 2, 3 in
     ml), n_lesions, and `lesions`, the dicts of `derive` sorted by descending n, then root.  A lesion of fewer than
     min_lesion_voxels voxels is counted in the totals and in n_lesions but not listed.
 
     mesh=True: each listed lesion also carries gts.mesh.shape_features' keys (the triangle surface of DESIGN.md 4z
-    after smooth_iterations Taubin iterations); meshes, a dict, then receives every region's gts.mesh.region_mesh."""
+    after smooth_iterations Taubin iterations); meshes, a dict, then receives every region's gts.mesh.region_mesh.
+
+    texture={name: image}: int16 or float32 tensors of labels' shape, one per modality; each listed lesion also carries
+    texture[name], gts.texture.derive's features of that lesion on that image without `root` and `n`,
+    at texture_bins levels or, when given, at a bin width of texture_bin_width."""
+    if texture is not None:
+        from . import texture as gts_texture
+
+        binning = gts_texture.binning_args(texture_bins, texture_bin_width, "tumour_report")
     report = {}
     for name in REGIONS:
         front = RegionLesions(labels, name, spacing_mm, connectivity, "lesion_table", LIMITS)
@@ -189,5 +200,12 @@ def tumour_report(labels, spacing_mm=(1, 1, 1), connectivity=26, min_lesion_voxe
             features = gts_mesh.shape_features(surface)
             if meshes is not None:
                 meshes[name] = surface
-        report[name] = report_from_table(table, min_lesion_voxels, features)
+        by_image = None
+        if texture is not None:    # the same roots again: the lesions of a region are labelled once
+            by_image = {}
+            for key, image in texture.items():
+                tex = gts_texture._texture(front, image, *binning, max(1, min_lesion_voxels))
+                rows = [gts_texture.derive(tex, k) for k in range(len(tex["root"]))]
+                by_image[key] = {row.pop("root"): row for row in rows if row.pop("n")}
+        report[name] = report_from_table(table, min_lesion_voxels, features, by_image)
     return report

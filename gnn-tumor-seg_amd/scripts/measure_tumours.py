@@ -17,8 +17,17 @@ existing ones (raw mesh area and volume, the same after --mesh_smooth Taubin ite
 volume), and with --mesh_dir DIR a binary PLY per (scan, region), DIR/{id}_{region}.ply, in the world coordinates of
 the file's own affine.  Without --mesh the CSV and the JSON are what they were.
 
+--texture SCAN_DIR adds what the tissue inside each lesion looks like on the scans (gts.texture): per
+modality of --texture_modalities the columns tex_{modality}_{feature} over TEXTURE_FEATURES (first-order and GLCM
+features at --texture_bins grey levels, or at a bin width of --texture_bin_width), after the mesh columns.  The scan
+of {id}.nii.gz is the folder {id} under SCAN_DIR, each modality the first file directly in it that ends with the
+extension; a scan with a modality that is missing, of another shape than the prediction or on another grid (affines
+more than gts.conform.AFFINE_AGREEMENT apart) is reported and left out.  Without --texture the CSV and the JSON are
+what they were.
+
     python -m scripts.measure_tumours -s PRED_DIR -o report.csv --json report.json --min_lesion_voxels 10
     python -m scripts.measure_tumours -s PRED_DIR -o report.csv --mesh --mesh_dir meshes
+    python -m scripts.measure_tumours -s PRED_DIR -o report.csv --texture SCAN_DIR --texture_bins 32
 """
 import argparse
 import json
@@ -43,6 +52,25 @@ HEADER = ["id", "region", "lesion", "n_lesions", "root", "voxels", "volume_ml", 
           "face_area_mm2", "diameter_mm", "plane_z", "plane_major_mm", "plane_minor_mm", "plane_product_mm2"]
 MESH_HEADER = ["mesh_triangles", "mesh_area_mm2", "mesh_volume_ml", "smooth_area_mm2", "smooth_volume_ml", "sphericity",
                "surface_to_volume_per_mm"]       # gts.mesh.FEATURE_KEYS, appended by --mesh
+TEXTURE_MODALITIES = ["_flair.nii.gz", "_t1.nii.gz", "_t1ce.nii.gz", "_t2.nii.gz"]
+TEXTURE_FEATURES = ["min", "max", "range", "levels", "mean_level", "variance", "skewness", "kurtosis", "median_level",
+                    "p10_level", "p90_level", "mode_level", "entropy", "uniformity", "mean_intensity_approx",
+                    "joint_maximum", "joint_average", "joint_variance", "joint_entropy", "difference_average",
+                    "difference_variance", "difference_entropy", "sum_average", "sum_variance", "sum_entropy",
+                    "angular_second_moment", "contrast", "dissimilarity", "inverse_difference",
+                    "inverse_difference_moment", "correlation", "autocorrelation", "cluster_tendency", "cluster_shade",
+                    "cluster_prominence", "information_correlation_1",
+                    "information_correlation_2"]    # gts.texture.FEATURE_KEYS, per modality of --texture
+
+
+def modality_name(extension):
+    """The name of a modality in the columns and the JSON: its extension without the leading '_' and the file type."""
+    name = extension[:-len(SUFFIX)] if extension.endswith(SUFFIX) else extension.split(".")[0]
+    return name.lstrip("_") or extension
+
+
+def texture_header(modalities):
+    return [f"tex_{modality_name(ext)}_{key}" for ext in modalities for key in TEXTURE_FEATURES]
 
 
 def build_parser():
@@ -62,6 +90,16 @@ def build_parser():
                         help="Taubin iterations before the smooth area, volume and sphericity (0: the raw mesh)")
     parser.add_argument("--mesh_dir", default=None, metavar="DIR",
                         help="with --mesh: write DIR/{id}_{region}.ply in each file's world coordinates")
+    parser.add_argument("--texture", default=None, metavar="SCAN_DIR",
+                        help="also report intensity and texture features of every lesion on the scans under SCAN_DIR "
+                             "(the folder {id} of a prediction {id}.nii.gz)")
+    parser.add_argument("--texture_modalities", nargs="+", default=list(TEXTURE_MODALITIES), metavar="EXT",
+                        help="with --texture: file suffixes of the modalities to report")
+    binning = parser.add_mutually_exclusive_group()
+    binning.add_argument("--texture_bins", type=int, default=None, metavar="N",
+                         help="with --texture: grey levels per lesion, a fixed bin number (default 32)")
+    binning.add_argument("--texture_bin_width", type=float, default=None, metavar="W",
+                         help="with --texture: a fixed bin width in the scan's units instead of a bin number")
     return parser
 
 
@@ -78,38 +116,71 @@ def load_prediction(path):
     return np.ascontiguousarray(labels), spacing_of(path)
 
 
+def load_texture(path, shape, scan_dir, modalities):
+    """Host stage of --texture: {modality name: the scan's volume as stored (int16 or float32), C-contiguous} of the
+    prediction at `path`, every modality of the prediction's `shape` and on its grid."""
+    from gts.conform import AFFINE_AGREEMENT
+
+    scan_id = os.path.basename(path)[:-len(SUFFIX)]
+    folder = os.path.join(scan_dir, scan_id)
+    if not os.path.isdir(folder):
+        raise FileNotFoundError(f"no scan folder {folder}")
+    affine, _ = nifti_io.read_affine(path)
+    images = {}
+    for ext in modalities:
+        found = sorted(f for f in os.listdir(folder) if f.endswith(ext))
+        if not found:
+            raise FileNotFoundError(f"{folder}: no file ending with {ext!r}")
+        file = os.path.join(folder, found[0])
+        volume = nifti_io.read_nifti_raw(file)
+        if volume.shape != shape:
+            raise ValueError(f"{found[0]} {volume.shape} and the prediction {shape} differ in shape")
+        gap = float(np.max(np.abs(nifti_io.read_affine(file)[0] - affine)))
+        if not gap <= AFFINE_AGREEMENT:
+            raise ValueError(f"the affines of {found[0]} and the prediction disagree by {gap:g} "
+                             f"(limit {AFFINE_AGREEMENT:g})")
+        images[modality_name(ext)] = np.ascontiguousarray(volume)
+    return images
+
+
 def _cell(value):
-    return repr(value) if isinstance(value, float) else str(value)
+    return "" if value is None else repr(value) if isinstance(value, float) else str(value)
 
 
-def rows_of(scan_id, report, regions=REGIONS, mesh=False):
+def rows_of(scan_id, report, regions=REGIONS, mesh=False, texture=()):
     """The CSV rows (lists of strings, HEADER's order) of one scan's tumour_report: per region its lesions in the
     report's order, numbered from 1, then the `total` row.  mesh: MESH_HEADER's columns after them (empty in the
-    `total` row), from a report made with mesh=True."""
+    `total` row), from a report made with mesh=True.  texture: the modality names of a report made with texture=;
+    TEXTURE_FEATURES' columns per modality after those (empty in the `total` row, and where a feature is None)."""
     rows = []
+    extra = (len(MESH_HEADER) if mesh else 0) + len(texture) * len(TEXTURE_FEATURES)
     for region in regions:
         record = report[region]
         for rank, m in enumerate(record["lesions"], 1):
             rows.append([scan_id, region, rank, "", m["root"], m["n"], m["volume_ml"]] + m["class_ml"] +
                         m["centroid_mm"] + m["extent_mm"] +
                         [m["face_area_mm2"], m["diameter_mm"], m["plane_z"], m["plane_major_mm"], m["plane_minor_mm"],
-                         m["plane_product_mm2"]] + ([m[key] for key in MESH_HEADER] if mesh else []))
+                         m["plane_product_mm2"]] + ([m[key] for key in MESH_HEADER] if mesh else []) +
+                        [m["texture"][name][key] for name in texture for key in TEXTURE_FEATURES])
         rows.append([scan_id, region, "total", record["n_lesions"], "", record["voxels"], record["ml"]] +
-                    record["class_ml"] + [""] * (12 + (len(MESH_HEADER) if mesh else 0)))
+                    record["class_ml"] + [""] * (12 + extra))
     return [[_cell(v) for v in row] for row in rows]
 
 
-def write_csv(path, rows, mesh=False):
+def write_csv(path, rows, mesh=False, texture=()):
+    """texture: the extensions of --texture_modalities."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
-        f.write(",".join(HEADER + (MESH_HEADER if mesh else [])) + "\n")
+        f.write(",".join(HEADER + (MESH_HEADER if mesh else []) + texture_header(texture)) + "\n")
         for row in rows:
             f.write(",".join(row) + "\n")
 
 
-def measure(paths, connectivity=26, min_lesion_voxels=1, mesh=False, mesh_smooth=20, mesh_dir=None, regions=REGIONS):
+def measure(paths, connectivity=26, min_lesion_voxels=1, mesh=False, mesh_smooth=20, mesh_dir=None, regions=REGIONS,
+            texture_dir=None, texture_modalities=(), texture_bins=32, texture_bin_width=None):
     """({id: {"spacing_mm", "regions": tumour_report}}, ids left out) of {id: path}.  mesh: the report carries the
-    shape features; mesh_dir: the PLY files of `regions` go there."""
+    shape features; mesh_dir: the PLY files of `regions` go there.  texture_dir: the report carries the texture
+    features of texture_modalities, the scans being decoded on the read-ahead pool beside the predictions."""
     import torch
 
     from gts import measure as gts_measure
@@ -119,27 +190,32 @@ def measure(paths, connectivity=26, min_lesion_voxels=1, mesh=False, mesh_smooth
 
         os.makedirs(mesh_dir, exist_ok=True)
 
+    def load(path):
+        labels, spacing = load_prediction(path)
+        return labels, spacing, (load_texture(path, labels.shape, texture_dir, texture_modalities)
+                                 if texture_dir is not None else None)
+
     ids = sorted(paths)
     reports, failed = {}, []
     with ThreadPoolExecutor(max_workers=IO_WORKERS) as pool:
-        pending = {i: pool.submit(load_prediction, paths[ids[i]]) for i in range(min(READ_AHEAD, len(ids)))}
+        pending = {i: pool.submit(load, paths[ids[i]]) for i in range(min(READ_AHEAD, len(ids)))}
         for i, scan_id in enumerate(ids):
             if i + READ_AHEAD < len(ids):
-                pending[i + READ_AHEAD] = pool.submit(load_prediction, paths[ids[i + READ_AHEAD]])
+                pending[i + READ_AHEAD] = pool.submit(load, paths[ids[i + READ_AHEAD]])
             try:
-                labels, spacing = pending.pop(i).result()
-                if not mesh:
-                    report = gts_measure.tumour_report(torch.from_numpy(labels).cuda(), spacing, connectivity,
-                                                       min_lesion_voxels)
-                else:
-                    meshes = {}
-                    report = gts_measure.tumour_report(torch.from_numpy(labels).cuda(), spacing, connectivity,
-                                                       min_lesion_voxels, mesh=True, smooth_iterations=mesh_smooth,
-                                                       meshes=meshes)
-                    if mesh_dir:
-                        affine, _ = nifti_io.read_affine(paths[scan_id])
-                        for region in regions:
-                            gts_mesh.write_ply(os.path.join(mesh_dir, f"{scan_id}_{region}.ply"), meshes[region], affine)
+                labels, spacing, images = pending.pop(i).result()
+                options, meshes = {}, {}
+                if mesh:
+                    options.update(mesh=True, smooth_iterations=mesh_smooth, meshes=meshes)
+                if images is not None:
+                    options.update(texture={name: torch.from_numpy(v).cuda() for name, v in images.items()},
+                                   texture_bins=texture_bins, texture_bin_width=texture_bin_width)
+                report = gts_measure.tumour_report(torch.from_numpy(labels).cuda(), spacing, connectivity,
+                                                   min_lesion_voxels, **options)
+                if mesh and mesh_dir:
+                    affine, _ = nifti_io.read_affine(paths[scan_id])
+                    for region in regions:
+                        gts_mesh.write_ply(os.path.join(mesh_dir, f"{scan_id}_{region}.ply"), meshes[region], affine)
                 reports[scan_id] = dict(spacing_mm=list(spacing), regions=report)
             except Exception as exc:
                 print(f"{scan_id}: left out ({exc!r})")
@@ -153,11 +229,19 @@ def main(argv=None):
     print(f"{len(paths)} predictions found; the report goes to {args.output}")
     if args.mesh_dir and not args.mesh:
         raise SystemExit("--mesh_dir needs --mesh")
+    if not args.texture and (args.texture_bins is not None or args.texture_bin_width is not None):
+        raise SystemExit("--texture_bins and --texture_bin_width need --texture")
+    modalities = tuple(args.texture_modalities) if args.texture else ()
+    names = [modality_name(ext) for ext in modalities]
+    if len(set(names)) != len(names):
+        raise SystemExit(f"--texture_modalities: {names} are not distinct names")
     reports, failed = measure(paths, args.connectivity, args.min_lesion_voxels, args.mesh, args.mesh_smooth,
-                              os.path.expanduser(args.mesh_dir) if args.mesh_dir else None, args.regions)
+                              os.path.expanduser(args.mesh_dir) if args.mesh_dir else None, args.regions,
+                              os.path.expanduser(args.texture) if args.texture else None, modalities,
+                              32 if args.texture_bins is None else args.texture_bins, args.texture_bin_width)
     rows = [row for scan_id in sorted(reports)
-            for row in rows_of(scan_id, reports[scan_id]["regions"], args.regions, args.mesh)]
-    write_csv(os.path.expanduser(args.output), rows, args.mesh)
+            for row in rows_of(scan_id, reports[scan_id]["regions"], args.regions, args.mesh, names)]
+    write_csv(os.path.expanduser(args.output), rows, args.mesh, modalities)
     if args.json:
         path = os.path.expanduser(args.json)
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)

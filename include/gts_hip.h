@@ -1311,6 +1311,66 @@ int32_t gts_mesh_smooth(const int32_t* row_start, const int32_t* neighbours, int
 int32_t gts_mesh_terms(const double* positions, const int32_t* faces, int64_t n_vertices, int64_t n_faces,
                        double* area, double* volume, int64_t grid_blocks, void* stream);
 
+/* ---- X1-X3: per-lesion intensity range, grey levels, histogram and GLCM (no counterpart in the
+ * reference) --------------------------------------------------------------------------------------------------------
+ * roots int32 [X][Y][Z] (Z contiguous) from gts_components_roots_i16 at `connectivity` 6 or 26; image [X][Y][Z] of
+ * dtype 4 (int16) or 16 (float32).  A lesion is the set of voxels of one root.  Definitions, the direction order and
+ * the level expressions: csrc/gts_texture.hip.  Every result is an integer (or a value of the image) that depends
+ * neither on grid_blocks (0: the library's choice, else 1 .. 2^31 - 1) nor on any order of arrival.
+ * Refusals, nothing being launched, in this order: a NULL pointer GTS_ERR_NULL; an extent outside [1, 4097],
+ * X * Y * Z >= 2^31 or a count (rows, lesions, listed voxels, work units) outside its range GTS_ERR_SHAPE; a
+ * connectivity or dtype code GTS_ERR_ARGKIND; bins / bin_width GTS_ERR_ARGKIND (bin_width must be 0, for a fixed bin
+ * number with bins in [1, GTS_TEXTURE_MAX_LEVELS], or positive and finite, bins then being ignored); a bad grid_blocks
+ * GTS_ERR_SHAPE; a workspace below gts_texture_workspace(X, Y, Z) bytes or a table below its size GTS_ERR_SHAPE.
+ * gts_texture_workspace and gts_texture_count_i64s return 0 for a refused shape; gts_texture_table_words(lesions,
+ * max_levels) returns 0 for max_levels outside [1, GTS_TEXTURE_MAX_LEVELS] or when 4 x the words exceed
+ * GTS_TEXTURE_MAX_TABLE_BYTES: the table is lesions x (max_levels + 13 max_levels (max_levels + 1) / 2) int32.
+ * gts_texture_counts (X1): counts (device int64): a header of GTS_TEXTURE_HEAD_I64 entries { roots, 0 .. } and one row
+ *   of GTS_TEXTURE_COUNT_ROW_I64 entries { root, voxels } per root in arrival order; the workspace keeps every root's
+ *   row.  The host selects lesions from it and numbers them 0 .. lesions - 1.
+ * gts_texture_ranges (X1): select (device int32 [n_rows]): row -> selected lesion or -1; segments (device int32
+ *   [lesions + 1]): the exclusive sums of the selected lesions' voxels, segments[lesions] = n_listed.  ranges (device
+ *   int64): a header { non-finite voxels of the selected lesions, 0 .. } and one row of GTS_TEXTURE_RANGE_ROW_I64
+ *   entries { lo, hi (encoded: int16 v + 32768; float32 the bits of v + 0.0f, flipped entirely when negative, else
+ *   with the sign set), end of the lesion's segment, non-finite voxels } per lesion.  list (device int32 [n_listed])
+ *   receives every selected lesion's voxel indices in its segment, in arrival order.
+ * gts_texture_levels (X2): plan (device int64 [lesions][GTS_TEXTURE_PLAN_I64]): { lo, hi as float64 bits, levels in
+ *   [1, max_levels], root }.  levels (device uint8 [n_listed]) receives the grey level of every listed voxel, the
+ *   workspace's level volume the same by voxel; table is cleared and its first lesions x max_levels words receive the
+ *   histograms.
+ * gts_texture_glcm (X3): work (device int32 [n_work][3]): (lesion, direction 0 .. 12, chunk of GTS_TEXTURE_CHUNK listed
+ *   voxels); a unit outside the plan is skipped.  The folded matrices are added to table after the histograms:
+ *   [lesion][direction][j (j + 1) / 2 + i], i <= j, with a stride of max_levels (max_levels + 1) / 2, every unordered
+ *   neighbouring pair once.  n_work 0: nothing is launched. */
+#define GTS_TEXTURE_MAX_LEVELS 128
+#define GTS_TEXTURE_DIRECTIONS 13
+#define GTS_TEXTURE_CHUNK 2048
+#define GTS_TEXTURE_HEAD_I64 8
+#define GTS_TEXTURE_COUNT_ROW_I64 2
+#define GTS_TEXTURE_RANGE_ROW_I64 4
+#define GTS_TEXTURE_PLAN_I64 4
+#define GTS_TEXTURE_MAX_TABLE_BYTES 1073741824
+int64_t gts_texture_workspace(int64_t X, int64_t Y, int64_t Z);
+int64_t gts_texture_count_i64s(int64_t X, int64_t Y, int64_t Z, int32_t connectivity);
+int64_t gts_texture_table_words(int64_t lesions, int64_t max_levels);
+int32_t gts_texture_counts(const int32_t* roots, int64_t X, int64_t Y, int64_t Z, int32_t connectivity,
+                           int64_t* counts, int64_t counts_i64s, void* workspace, int64_t workspace_bytes,
+                           int64_t grid_blocks, void* stream);
+int32_t gts_texture_ranges(const int32_t* roots, const void* image, int32_t dtype, int64_t X, int64_t Y, int64_t Z,
+                           const int32_t* select, int64_t n_rows, const int32_t* segments, int64_t lesions,
+                           int64_t* ranges, int64_t ranges_i64s, int32_t* list, int64_t n_listed,
+                           const void* workspace, int64_t workspace_bytes, int64_t grid_blocks, void* stream);
+int32_t gts_texture_levels(const void* image, int32_t dtype, int64_t X, int64_t Y, int64_t Z, int32_t bins,
+                           double bin_width, const int32_t* segments, const int64_t* plan, int64_t lesions,
+                           const int32_t* list, int64_t n_listed, uint8_t* levels, int32_t* table, int64_t table_words,
+                           int64_t max_levels, void* workspace, int64_t workspace_bytes, int64_t grid_blocks,
+                           void* stream);
+int32_t gts_texture_glcm(const int32_t* roots, int64_t X, int64_t Y, int64_t Z, const int32_t* work, int64_t n_work,
+                         const int32_t* segments, const int64_t* plan, int64_t lesions, const int32_t* list,
+                         const uint8_t* levels, int64_t n_listed, int32_t* table, int64_t table_words,
+                         int64_t max_levels, const void* workspace, int64_t workspace_bytes, int64_t grid_blocks,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
