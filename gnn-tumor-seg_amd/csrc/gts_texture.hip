@@ -30,43 +30,22 @@
 //       are not zero with global atomics.
 //
 // Integer atomics (add, min, max), float64 level arithmetic that is one rounded operation per step, and plain vector
-// stores only: identical results on every run and at every grid_blocks.  Limits: those of gts_measure_check's shape
+// stores only: identical results on every run and at every grid_blocks.  What X4-X6 (gts_texture_matrices.hip, the
+// run, zone and neighbourhood tables) share with these passes is in gts_texture.h.  Limits: those of gts_measure_check's shape
 // (every extent in [1, 4097], X * Y * Z < 2^31).  A count is at most the lesion's voxels, so int32 holds it.
 #include <type_traits>
 
-#include "gts_lesions.h"
-#include "gts_scan.h"
+#include "gts_texture.h"
 
 namespace gts {
 namespace {
 
-constexpr int kHead = GTS_TEXTURE_HEAD_I64;
-constexpr int kCountRow = GTS_TEXTURE_COUNT_ROW_I64;
-constexpr int kRangeRow = GTS_TEXTURE_RANGE_ROW_I64;
-constexpr int kPlanRow = GTS_TEXTURE_PLAN_I64;
-constexpr int kMaxLevels = GTS_TEXTURE_MAX_LEVELS;
-constexpr int kChunk = GTS_TEXTURE_CHUNK;
-constexpr int kDirections = GTS_TEXTURE_DIRECTIONS;
 constexpr int kTriangle = kMaxLevels * (kMaxLevels + 1) / 2;
-typedef unsigned long long u64;
 
-static_assert(kChunk % kBlock == 0, "a chunk is a whole number of passes of the workgroup");
-static_assert(kMaxLevels <= 256, "a level is stored as uint8");
 static_assert(kTriangle * 4 <= 48 * 1024, "the folded tile leaves LDS for a second workgroup per CU");
 
 // range row fields; head word 0 counts the non-finite voxels of all selected lesions
 enum { rLo = 0, rHi = 1, rCursor = 2, rNonFinite = 3 };
-// plan row fields
-enum { pLo = 0, pHi = 1, pLevels = 2, pRoot = 3 };
-
-__constant__ int kOffsets[kDirections][3] = {{0, 0, 1},  {0, 1, -1}, {0, 1, 0},  {0, 1, 1}, {1, -1, -1},
-                                             {1, -1, 0}, {1, -1, 1}, {1, 0, -1}, {1, 0, 0}, {1, 0, 1},
-                                             {1, 1, -1}, {1, 1, 0},  {1, 1, 1}};
-
-struct Vol {
-  int X, Y, Z;
-  int64_t n;
-};
 
 __host__ __device__ constexpr int64_t triangle(int64_t levels) { return levels * (levels + 1) / 2; }
 
@@ -165,16 +144,6 @@ __global__ __launch_bounds__(kBlock) void texture_range_kernel(const int* __rest
 }
 
 // ------------------------------------------------------------------ X2: levels and histogram
-// the lesion of listed position k: the last l with segments[l] <= k
-__device__ __forceinline__ int lesion_of(const int* __restrict__ segments, int L, int64_t k) {
-  int lo = 0, hi = L - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (segments[mid] <= k) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 template <typename T>
 __global__ __launch_bounds__(kBlock) void texture_levels_kernel(const T* __restrict__ image, int bins, double width,
                                                                 const int* __restrict__ segments,
@@ -269,23 +238,6 @@ __global__ __launch_bounds__(kBlock) void texture_glcm_kernel(const int* __restr
 }
 
 // ------------------------------------------------------------------ host
-inline bool texture_voxels(int64_t X, int64_t Y, int64_t Z, int64_t* n) {
-  return volume_voxels(X, Y, Z, false, n) && X <= kMmMaxExtent && Y <= kMmMaxExtent && Z <= kMmMaxExtent;
-}
-
-// header | slot int32[n] | level volume uint8[n]
-inline int64_t texture_bytes(int64_t n) { return kHeaderBytes + round256(4 * n) + round256(n); }
-
-struct TextureBuffers {
-  int* slot;
-  uint8_t* level_volume;
-};
-
-inline TextureBuffers texture_buffers(void* workspace, int64_t n) {
-  char* ws = static_cast<char*>(workspace) + kHeaderBytes;
-  return {reinterpret_cast<int*>(ws), reinterpret_cast<uint8_t*>(ws + round256(4 * n))};
-}
-
 // int32 words of hist [L][G] and the folded glcm [L][13][G (G + 1) / 2]; 0 outside the limits or above the byte cap
 inline int64_t table_words(int64_t lesions, int64_t levels) {
   if (lesions < 0 || lesions > INT32_MAX || levels < 1 || levels > kMaxLevels) return 0;

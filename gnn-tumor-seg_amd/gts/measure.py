@@ -171,7 +171,8 @@ def report_from_table(table, min_lesion_voxels=1, features=None, texture=None):
 
 
 def tumour_report(labels, spacing_mm=(1, 1, 1), connectivity=26, min_lesion_voxels=1, *, mesh=False,
-                  smooth_iterations=20, meshes=None, texture=None, texture_bins=32, texture_bin_width=None):
+                  smooth_iterations=20, meshes=None, texture=None, texture_bins=32, texture_bin_width=None,
+                  texture_matrices=(), texture_dependence_alpha=0):
     """{"WT" | "CT" | "ET": record}: voxels and ml of the region, class_ml (the region's voxels of label 1, 2, 3 in
     ml), n_lesions, and `lesions`, the dicts of `derive` sorted by descending n, then root.  A lesion of fewer than
     min_lesion_voxels voxels is counted in the totals and in n_lesions but not listed.
@@ -181,11 +182,16 @@ def tumour_report(labels, spacing_mm=(1, 1, 1), connectivity=26, min_lesion_voxe
 
     texture={name: image}: int16 or float32 tensors of labels' shape, one per modality; each listed lesion also carries
     texture[name], gts.texture.derive's features of that lesion on that image without `root` and `n`,
-    at texture_bins levels or, when given, at a bin width of texture_bin_width."""
-    if texture is not None:
+    at texture_bins levels or, when given, at a bin width of texture_bin_width.  texture_matrices, a subset of
+    gts.texture.MATRICES, and texture_dependence_alpha go to the texture call as `matrices` and `dependence_alpha`:
+    texture[name] then also carries the features of those families.  They need `texture`."""
+    if texture is not None or texture_matrices:
         from . import texture as gts_texture
 
+        if texture is None:
+            raise _lib.GtsError("tumour_report: texture_matrices needs texture")
         binning = gts_texture.binning_args(texture_bins, texture_bin_width, "tumour_report")
+        families = gts_texture.matrices_arg(texture_matrices, texture_dependence_alpha, "tumour_report")
     report = {}
     for name in REGIONS:
         front = RegionLesions(labels, name, spacing_mm, connectivity, "lesion_table", LIMITS)
@@ -204,7 +210,7 @@ def tumour_report(labels, spacing_mm=(1, 1, 1), connectivity=26, min_lesion_voxe
         if texture is not None:    # the same roots again: the lesions of a region are labelled once
             by_image = {}
             for key, image in texture.items():
-                tex = gts_texture._texture(front, image, *binning, max(1, min_lesion_voxels))
+                tex = gts_texture._texture(front, image, *binning, max(1, min_lesion_voxels), 0, *families)
                 rows = [gts_texture.derive(tex, k) for k in range(len(tex["root"]))]
                 by_image[key] = {row.pop("root"): row for row in rows if row.pop("n")}
         report[name] = report_from_table(table, min_lesion_voxels, features, by_image)

@@ -25,9 +25,16 @@ extension; a scan with a modality that is missing, of another shape than the pre
 more than gts.conform.AFFINE_AGREEMENT apart) is reported and left out.  Without --texture the CSV and the JSON are
 what they were.
 
+--texture_matrices NAME [NAME ...] (with --texture; glrlm, glszm, gldm, ngtdm or all) adds the features of the
+run-length, size-zone, dependence and neighbourhood-difference families (gts.texture.GLRLM_KEYS and
+its siblings; --texture_dependence_alpha A is the GLDM's level tolerance, default 0): the columns
+tex_{modality}_{key} after all the columns above, by modality and then by family.  Without it the CSV and the JSON of
+--texture are what they were.
+
     python -m scripts.measure_tumours -s PRED_DIR -o report.csv --json report.json --min_lesion_voxels 10
     python -m scripts.measure_tumours -s PRED_DIR -o report.csv --mesh --mesh_dir meshes
     python -m scripts.measure_tumours -s PRED_DIR -o report.csv --texture SCAN_DIR --texture_bins 32
+    python -m scripts.measure_tumours -s PRED_DIR -o report.csv --texture SCAN_DIR --texture_matrices all
 """
 import argparse
 import json
@@ -69,8 +76,20 @@ def modality_name(extension):
     return name.lstrip("_") or extension
 
 
-def texture_header(modalities):
-    return [f"tex_{modality_name(ext)}_{key}" for ext in modalities for key in TEXTURE_FEATURES]
+TEXTURE_MATRICES = ["glrlm", "glszm", "gldm", "ngtdm"]       # gts.texture.MATRICES, --texture_matrices
+
+
+def matrix_features(matrices):
+    """The feature names of the families of --texture_matrices, in TEXTURE_MATRICES' order."""
+    from gts.texture import MATRIX_FEATURE_KEYS
+
+    return [key for family in TEXTURE_MATRICES if family in matrices for key in MATRIX_FEATURE_KEYS[family]]
+
+
+def texture_header(modalities, matrices=()):
+    more = matrix_features(matrices) if matrices else []
+    return [f"tex_{modality_name(ext)}_{key}" for ext in modalities for key in TEXTURE_FEATURES] + \
+        [f"tex_{modality_name(ext)}_{key}" for ext in modalities for key in more]
 
 
 def build_parser():
@@ -100,6 +119,12 @@ def build_parser():
                          help="with --texture: grey levels per lesion, a fixed bin number (default 32)")
     binning.add_argument("--texture_bin_width", type=float, default=None, metavar="W",
                          help="with --texture: a fixed bin width in the scan's units instead of a bin number")
+    parser.add_argument("--texture_matrices", nargs="+", default=None, metavar="NAME",
+                        choices=TEXTURE_MATRICES + ["all"],
+                        help="with --texture: also report the features of these families (glrlm, glszm, gldm, ngtdm, "
+                             "or all)")
+    parser.add_argument("--texture_dependence_alpha", type=int, default=None, metavar="A",
+                        help="with --texture_matrices: levels at most A apart count as dependent (GLDM; default 0)")
     return parser
 
 
@@ -147,13 +172,15 @@ def _cell(value):
     return "" if value is None else repr(value) if isinstance(value, float) else str(value)
 
 
-def rows_of(scan_id, report, regions=REGIONS, mesh=False, texture=()):
+def rows_of(scan_id, report, regions=REGIONS, mesh=False, texture=(), matrices=()):
     """The CSV rows (lists of strings, HEADER's order) of one scan's tumour_report: per region its lesions in the
     report's order, numbered from 1, then the `total` row.  mesh: MESH_HEADER's columns after them (empty in the
     `total` row), from a report made with mesh=True.  texture: the modality names of a report made with texture=;
-    TEXTURE_FEATURES' columns per modality after those (empty in the `total` row, and where a feature is None)."""
+    TEXTURE_FEATURES' columns per modality after those (empty in the `total` row, and where a feature is None).
+    matrices: the families of a report made with texture_matrices=; their columns per modality after all those."""
     rows = []
-    extra = (len(MESH_HEADER) if mesh else 0) + len(texture) * len(TEXTURE_FEATURES)
+    more = matrix_features(matrices) if matrices else []
+    extra = (len(MESH_HEADER) if mesh else 0) + len(texture) * (len(TEXTURE_FEATURES) + len(more))
     for region in regions:
         record = report[region]
         for rank, m in enumerate(record["lesions"], 1):
@@ -161,26 +188,29 @@ def rows_of(scan_id, report, regions=REGIONS, mesh=False, texture=()):
                         m["centroid_mm"] + m["extent_mm"] +
                         [m["face_area_mm2"], m["diameter_mm"], m["plane_z"], m["plane_major_mm"], m["plane_minor_mm"],
                          m["plane_product_mm2"]] + ([m[key] for key in MESH_HEADER] if mesh else []) +
-                        [m["texture"][name][key] for name in texture for key in TEXTURE_FEATURES])
+                        [m["texture"][name][key] for name in texture for key in TEXTURE_FEATURES] +
+                        [m["texture"][name][key] for name in texture for key in more])
         rows.append([scan_id, region, "total", record["n_lesions"], "", record["voxels"], record["ml"]] +
                     record["class_ml"] + [""] * (12 + extra))
     return [[_cell(v) for v in row] for row in rows]
 
 
-def write_csv(path, rows, mesh=False, texture=()):
-    """texture: the extensions of --texture_modalities."""
+def write_csv(path, rows, mesh=False, texture=(), matrices=()):
+    """texture: the extensions of --texture_modalities; matrices: the families of --texture_matrices."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
-        f.write(",".join(HEADER + (MESH_HEADER if mesh else []) + texture_header(texture)) + "\n")
+        f.write(",".join(HEADER + (MESH_HEADER if mesh else []) + texture_header(texture, matrices)) + "\n")
         for row in rows:
             f.write(",".join(row) + "\n")
 
 
 def measure(paths, connectivity=26, min_lesion_voxels=1, mesh=False, mesh_smooth=20, mesh_dir=None, regions=REGIONS,
-            texture_dir=None, texture_modalities=(), texture_bins=32, texture_bin_width=None):
+            texture_dir=None, texture_modalities=(), texture_bins=32, texture_bin_width=None, texture_matrices=(),
+            texture_dependence_alpha=0):
     """({id: {"spacing_mm", "regions": tumour_report}}, ids left out) of {id: path}.  mesh: the report carries the
     shape features; mesh_dir: the PLY files of `regions` go there.  texture_dir: the report carries the texture
-    features of texture_modalities, the scans being decoded on the read-ahead pool beside the predictions."""
+    features of texture_modalities, the scans being decoded on the read-ahead pool beside the predictions, and those
+    of the families of texture_matrices."""
     import torch
 
     from gts import measure as gts_measure
@@ -210,6 +240,9 @@ def measure(paths, connectivity=26, min_lesion_voxels=1, mesh=False, mesh_smooth
                 if images is not None:
                     options.update(texture={name: torch.from_numpy(v).cuda() for name, v in images.items()},
                                    texture_bins=texture_bins, texture_bin_width=texture_bin_width)
+                    if texture_matrices:
+                        options.update(texture_matrices=tuple(texture_matrices),
+                                       texture_dependence_alpha=texture_dependence_alpha)
                 report = gts_measure.tumour_report(torch.from_numpy(labels).cuda(), spacing, connectivity,
                                                    min_lesion_voxels, **options)
                 if mesh and mesh_dir:
@@ -231,6 +264,12 @@ def main(argv=None):
         raise SystemExit("--mesh_dir needs --mesh")
     if not args.texture and (args.texture_bins is not None or args.texture_bin_width is not None):
         raise SystemExit("--texture_bins and --texture_bin_width need --texture")
+    if not args.texture and (args.texture_matrices is not None or args.texture_dependence_alpha is not None):
+        raise SystemExit("--texture_matrices and --texture_dependence_alpha need --texture")
+    if args.texture_dependence_alpha is not None and args.texture_dependence_alpha < 0:
+        raise SystemExit("--texture_dependence_alpha: 0 or more")
+    chosen = args.texture_matrices or []
+    matrices = [m for m in TEXTURE_MATRICES if m in chosen or "all" in chosen]
     modalities = tuple(args.texture_modalities) if args.texture else ()
     names = [modality_name(ext) for ext in modalities]
     if len(set(names)) != len(names):
@@ -238,10 +277,11 @@ def main(argv=None):
     reports, failed = measure(paths, args.connectivity, args.min_lesion_voxels, args.mesh, args.mesh_smooth,
                               os.path.expanduser(args.mesh_dir) if args.mesh_dir else None, args.regions,
                               os.path.expanduser(args.texture) if args.texture else None, modalities,
-                              32 if args.texture_bins is None else args.texture_bins, args.texture_bin_width)
+                              32 if args.texture_bins is None else args.texture_bins, args.texture_bin_width,
+                              matrices, args.texture_dependence_alpha or 0)
     rows = [row for scan_id in sorted(reports)
-            for row in rows_of(scan_id, reports[scan_id]["regions"], args.regions, args.mesh, names)]
-    write_csv(os.path.expanduser(args.output), rows, args.mesh, modalities)
+            for row in rows_of(scan_id, reports[scan_id]["regions"], args.regions, args.mesh, names, matrices)]
+    write_csv(os.path.expanduser(args.output), rows, args.mesh, modalities, matrices)
     if args.json:
         path = os.path.expanduser(args.json)
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)

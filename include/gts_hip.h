@@ -1371,6 +1371,58 @@ int32_t gts_texture_glcm(const int32_t* roots, int64_t X, int64_t Y, int64_t Z, 
                          int64_t max_levels, const void* workspace, int64_t workspace_bytes, int64_t grid_blocks,
                          void* stream);
 
+/* ---- X4-X6: per-lesion run-length, size-zone, dependence and neighbourhood-difference tables (GLRLM, GLSZM, GLDM,
+ * NGTDM; no counterpart in the reference) ------------------------------------------------------------
+ * They run after gts_texture_levels on the same roots, segments, plan, list, levels and workspace (whose level volume
+ * they read).  Definitions: csrc/gts_texture_matrices.hip.  Every result is an integer that depends neither on
+ * grid_blocks nor on any order of arrival, the order of the zone records excepted (the host sorts them).
+ * Refusals, nothing being launched, in this order: a NULL pointer GTS_ERR_NULL; a shape outside X1-X3's limits, a
+ * count (lesions, listed voxels, work units: at least 1), max_levels outside [1, GTS_TEXTURE_MAX_LEVELS] or longest
+ * outside [1, GTS_TEXTURE_MAX_RUN] GTS_ERR_SHAPE; a negative alpha GTS_ERR_ARGKIND; a bad grid_blocks GTS_ERR_SHAPE; a
+ * workspace, scratch, record buffer or table below its size GTS_ERR_SHAPE.
+ * gts_texture_run_words(lesions, max_levels, longest): the int32 words of the run table, lesions x 13 x max_levels x
+ *   longest; 0 outside the limits or when 4 x the words exceed GTS_TEXTURE_MAX_TABLE_BYTES.
+ * gts_texture_neighbourhood_i64s(lesions, max_levels): the int64 entries of X6's table, 3 x lesions x max_levels x
+ *   GTS_TEXTURE_DEPENDENCES; 0 outside the limits or above the same byte cap.
+ * gts_texture_run_lengths (X4, first pass): work is X3's (lesion, direction, chunk).  run_length (device uint16
+ *   [13][n_listed]) receives per direction and listed voxel the length of the run that starts there, 0 where none
+ *   does; head (device int64 [GTS_TEXTURE_HEAD_I64]) is cleared and head[0] receives the longest run.
+ * gts_texture_runs (X4, second pass): table (device int32) is cleared and receives [lesion][direction][level]
+ *   [length - 1] with strides max_levels and longest, longest being at least head[0] of the first pass.
+ * gts_texture_zones (X5): scratch (device int32, 2 X Y Z words: parents and sizes by voxel).  records (device int32
+ *   [n_listed][GTS_TEXTURE_ZONE_RECORD_I32]) receives { lesion, level, voxels } per zone in arrival order; head is
+ *   cleared, head[0] receives the number of zones and head[1] the number of root searches that passed n_listed steps
+ *   (a forest that is not well formed): the records are then not to be used.
+ * gts_texture_neighbourhood (X6): work (device int32 [n_work][2]): (lesion, chunk).  table (device int64) is cleared
+ *   and receives gldm, ngtdm_n and ngtdm_s one after another, each [lesion][level][GTS_TEXTURE_DEPENDENCES] with a
+ *   stride of max_levels: column k - 1 of gldm is dependence k at `alpha`, column m of the others is a neighbourhood
+ *   of m voxels. */
+#define GTS_TEXTURE_NEIGHBOURS 26
+#define GTS_TEXTURE_DEPENDENCES 27
+#define GTS_TEXTURE_MAX_RUN 4097
+#define GTS_TEXTURE_ZONE_RECORD_I32 3
+int64_t gts_texture_run_words(int64_t lesions, int64_t max_levels, int64_t longest);
+int64_t gts_texture_neighbourhood_i64s(int64_t lesions, int64_t max_levels);
+int32_t gts_texture_run_lengths(const int32_t* roots, int64_t X, int64_t Y, int64_t Z, const int32_t* work,
+                                int64_t n_work, const int32_t* segments, const int64_t* plan, int64_t lesions,
+                                const int32_t* list, const uint8_t* levels, int64_t n_listed, uint16_t* run_length,
+                                int64_t run_length_words, int64_t* head, const void* workspace,
+                                int64_t workspace_bytes, int64_t grid_blocks, void* stream);
+int32_t gts_texture_runs(const int32_t* work, int64_t n_work, const int32_t* segments, const int64_t* plan,
+                         int64_t lesions, const uint8_t* levels, const uint16_t* run_length, int64_t n_listed,
+                         int32_t* table, int64_t table_words, int64_t max_levels, int64_t longest, int64_t grid_blocks,
+                         void* stream);
+int32_t gts_texture_zones(const int32_t* roots, int64_t X, int64_t Y, int64_t Z, const int32_t* segments,
+                          const int64_t* plan, int64_t lesions, const int32_t* list, const uint8_t* levels,
+                          int64_t n_listed, int32_t* scratch, int64_t scratch_words, int32_t* records,
+                          int64_t records_words, int64_t* head, const void* workspace, int64_t workspace_bytes,
+                          int64_t grid_blocks, void* stream);
+int32_t gts_texture_neighbourhood(const int32_t* roots, int64_t X, int64_t Y, int64_t Z, const int32_t* work,
+                                  int64_t n_work, const int32_t* segments, const int64_t* plan, int64_t lesions,
+                                  const int32_t* list, const uint8_t* levels, int64_t n_listed, int32_t alpha,
+                                  int64_t* table, int64_t table_i64s, int64_t max_levels, const void* workspace,
+                                  int64_t workspace_bytes, int64_t grid_blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
