@@ -505,6 +505,9 @@ inline int launch_cluster(ClusterArgs a, int max_rows, int loc_words, hipStream_
     if (wg_lds > kMaxLds || a.layout.words > 512) return GTS_ERR_SHAPE;
     a.ring = depth;
     if (a.max_srcs > 64 * waves) return GTS_ERR_SHAPE;
+    // fetch_record: wave p brings piece p of a record.  A workgroup of fewer waves than pieces (GTS_OPT_CLUSTER_CONSUMERS = 1,
+    // records of more than 256 words) would reduce from a piece nobody fetched: refused, as the GAT launch refuses it
+    if ((a.layout.words + 255) / 256 > waves) return GTS_ERR_SHAPE;
     if (!geo.deals) a.counters = nullptr;
     static const bool once = (allow_big_lds(spmm_cluster_stream_kernel<BWD, ARGB, WHATIF, 1, false>),
                               allow_big_lds(spmm_cluster_stream_kernel<BWD, ARGB, WHATIF, 1, true>),

@@ -116,7 +116,9 @@ int32_t gts_spmm_max_bwd_cluster_f32(const int32_t* rec, int64_t n_clusters, int
  * of each XCD to finish resets them), so one zeroed buffer per stream serves every launch on it.  On launches of 16 and more units per
  * workgroup (GTS_OPT_CLUSTER_DEALING) the persistent workgroups of an XCD take their units off one counter, which keeps the units in flight
  * neighbours in the walk whatever each workgroup's pace — their halo rows then meet in the XCD's L2 (profiles/r04/gat_l2_replay.log,
- * k12_dealing_ab.log).  NULL: static round-robin dealing (same values, more re-fetched rows at streaming sizes). */
+ * k12_dealing_ab.log).  NULL: static round-robin dealing (same values, more re-fetched rows at streaming sizes).
+ * GTS_ERR_SHAPE, before anything is launched: an LDS plan above 160 KiB, records above 512 words, max_srcs above 64 x the waves of a
+ * workgroup, or records of more 256-word pieces than a workgroup has waves (GTS_OPT_CLUSTER_CONSUMERS = 1 with records above 256 words). */
 #define GTS_CLUSTER_COUNTER_WORDS 256
 /* 1 when a launch over these records would deal its units off `counters` (so that a caller who carves them out of a scratch block knows whether
  * they need zeroing at all), 0 when it deals statically */
