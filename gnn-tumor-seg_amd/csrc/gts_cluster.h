@@ -1,6 +1,9 @@
 // Pieces the clustered kernels share (gts_spmm_cluster.hip: K1 / K2 at F = 256; gts_gat_cluster.hip: the GATConv
-// aggregation over the same schedule records): record layout, LDS-DMA gathers, counted waits, count-specialised loops.
+// aggregation over the same schedule records): record layout, LDS-DMA gathers, counted waits, count-specialised loops,
+// the per-XCD unit dealer and the persistent launch.
 #pragma once
+#include <algorithm>
+
 #include "gts_rows.h"
 
 namespace gts {
@@ -112,6 +115,91 @@ __device__ __forceinline__ void gather_halves(const Dma& dma, int part, unsigned
   }
 }
 
+// ---- units dealt per XCD ---------------------------------------------------------------------------------------
+// A persistent launch has gridDim.x = 8 * per_xcd workgroups; those with blockIdx % 8 == x (one XCD under round-robin placement:
+// speed only) share the x-th eighth of the clusters, [clo, clo + span), and walk its units in an order the kernel chooses so that
+// consecutive units are the same column slice of neighbouring clusters, whose halo rows meet in the XCD's L2.
+//
+// STATIC dealing: unit i of the walk goes to workgroup i % per_xcd.  A workgroup that falls ONE unit behind its neighbours is then
+// per_xcd units behind them in the walk — a whole generation — and the halo rows it shares with them have left the L2 before it
+// asks (1.57 x the table fetched where the walk in step fetches 1.20 x, profiles/r04/gat_l2_replay.log).
+// DYNAMIC dealing: the XCD's workgroups draw the walk's next index off ONE counter, so the units in flight are always the latest
+// per_xcd of the walk whatever each workgroup's pace.  Which workgroup computes a unit changes nothing in what it computes.
+//   * The counters: kCounterStride words per XCD (a line of its own each): word 0 = units drawn, word kCounterDone = workgroups
+//     finished.  Zero at launch; K1 / K2 leave them zero (their XCD's last workgroup resets them), the GAT passes zero them in the
+//     pass in front.
+//   * The dealer is the workgroup's LAST wave (it fetches no record piece).  It draws by an agent-scope atomic add (take) and hands
+//     the drawn index to the other waves through kDealBytes of LDS, `l_deal` (publish): eight slots, whose contents the kernel's
+//     `Fill` writes (K1 / K2: the raw index, which every wave decodes; GAT: the decoded (cluster, sub) pair).  An index past the walk's end
+//     yields "no unit"; units come in walk order, so nothing follows an empty slot.
+//   * A pipeline of PIPE units (fetching a record ... being reduced) is filled by ONE add of PIPE in the prologue: PIPE - 1 indices
+//     into slots 0 .. PIPE - 2 for the prologue, the last into slot 6 for iteration 0.  One round trip, then a barrier.
+//   * In the loop, iteration `it` reads slot 6 + (it & 1) behind its barrier.  The dealer issues the add for iteration it + 1 in
+//     iteration `it` (take_next) and publishes it at the TOP of iteration it + 1 (publish_next), behind the wait every wave makes
+//     there anyway and in front of that iteration's barrier: it never waits for the counter's round trip on its own, and the slot
+//     it writes was last read two barriers ago.
+constexpr int kCounterStride = 32;                           // words from one XCD's counters to the next
+constexpr int kCounterDone = 16;                             // the XCD's count of finished workgroups, words behind its unit counter
+constexpr int64_t kCounterBytes = 8 * kCounterStride * 4;
+static_assert(kCounterBytes == 4 * GTS_CLUSTER_COUNTER_WORDS, "include/gts_hip.h promises callers this size");
+static_assert(kCounterBytes == 4 * kBlock, "the GAT weight passes zero the counters with one workgroup, a word per thread");
+constexpr int kDealBytes = 64;                               // l_deal, at the end of a workgroup's LDS
+constexpr int kDealLoopSlot = 6;
+
+struct XcdShare {
+  int xcd, j, per_xcd;   // this workgroup is the XCD's j-th of per_xcd
+};
+__device__ __forceinline__ XcdShare xcd_share() { return XcdShare{static_cast<int>(blockIdx.x & 7), static_cast<int>(blockIdx.x >> 3), static_cast<int>(gridDim.x >> 3)}; }
+struct XcdSpan {
+  int clo, span;         // the XCD's clusters: [clo, clo + span)
+};
+__device__ __forceinline__ XcdSpan xcd_span(int n_clusters, int xcd) {
+  XcdSpan s;
+  s.clo = static_cast<int>(static_cast<long long>(n_clusters) * xcd / 8);
+  s.span = static_cast<int>(static_cast<long long>(n_clusters) * (xcd + 1) / 8) - s.clo;
+  return s;
+}
+
+__device__ __forceinline__ int deal_loop_slot(int it) { return kDealLoopSlot + (it & 1); }   // the slot iteration `it` reads
+
+// PIPE: units in the kernel's pipeline.  fill(first, count, slot0): the kernel's way to write the walk's indices first .. first +
+// count - 1 (held by lane 0) into l_deal's slots slot0 ..; called by every lane of the dealing wave.
+template <int PIPE, typename Fill>
+struct UnitDealer {
+  unsigned* const& counters;   // the kernel argument itself, re-read where used (a copy held in registers cost the GAT kernels two)
+  int xcd;
+  int wave, n_waves;           // of this workgroup: its last wave deals
+  Fill fill;
+  unsigned taken;              // the add of the iteration before, not yet published (lane 0)
+
+  __device__ __forceinline__ bool dealing() const { return wave == n_waves - 1; }
+  __device__ __forceinline__ unsigned* counter() const { return counters + kCounterStride * xcd; }   // this XCD's unit counter
+  __device__ __forceinline__ unsigned take(int count) const {
+    unsigned base = 0;
+    if ((threadIdx.x & (kWave - 1)) == 0)
+      base = __hip_atomic_fetch_add(counter(), static_cast<unsigned>(count), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return base;
+  }
+  __device__ __forceinline__ void prologue() {
+    if (dealing()) {
+      const unsigned first = take(PIPE);
+      fill(first, PIPE - 1, 0);
+      fill(first + (PIPE - 1), 1, kDealLoopSlot);
+    }
+    barrier_all();
+  }
+  __device__ __forceinline__ void publish_next(int it) const {   // top of iteration `it`, in front of its barrier
+    if (it > 0 && dealing()) fill(taken, 1, deal_loop_slot(it));
+  }
+  __device__ __forceinline__ void take_next() {                  // inside iteration `it`: the unit iteration it + 1 enters
+    if (dealing()) taken = take(1);
+  }
+};
+template <int PIPE, typename Fill>
+__device__ __forceinline__ UnitDealer<PIPE, Fill> unit_dealer(unsigned* const& counters, int xcd, int wave, int n_waves, Fill fill) {
+  return UnitDealer<PIPE, Fill>{counters, xcd, wave, n_waves, fill, 0u};
+}
+
 constexpr int64_t kMaxLds = 160 * 1024;
 
 inline int device_cus() {
@@ -124,9 +212,24 @@ inline int device_cus() {
   return cus;
 }
 
+// workgroups of a persistent launch: per_cu on every CU, no more than there are units, a multiple of 8 (one share per XCD), at least 8
+inline int64_t persistent_grid(int per_cu, int64_t units) {
+  const int64_t grid = static_cast<int64_t>(device_cus()) * per_cu;
+  return std::max<int64_t>(8, std::min(grid, (units + 7) / 8 * 8)) / 8 * 8;
+}
+
 template <typename Kernel>
 inline void allow_big_lds(Kernel k) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kMaxLds));
+}
+
+// one persistent streaming kernel on `grid` workgroups of `waves` waves; its LDS attribute is set once per kernel, not per launch
+template <auto Kernel, typename Args>
+inline int launch_persistent(const Args& a, int64_t grid, int waves, int64_t wg_lds, hipStream_t st) {
+  static const bool once = (allow_big_lds(Kernel), true);
+  (void)once;
+  Kernel<<<dim3(static_cast<unsigned>(grid)), waves * kWave, wg_lds, st>>>(a);
+  return launch_status();
 }
 
 }  // namespace

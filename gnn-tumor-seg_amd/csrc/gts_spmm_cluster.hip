@@ -47,9 +47,8 @@ struct ClusterArgs {
   unsigned table_bytes, winners_bytes;
   int relu_input, nt;
   int ring, slot_bytes, image_off, win_off;   // LDS: ring slots of slot_bytes = [record | image | winner image]
-  int deal_off;            // LDS: 64 bytes of dealt units behind the images
-  unsigned* counters;      // dynamic dealing: per XCD a unit counter (word 32 x) and a count of finished workgroups (word 32 x + 16),
-                           // zero on entry and on exit (null: static round-robin dealing)
+  int deal_off;            // LDS: kDealBytes of dealt units behind the images
+  unsigned* counters;      // dynamic dealing: the XCDs' counters (gts_cluster.h), zero on entry and on exit (null: static round-robin dealing)
 };
 
 // ---- reduce the rows of one unit out of its LDS slot ------------------------------------------------------
@@ -58,7 +57,7 @@ struct ClusterArgs {
 // operations per column — straight-line code for the exact count the longer of the wave's two rows needs (CNT is
 // wave-uniform).  The pads of a row's last chunk repeat its last edge: a repeated value never beats the maximum
 // it already is (strict '<'), so the shorter row needs no mask in K1; K2 masks by the degree.
-template <int ARGB, int WHATIF = 0>   // WHATIF (tools/diag only): 3 = no stores, 4 = stores without the reduction
+template <int ARGB>
 __device__ __forceinline__ int reduce_max_rows(const ClusterArgs& a, const int32_t* l_rec, const unsigned char* image,
                                                int part, int first, int step) {
   const int lane = threadIdx.x & (kWave - 1), half = lane >> 5, hl = lane & 31;
@@ -77,7 +76,7 @@ __device__ __forceinline__ int reduce_max_rows(const ClusterArgs& a, const int32
     int slot[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) best[t] = -INFINITY, slot[t] = -1;
-    for (int c = 0; 8 * c < deg_w && WHATIF != 4; ++c) {
+    for (int c = 0; 8 * c < deg_w; ++c) {
       const bool mine_too = 8 * c < deg;                     // the shorter row of the pair may have run out of chunks
       const uint2 w = loc[mine_too ? c0 + c : c0];
       for_count(min(8, deg_w - 8 * c), [&](auto cnt_c) {
@@ -122,9 +121,7 @@ __device__ __forceinline__ int reduce_max_rows(const ClusterArgs& a, const int32
       o.v[t] = dead ? 0.0f : best[t];
       slot[t] = (dead || (a.relu_input && !(best[t] > 0.0f))) ? -1 : slot[t];
     }
-    if (WHATIF == 3) {
-      if (o.v[0] == 123.456f) a.out[0] = static_cast<float>(slot[0] + slot[1] + slot[2] + slot[3]) + o.v[1] + o.v[2] + o.v[3];
-    } else if (have) {
+    if (have) {
       const size_t off = static_cast<size_t>(l_rec[a.layout.rows + j]) * kF + part * (kF / 2) + hl * 4;
       if (a.nt & 1) o.store_nt(a.out + off); else o.store(a.out + off);
       if constexpr (ARGB == 1) {
@@ -244,9 +241,8 @@ __device__ __forceinline__ void gather_winner_halves(const Dma& dma, int part, u
 // ---- the persistent streaming kernel --------------------------------------------------------------------------
 // gridDim.x is a multiple of 8: the workgroups with blockIdx % 8 == x (one XCD under round-robin placement; speed
 // only) share the x-th eighth of the units and take them round-robin.  LDS: three record slots, two images.
-// WHATIF != 0 only in the timing experiments of tools/diag (wrong results): 1 = no row gathers, 2 = no reduction and
-// no stores, 3 = no stores, 4 = stores without the reduction (K1).
-template <bool BWD, int ARGB, int WHATIF = 0, int DEPTH = 1, bool DEAL = false>   // DEAL: units dealt off the XCD's counter (a.counters)
+// (The timing experiments that switch parts of this work off keep a frozen copy of the kernel under tools/diag.)
+template <bool BWD, int ARGB, int DEPTH, bool DEAL>   // DEAL: units dealt off the XCD's counter (a.counters)
 // Two workgroups per CU: 16 waves each for K1 (<= 64 registers), 12 for K2 (its 68 registers: 6 waves per SIMD).  With 8 waves
 // the reduction of a unit is latency-bound (lattice, 8 graphs: 67.6 / 72.2 us against 63.9 / 67.8; k-NN graphs of mean
 // degree 7 - 10: 78 - 144 us against 65 - 96, profiles/r03_cluster_other_graphs.log).
@@ -255,18 +251,17 @@ __global__ __launch_bounds__(1024, BWD ? 6 : 8) void spmm_cluster_stream_kernel(
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   const int n_waves = blockDim.x / kWave;
-  const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
+  const XcdShare x = xcd_share();
+  const int xcd = x.xcd, j = x.j, per_xcd = x.per_xcd;
   const long long n_units = 2LL * a.n_clusters;
   const int lo = static_cast<int>(n_units * xcd / 8), hi = static_cast<int>(n_units * (xcd + 1) / 8);
-  // Dealing (as in gat_cluster_stream_kernel, see there).  STATIC (a.counters == nullptr): unit lo + j + t * per_xcd is this workgroup's
-  // t-th.  DYNAMIC (the default): the XCD's workgroups take their units off one counter, in the order "every cluster of the XCD's span for
-  // the left half, then for the right half" — the units in flight stay neighbours in that walk whatever each workgroup's pace, and their
-  // halo rows meet in the XCD's L2 (a workgroup one unit behind under static dealing is per_xcd units behind in the walk).
+  // Dealing (gts_cluster.h).  STATIC: unit lo + j + t * per_xcd is this workgroup's t-th.  DYNAMIC: the walk is "every cluster of the XCD's
+  // span for the left half, then for the right half".
   constexpr bool dynamic = DEAL;           // a compile-time choice: as a run-time one it cost both forms spilled registers
   const int n_static = lo + j < hi ? (hi - lo - j + per_xcd - 1) / per_xcd : 0;   // units lo + j + t * per_xcd, t < n_static
   if (!dynamic && n_static == 0) return;
-  const int clo = static_cast<int>(static_cast<long long>(a.n_clusters) * xcd / 8);
-  const int span = static_cast<int>(static_cast<long long>(a.n_clusters) * (xcd + 1) / 8) - clo;
+  const XcdSpan xs = xcd_span(a.n_clusters, xcd);
+  const int clo = xs.clo, span = xs.span;
   const int words = a.layout.words;
   const int pieces = (words + 255) / 256;   // a record arrives as one or two whole 1 KiB LDS-DMA pieces (lanes past its end deliver zeros)
   const int rec_bytes = 1024 * pieces, image_bytes = a.slot_bytes - a.image_off;
@@ -284,8 +279,19 @@ __global__ __launch_bounds__(1024, BWD ? 6 : 8) void spmm_cluster_stream_kernel(
   int u_unit[dynamic ? PIPE : 1];
 #pragma unroll
   for (int q = 0; q < (dynamic ? PIPE : 1); ++q) u_unit[q] = -1;
-  int32_t* l_deal = reinterpret_cast<int32_t*>(lds + a.deal_off);   // 0 .. PIPE - 2: the prologue's units, 6 / 7: the loop's
-  // l_deal holds the counter's values as taken; every wave turns one into its unit (2 * cluster + half; < 0: the span is exhausted)
+  int32_t* l_deal = reinterpret_cast<int32_t*>(lds + a.deal_off);
+  // a slot of l_deal holds the walk's index as drawn; every wave turns it into its unit (2 * cluster + half; < 0: the span is exhausted)
+  auto dealer = [&] {   // (the static form builds none: its code stays what it was without one)
+    if constexpr (dynamic) {
+      return unit_dealer<PIPE>(a.counters, xcd, wave, n_waves, [&](unsigned drawn, int count, int slot0) {
+        if (lane == 0) {
+          for (int q = 0; q < count; ++q) l_deal[slot0 + q] = static_cast<int>(drawn + q);
+        }
+      });
+    } else {
+      return 0;
+    }
+  }();
   auto next_unit = [&](int deal_slot) {
     if constexpr (dynamic) {
 #pragma unroll
@@ -302,19 +308,6 @@ __global__ __launch_bounds__(1024, BWD ? 6 : 8) void spmm_cluster_stream_kernel(
     } else {
       const int t = newest - k;
       return t < n_static ? lo + j + t * per_xcd : -1;
-    }
-  };
-  // the dealer (the workgroup's last wave): `count` units off the XCD's counter (take) into l_deal[slot0 ..] (publish).  In the loop
-  // the add is issued in one iteration and published at the top of the next, behind the wait every wave makes there anyway: the dealer
-  // never waits for the counter's round trip on its own.
-  auto take = [&](int count) {
-    unsigned base = 0;
-    if (lane == 0) base = __hip_atomic_fetch_add(a.counters + 32 * xcd, static_cast<unsigned>(count), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return base;
-  };
-  auto publish = [&](unsigned taken, int count, int slot0) {
-    if (lane == 0) {
-      for (int q = 0; q < count; ++q) l_deal[slot0 + q] = static_cast<int>(taken + q);
     }
   };
   auto fetch_record = [&](int t, int unit) {   // record of unit t -> its slot, by LDS-DMA (waves 0 / 1: one piece each)
@@ -359,15 +352,7 @@ __global__ __launch_bounds__(1024, BWD ? 6 : 8) void spmm_cluster_stream_kernel(
   // fetched in iteration it - 1 must have landed; vector-memory operations retire in order, so everything YOUNGER than that
   // record fetch may stay in flight: the previous iteration's stores and, for depth >= 2, its gathers (for depth 1 those ARE
   // the gathers of unit `it`).
-  if constexpr (dynamic) {
-    if (wave == n_waves - 1) {
-      const unsigned first = take(PIPE);      // ONE round trip for the prologue's units and the one iteration 0 enters
-      publish(first, PIPE - 1, 0);
-      publish(first + (PIPE - 1), 1, 6);
-    }
-    barrier_all();
-  }
-  unsigned taken = 0;                         // the dealer's add of the iteration before
+  if constexpr (dynamic) dealer.prologue();
 #pragma unroll
   for (int t = 0; t <= depth; ++t) {        // afterwards stage depth - t holds unit t
     next_unit(t);
@@ -376,72 +361,43 @@ __global__ __launch_bounds__(1024, BWD ? 6 : 8) void spmm_cluster_stream_kernel(
   barrier_all();
   int pending_gathers = 0, stores = 0;
 #pragma unroll
-  for (int t = 0; t < depth; ++t) pending_gathers = (WHATIF != 1 && unit_at(depth - t, depth) >= 0) ? issue_gathers(t, unit_at(depth - t, depth)) : 0;
+  for (int t = 0; t < depth; ++t) pending_gathers = unit_at(depth - t, depth) >= 0 ? issue_gathers(t, unit_at(depth - t, depth)) : 0;
   if (depth == 1) pending_gathers = 0;
-  // WHATIF == 9 (tools/diag only): shader-clock stamps of wave 0 around the phases of an iteration, summed per workgroup into
-  // `arg` (which then is a buffer of 8 x uint64 per workgroup, not the winners): wait for gathers | barrier | issue | reduce
-  unsigned long long phase[4] = {0, 0, 0, 0}, stamp = 0;
-  auto lap = [&](int which) {
-    if constexpr (WHATIF == 9) {
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      phase[which] += now - stamp;
-      stamp = now;
-    }
-  };
-  if constexpr (WHATIF == 9) stamp = __builtin_amdgcn_s_memtime();
   int it = 0;
   for (; dynamic || it < n_static; ++it) {
     wait_vm_all_but(pending_gathers + stores);
-    if constexpr (dynamic) {
-      if (it > 0 && wave == n_waves - 1) publish(taken, 1, 6 + (it & 1));   // this slot was last read two barriers ago
-    }
-    lap(0);
+    if constexpr (dynamic) dealer.publish_next(it);
     barrier_lds();                          // ... and everyone else's; the oldest image and the oldest record slot are free
-    lap(1);
-    next_unit(6 + (it & 1));                // stage 0 = unit it + depth + 1, stage 1 = unit it + depth, stage PIPE - 1 = unit it
+    next_unit(deal_loop_slot(it));            // stage 0 = unit it + depth + 1, stage 1 = unit it + depth, stage PIPE - 1 = unit it
     const int newest = it + depth + 1;
     const int unit_now = unit_at(PIPE - 1, newest);
     if constexpr (dynamic) {
       if (unit_now < 0) break;              // units come in walk order: nothing behind an empty slot
     }
-    if constexpr (dynamic) {
-      if (wave == n_waves - 1) taken = take(1);   // published at the top of the next iteration
-    }
+    if constexpr (dynamic) dealer.take_next();
     if constexpr (DEPTH == 1) {             // the next unit's gathers first, then the record of the unit after it
-      if (unit_at(1, newest) >= 0 && WHATIF != 1) issue_gathers(it + 1, unit_at(1, newest));
+      if (unit_at(1, newest) >= 0) issue_gathers(it + 1, unit_at(1, newest));
       if (unit_at(0, newest) >= 0) fetch_record(it + 2, unit_at(0, newest));
     } else {
       if (unit_at(0, newest) >= 0) fetch_record(it + depth + 1, unit_at(0, newest));
-      pending_gathers = (unit_at(1, newest) >= 0 && WHATIF != 1) ? issue_gathers(it + depth, unit_at(1, newest)) : 0;
+      pending_gathers = unit_at(1, newest) >= 0 ? issue_gathers(it + depth, unit_at(1, newest)) : 0;
     }
-    lap(2);
     const int32_t* l_rec = reinterpret_cast<const int32_t*>(lds + (it % n_recs) * rec_bytes);
     const unsigned char* image = images + (it % n_images) * image_bytes;
     const int part = unit_now & 1;
-    if constexpr (WHATIF == 2)
-      stores = 0;
-    else if constexpr (WHATIF >= 3 && WHATIF <= 4 && !BWD)
-      stores = WHATIF == 3 ? (reduce_max_rows<ARGB, WHATIF>(a, l_rec, image, part, wave, n_waves), 0)
-                           : reduce_max_rows<ARGB, WHATIF>(a, l_rec, image, part, wave, n_waves);
-    else if constexpr (BWD)
+    if constexpr (BWD)
       stores = reduce_winner_rows(a, l_rec, image, image + ((a.max_srcs + 1) & ~1) * kHalfBytes, part, wave, n_waves);
     else
       stores = reduce_max_rows<ARGB>(a, l_rec, image, part, wave, n_waves);
-    lap(3);
-  }
-  if constexpr (WHATIF == 9) {
-    if (threadIdx.x == 0) {
-      unsigned long long* dbg = reinterpret_cast<unsigned long long*>(a.arg) + 8 * static_cast<size_t>(blockIdx.x);
-      for (int q = 0; q < 4; ++q) dbg[q] = phase[q];
-      dbg[4] = static_cast<unsigned long long>(it);
-    }
   }
   // the last workgroup of the XCD to finish leaves the counters zero for the next launch
-  if (dynamic && threadIdx.x == 0) {   // (compile-time)
-    unsigned* done = a.counters + 32 * xcd + 16;
-    if (__hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == static_cast<unsigned>(per_xcd) - 1u) {
-      __hip_atomic_store(a.counters + 32 * xcd, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if constexpr (dynamic) {
+    if (threadIdx.x == 0) {
+      unsigned* done = dealer.counter() + kCounterDone;
+      if (__hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == static_cast<unsigned>(per_xcd) - 1u) {
+        __hip_atomic_store(dealer.counter(), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
     }
   }
 }
@@ -465,23 +421,24 @@ struct ClusterGeometry {
   int depth, waves;
   bool deals;      // units dealt off the XCD's counter (where the caller gives counters)
 };
-inline ClusterGeometry cluster_geometry(int64_t n_clusters, int words, int slot_bytes, int image_off, bool bwd, bool whatif) {
+inline ClusterGeometry cluster_geometry(int64_t n_clusters, int words, int slot_bytes, int image_off, bool bwd) {
   ClusterGeometry g;
   const int64_t units = 2LL * n_clusters;
   // depth + 2 record slots + depth + 1 images per workgroup; two workgroups per CU.  Gathers run one unit ahead; two units ahead
   // (GTS_OPT_CLUSTER_RING = 2, where that fits) is kept for A/B runs: no gain measured
   const int64_t rec_slot = 1024LL * ((words + 255) / 256), image = slot_bytes - image_off;
-  g.depth = (g_cluster_ring == 2 && !whatif && 4 * rec_slot + 3 * image + 64 <= kMaxLds) ? 2 : 1;
-  g.wg_lds = (g.depth + 2) * rec_slot + (g.depth + 1) * image + 64;   // + the dealt units
+  g.depth = (g_cluster_ring == 2 && 4 * rec_slot + 3 * image + kDealBytes <= kMaxLds) ? 2 : 1;
+  g.wg_lds = (g.depth + 2) * rec_slot + (g.depth + 1) * image + kDealBytes;
   g.waves = g_cluster_consumers > 0 ? std::min(16, g_cluster_consumers) : (bwd ? 12 : 16);
-  // persistent workgroups per CU: two; three (where the LDS holds them) for a backward launch that gives a workgroup only a
-  // few units — C2: 8.8 units per workgroup, the reference's batches: 5 — where the pipeline's fill and drain weigh most
+  // persistent workgroups per CU: two; a grid of three per CU for a backward launch that gives a workgroup only a few units — C2: 8.8
+  // units per workgroup, the reference's batches: 5.  Three 12-wave workgroups are NOT co-resident at K2's register count (6 waves per
+  // SIMD = two of them): the third is queued and starts where one of the two ends, so the 1.5 x grid deals the same units in finer
+  // shares and the CUs finish closer together
   // (profiles/r04/tune_k2_small.log, operands from HBM: 37.0 -> 35.2 us at 60 000 rows, 22.8 -> 22.0 at 35 000; nothing either way from
   // 120 000 rows on, and nothing in the training step, where the gradient rows were just written by the GEMM in front: 36.7 / 36.9 us)
   const int auto_per_cu = (bwd && units <= 24LL * device_cus()) ? 3 : 2;
   const int per_cu = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(g_cluster_per_cu > 0 ? g_cluster_per_cu : auto_per_cu, kMaxLds / std::max<int64_t>(1, g.wg_lds))));
-  g.grid = static_cast<int64_t>(device_cus()) * per_cu;
-  g.grid = std::max<int64_t>(8, std::min(g.grid, (units + 7) / 8 * 8)) / 8 * 8;
+  g.grid = persistent_grid(per_cu, units);
   // Units dealt off the XCD's counter (GTS_OPT_CLUSTER_DEALING: 0 = automatic, 1 = wherever counters are given, 2 = never) from 16 units per
   // workgroup on: the dealt form brings the fabric traffic to its compulsory figure (32 graphs per GPU: 1.31 / 1.18 -> 1.05 / 1.03 x) at the
   // static form's time or a little under (8 graphs: K1 69.7 -> 70.4 us, K2 67.9 -> 66.1), but its first units cost a counter round trip
@@ -491,41 +448,26 @@ inline ClusterGeometry cluster_geometry(int64_t n_clusters, int words, int slot_
   return g;
 }
 
-template <bool BWD, int ARGB, int WHATIF = 0>
+template <bool BWD, int ARGB>
 inline int launch_cluster(ClusterArgs a, int max_rows, int loc_words, hipStream_t st) {
   const LdsPlan p = lds_plan(max_rows, a.max_srcs, loc_words, BWD);
   a.image_off = p.image_off, a.win_off = p.win_off, a.slot_bytes = p.slot_bytes;
   if (p.slot_bytes > kMaxLds) return GTS_ERR_SHAPE;
-  const int64_t units = 2LL * a.n_clusters;
-  {
-    const ClusterGeometry geo = cluster_geometry(a.n_clusters, a.layout.words, p.slot_bytes, p.image_off, BWD, WHATIF != 0);
-    const int depth = geo.depth, waves = geo.waves;
-    const int64_t wg_lds = geo.wg_lds, grid = geo.grid;
-    a.deal_off = static_cast<int>(wg_lds) - 64;
-    if (wg_lds > kMaxLds || a.layout.words > 512) return GTS_ERR_SHAPE;
-    a.ring = depth;
-    if (a.max_srcs > 64 * waves) return GTS_ERR_SHAPE;
-    // fetch_record: wave p brings piece p of a record.  A workgroup of fewer waves than pieces (GTS_OPT_CLUSTER_CONSUMERS = 1,
-    // records of more than 256 words) would reduce from a piece nobody fetched: refused, as the GAT launch refuses it
-    if ((a.layout.words + 255) / 256 > waves) return GTS_ERR_SHAPE;
-    if (!geo.deals) a.counters = nullptr;
-    static const bool once = (allow_big_lds(spmm_cluster_stream_kernel<BWD, ARGB, WHATIF, 1, false>),
-                              allow_big_lds(spmm_cluster_stream_kernel<BWD, ARGB, WHATIF, 1, true>),
-                              allow_big_lds(spmm_cluster_stream_kernel<BWD, ARGB, WHATIF == 0 ? 0 : WHATIF, WHATIF == 0 ? 2 : 1, false>),
-                              allow_big_lds(spmm_cluster_stream_kernel<BWD, ARGB, WHATIF == 0 ? 0 : WHATIF, WHATIF == 0 ? 2 : 1, true>), true);
-    (void)once;
-    const dim3 g3(static_cast<unsigned>(grid));
-    if constexpr (WHATIF == 0) {
-      if (depth == 2) {
-        if (a.counters != nullptr) spmm_cluster_stream_kernel<BWD, ARGB, 0, 2, true><<<g3, waves * kWave, wg_lds, st>>>(a);
-        else spmm_cluster_stream_kernel<BWD, ARGB, 0, 2, false><<<g3, waves * kWave, wg_lds, st>>>(a);
-        return launch_status();
-      }
-    }
-    if (a.counters != nullptr) spmm_cluster_stream_kernel<BWD, ARGB, WHATIF, 1, true><<<g3, waves * kWave, wg_lds, st>>>(a);
-    else spmm_cluster_stream_kernel<BWD, ARGB, WHATIF, 1, false><<<g3, waves * kWave, wg_lds, st>>>(a);
-    return launch_status();
-  }
+  const ClusterGeometry geo = cluster_geometry(a.n_clusters, a.layout.words, p.slot_bytes, p.image_off, BWD);
+  a.deal_off = static_cast<int>(geo.wg_lds) - kDealBytes;
+  if (geo.wg_lds > kMaxLds || a.layout.words > 512) return GTS_ERR_SHAPE;
+  a.ring = geo.depth;
+  if (a.max_srcs > 64 * geo.waves) return GTS_ERR_SHAPE;
+  // fetch_record: wave p brings piece p of a record.  A workgroup of fewer waves than pieces (GTS_OPT_CLUSTER_CONSUMERS = 1,
+  // records of more than 256 words) would reduce from a piece nobody fetched: refused, as the GAT launch refuses it
+  if ((a.layout.words + 255) / 256 > geo.waves) return GTS_ERR_SHAPE;
+  if (!geo.deals) a.counters = nullptr;
+  const bool deals = a.counters != nullptr;   // the geometry asks for it AND the caller gave counters
+  const auto go = geo.depth == 2 ? (deals ? launch_persistent<spmm_cluster_stream_kernel<BWD, ARGB, 2, true>, ClusterArgs>
+                                               : launch_persistent<spmm_cluster_stream_kernel<BWD, ARGB, 2, false>, ClusterArgs>)
+                                  : (deals ? launch_persistent<spmm_cluster_stream_kernel<BWD, ARGB, 1, true>, ClusterArgs>
+                                               : launch_persistent<spmm_cluster_stream_kernel<BWD, ARGB, 1, false>, ClusterArgs>);
+  return go(a, geo.grid, geo.waves, geo.wg_lds, st);
 }
 
 }  // namespace
@@ -708,7 +650,7 @@ extern "C" int32_t gts_cluster_uses_counters(int64_t n_clusters, int32_t max_row
   using namespace gts;
   if (n_clusters <= 0 || max_rows < 1 || max_srcs < 1 || loc_words < 0) return 0;
   const LdsPlan p = lds_plan(max_rows, max_srcs, loc_words, backward != 0);
-  return cluster_geometry(n_clusters, rec_layout(max_rows, max_srcs, loc_words, backward != 0).words, p.slot_bytes, p.image_off, backward != 0, false).deals ? 1 : 0;
+  return cluster_geometry(n_clusters, rec_layout(max_rows, max_srcs, loc_words, backward != 0).words, p.slot_bytes, p.image_off, backward != 0).deals ? 1 : 0;
 }
 
 extern "C" int32_t gts_spmm_max_fwd_cluster_f32(const int32_t* rec, int64_t n_clusters, int32_t max_rows, int32_t max_srcs,

@@ -1,6 +1,7 @@
 """Where the persistent clustered K1 / K2 kernel spends its time: the same launch with the row gathers switched
 off (records + reduction + stores only) and with the reduction switched off (records + gathers only), on B lattice
-graphs, tensors rotated so that inputs come from HBM.  Usage: python tools/diag/cluster_whatif.py [graphs ...]"""
+graphs, tensors rotated so that inputs come from HBM.  The kernel timed is the frozen copy with these switches in
+tools/diag/spmm_cluster_whatif.inc (built through cluster_whatif.hip), not the library's.  Usage: python tools/diag/cluster_whatif.py [graphs ...]"""
 import ctypes
 import os
 import subprocess

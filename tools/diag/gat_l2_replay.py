@@ -1,5 +1,5 @@
 """What an XCD's L2 keeps of the clustered GAT forward's gathers when the units pass through it strictly in order (tools/diag): the
-gathers-only form of the streaming kernel (what-if 2) with ONE workgroup per XCD (grid 8) and with 2 / 8 / 64 per XCD, walking the whole
+gathers-only form of the streaming kernel (what-if 2 of tools/diag/gat_cluster_whatif.inc) with ONE workgroup per XCD (grid 8) and with 2 / 8 / 64 per XCD, walking the whole
 span slice by slice (group 100000) or 16 clusters through all their slices.  Run under rocprofv3 --pmc FETCH_SIZE; the offline model
 (tools/diag/l2_halo_sim.py: 4 MiB LRU) says 1.08 x the table for the whole-span walk, 1.66 x for groups of 16.
 Usage: rocprofv3 --pmc FETCH_SIZE ... -- python tools/diag/gat_l2_replay.py"""

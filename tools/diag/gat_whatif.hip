@@ -1,9 +1,11 @@
-// Diagnostic translation unit (never part of libgts_hip.so): the forward streaming kernel of
-// gnn-tumor-seg_amd/csrc/gts_gat_cluster.hip alone (the weight blocks in `workspace` come from a regular call before) with parts
+// Diagnostic translation unit (never part of libgts_hip.so): the forward streaming kernel as frozen in
+// tools/diag/gat_cluster_whatif.inc (the product kernel of gnn-tumor-seg_amd/csrc/gts_gat_cluster.hip carries no timing arms and runs
+// depth 1 only) alone (the weight blocks in `workspace` come from a regular call before) with parts
 // of its work switched off — timing only, wrong results: whatif 0 = everything, 1 = no neighbour gathers (records, weights,
 // reduction, stores), 2 = gathers and records but no reduction / stores, 3 = everything but the stores.
 // Built and driven by tools/diag/gat_whatif.py.
 #include "../../gnn-tumor-seg_amd/csrc/gts_gat_cluster.hip"
+#include "gat_cluster_whatif.inc"
 
 static int g_whatif_grid = 0;    // workgroups of the launch (0 = the library's choice); 8 = ONE per XCD: the span's units strictly in order
 static int g_whatif_depth = 1;
@@ -13,7 +15,7 @@ extern "C" int gts_whatif_gat_fwd(const int32_t* rec, int64_t n_clusters, int32_
                                   const float* ft, const float* bias, int32_t activation, float* out, float* workspace, int64_t n,
                                   int64_t heads, int32_t whatif, void* stream) {
   using namespace gts;
-  const GatPlan p = gat_plan(max_rows, max_srcs, loc_words, false, false, false, g_whatif_depth);
+  const GatWhatifPlan p = gat_whatif_plan(max_rows, max_srcs, loc_words, false, false, false, g_whatif_depth);
   GatClusterArgs a{};
   a.rec = rec, a.layout = rec_layout(max_rows, max_srcs, loc_words, false), a.n_clusters = static_cast<int>(n_clusters), a.max_srcs = max_srcs;
   a.table = ft, a.side = workspace, a.vec = bias, a.out = out;
@@ -25,11 +27,11 @@ extern "C" int gts_whatif_gat_fwd(const int32_t* rec, int64_t n_clusters, int32_
   a.vec_bytes = static_cast<unsigned>(heads * kF * 4);
   a.heads = static_cast<int>(heads), a.act = activation, a.nt = g_whatif_nt;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (whatif == 1) return launch_gat_cluster<0, 1, 3>(a, p, st, g_whatif_grid);
-  if (whatif == 2) return launch_gat_cluster<0, 2, 3>(a, p, st, g_whatif_grid);
-  if (whatif == 3) return launch_gat_cluster<0, 3, 3>(a, p, st, g_whatif_grid);
-  if (whatif == 9) return launch_gat_cluster<0, 9, 3>(a, p, st, g_whatif_grid);   // out = stamp buffer
-  return launch_gat_cluster<0, 0, 3>(a, p, st, g_whatif_grid);
+  if (whatif == 1) return launch_gat_cluster_whatif<0, 1, 3>(a, p, st, g_whatif_grid);
+  if (whatif == 2) return launch_gat_cluster_whatif<0, 2, 3>(a, p, st, g_whatif_grid);
+  if (whatif == 3) return launch_gat_cluster_whatif<0, 3, 3>(a, p, st, g_whatif_grid);
+  if (whatif == 9) return launch_gat_cluster_whatif<0, 9, 3>(a, p, st, g_whatif_grid);   // out = stamp buffer
+  return launch_gat_cluster_whatif<0, 0, 3>(a, p, st, g_whatif_grid);
 }
 
 extern "C" void gts_whatif_grid(int32_t grid) { g_whatif_grid = grid; }

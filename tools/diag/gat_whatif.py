@@ -1,6 +1,7 @@
 """Where the clustered GAT forward aggregation spends its time (tools/diag): the streaming kernel alone with the neighbour gathers,
 the reduction or the stores switched off, for gather depths 1 - 3 and 1 / 2 workgroups per CU, on the C3 hidden-layer shape
-(B lattice graphs, 4 heads x 256).  Tables rotated so that inputs come from HBM.  Usage: python tools/diag/gat_whatif.py [graphs]"""
+(B lattice graphs, 4 heads x 256).  Tables rotated so that inputs come from HBM.  The kernel timed is the frozen copy with these switches
+in tools/diag/gat_cluster_whatif.inc (built through gat_whatif.hip), not the library's.  Usage: python tools/diag/gat_whatif.py [graphs]"""
 import ctypes
 import os
 import subprocess
